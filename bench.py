@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the GFLA feature-warping hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch of B synthetic images
@@ -158,6 +158,26 @@ class HotPath:
             outs += [resample(feat, flow) for feat, (_, _, flow) in zip(self.vgg, self.inputs)]
         return self._backward(outs, allreduce)
 
+    def named_results(self, outs):
+        """What a caller of the step receives, by name: the forward outputs it returned and the gradients it left on the
+        inputs and the FC parameters."""
+        res = {}
+        for (name, _, _, _, _), o in zip(LAYERS, outs):
+            res[name + "_out"] = o
+        if self.losses is not None:
+            res["losses"] = outs[len(LAYERS)]
+        else:
+            for (name, _, _, _), o in zip(VGG, outs[len(LAYERS):]):
+                res[name + "_warp"] = o
+        for (name, _, _, _, _), (src, tgt, flow) in zip(LAYERS, self.inputs):
+            res.update({name + "_grad_source": src.grad, name + "_grad_target": tgt.grad, name + "_grad_flow": flow.grad})
+        for (name, _, _, _), feat in zip(VGG, self.vgg):
+            res[name + "_grad_feat"] = feat.grad
+        for (name, _, _, _, _), mod in zip(LAYERS, self.attn):
+            for pn, p in mod.named_parameters():
+                res[name + "_grad_" + pn] = p.grad
+        return res
+
     def _backward(self, outs, allreduce):
         if self.upstream is None:
             gen = torch.Generator(device=outs[0].device).manual_seed(4321)
@@ -232,6 +252,16 @@ class FacePath:
             self.reducer.finish()
         return outs
 
+    def named_results(self, outs):
+        res = {}
+        for i, o in enumerate(outs):  # frame-major, layer-minor (step())
+            res["frame%d_%s_out" % (i // len(FACE_LAYERS), FACE_LAYERS[i % len(FACE_LAYERS)][0])] = o
+        for i, t in enumerate(self.leaves()):
+            res["grad_leaf%03d" % i] = t.grad
+        for i, p in enumerate(self.params()):
+            res["grad_param%03d" % i] = p.grad
+        return res
+
     def describe(self, args, world):
         return {
             "metric": "frames/sec (fwd+bwd) FaceGenerator 256x256 attn_layer=2,3, bf16 features -- feature-warping hot path",
@@ -285,6 +315,12 @@ class TrainerPath:
         self.losses = self.shell.optimize_parameters((self.source, self.source_B, self.target_B), self.target,
                                                      source=self.source)
         return self.losses
+
+    def named_results(self, losses):
+        """The losses of the step and the parameters after its Adam update."""
+        res = {"loss_" + k: torch.tensor(float(v), dtype=torch.float64) for k, v in losses.items()}
+        res.update({"param_" + n: p for n, p in self.net.named_parameters()})
+        return res
 
     def describe(self, args, world):
         nparam = sum(p.numel() for p in self.params())
@@ -964,6 +1000,20 @@ def oracle_check(hp, resample, tol=1e-4):
             "max_abs": max_abs, "max_rel": max_rel}
 
 
+CPU_BASELINE_MAX_WORKERS = 4   # + the benchmark process itself: at most 5 processes that have loaded the HIP runtime
+
+
+def cgroup_cpu_quota():
+    """CPUs granted by the cgroup v2 `cpu.max` quota of this process (a large number when there is none)."""
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            return max(1, int(int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return 1 << 20
+
+
 def cpu_baseline(budget_s=20.0):
     """The reference composition on the host cores with the oracle kernels (kind "port").
 
@@ -979,7 +1029,10 @@ def cpu_baseline(budget_s=20.0):
     except AttributeError:
         usable = list(range(host))
     per = 16
-    workers = max(1, min(len(usable) // per, 16))
+    # Every worker imports torch (ROCm build) and counts as a process with the GPU open, next to this one: a shared GPU
+    # host may refuse more than a handful of those.  The cgroup CPU quota, where there is one, bounds the cores the
+    # workers can really use, whatever the affinity mask shows.
+    workers = max(1, min(len(usable) // per, cgroup_cpu_quota() // per, CPU_BASELINE_MAX_WORKERS))
     budget = max(5.0, min(budget_s, 20.0))
     start_at = time.time() + 30.0          # imports + the warm-up step of every worker fit in here; late workers start at once
     procs = []
@@ -1161,6 +1214,40 @@ def timed_steps(step, steps, warmup, barrier, world, device):
     return elapsed
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # everything --dump-outputs writes, .npy headers included
+
+
+def dump_outputs(out_dir, results, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write every array of `results` (name -> tensor; None entries are skipped) as out_dir/<name>.npy in
+    float32 (float64 stays float64).  The budget is shared out smallest array first: arrays that fit what is left per
+    remaining array are written whole, the others are replaced by a fixed sample of their flattened elements (sorted
+    indices drawn without replacement by numpy's default_rng seeded with the CRC-32 of the name, so two runs with the same
+    arguments sample the same positions).  Returns {name: description}."""
+    import zlib
+    import numpy as np
+    results = {k: (v.detach().double() if v.dtype == torch.float64 else v.detach().float())
+               for k, v in results.items() if v is not None}
+    os.makedirs(out_dir, exist_ok=True)
+    caps, left = {}, budget
+    for i, name in enumerate(sorted(results, key=lambda k: results[k].numel() * results[k].element_size())):
+        t = results[name]
+        share = left // (len(results) - i) - 128      # (the .npy header)
+        caps[name] = max(1, min(t.numel(), share // t.element_size()))
+        left -= caps[name] * t.element_size() + 128
+    info = {}
+    for name, t in results.items():
+        flat = t.reshape(-1)
+        n, cap = flat.numel(), caps[name]
+        desc = {"shape": list(t.shape), "dtype": str(flat.dtype).replace("torch.", "")}
+        if n > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, size=cap, replace=False))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+            desc["sampled"] = cap
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy() if "sampled" in desc else t.cpu().numpy())
+        info[name] = desc
+    return info
+
+
 def run(args, make_hotpath, make_resample, rank, world, device, on_gpu=True, data="synthetic"):
     """Everything after process-group / device setup; `make_hotpath(fc_mode)` builds the per-rank workload.  Split from
     main() so that the N>1 control flow can be exercised on CPU under gloo with a stand-in workload
@@ -1182,8 +1269,18 @@ def run(args, make_hotpath, make_resample, rank, world, device, on_gpu=True, dat
     # (Capturing the whole step -- forward + backward, ~90 launches -- into one hipGraph was measured twice and dropped:
     # round 1 7.146 ms replayed vs 7.147 ms eager, round 4 4.71 vs 4.69 ms (profiles/r4_hipgraph_step.json).  The gaps
     # between dependent kernels are the same inside a graph; the step is not launch-bound.)
-    step = lambda: hp.step(resample)
+    dump_dir = getattr(args, "dump_outputs", None)
+    last = []
+    if dump_dir:  # keep what the last timed step returned (a reference only; nothing is copied inside the timed region)
+        def step():
+            last[:] = [hp.step(resample)]
+    else:
+        step = lambda: hp.step(resample)
     elapsed = timed_steps(step, args.steps, args.warmup, barrier, world, device)
+    dumped = None
+    if dump_dir and rank == 0:
+        dumped = dump_outputs(dump_dir, hp.named_results(last[0]))
+    del last[:]
     # The oracle check runs AFTER the timed region: it is 16 OpenMP threads of host work, and worker threads still spinning
     # behind their last parallel region compete with the launching thread -- a timed region started right behind the
     # check was measured at 5.4 / 6.2 ms per step instead of 4.7 on two occasions.  It still fails the run on a mismatch.
@@ -1349,6 +1446,8 @@ def run(args, make_hotpath, make_resample, rank, world, device, on_gpu=True, dat
                                         "events around the call; peak = dense matrix-core rate of the operand type"}
     if variants:
         line["variants"] = variants
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": dump_dir, "arrays": dumped}
     if world > 1:   # every rank takes part (collectives); the fingerprint proves N ranks met on the backend
         line["dist"] = dist_leg(args, rank, world, device, on_gpu, barrier,
                                 tile_shape=None if on_gpu else (args.batch, 3, 8, 6))
@@ -1513,7 +1612,13 @@ def parse_args(argv=None):
                          "config 4): PerceptualCorrectness.calculate_loss on synthetic VGG-shaped features + "
                          "MultiAffineRegularizationLoss on the flow fields (no oracle check / CPU baseline for this leg)")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its outputs and the gradients it "
+                         "left, or for trainer_step its losses and updated parameters) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all: larger arrays are replaced by a fixed, seeded sample of their elements")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.with_losses:
         args.no_cpu_baseline = True
     return args
@@ -1565,6 +1670,11 @@ class _ControlFlowStub(object):
         if allreduce:
             self.reducer.finish()
         return [out]
+
+    def named_results(self, outs):
+        res = {"output": outs[0]}
+        res.update({"grad_" + n: p.grad for n, p in self.net.named_parameters()})
+        return res
 
 
 def main_cpu_stub(args):

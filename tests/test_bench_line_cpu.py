@@ -58,3 +58,39 @@ def test_last_stdout_line_of_an_n2_run_is_short_and_detail_goes_to_a_file(tmp_pa
     assert line["n_gpus"] == 2 and line["dist"]["world_size_seen_by_group"] == 2
     full = json.load(open(detail))
     assert full["value"] == line["value"] and "kernels" in full
+
+
+def test_dump_outputs_writes_the_last_step_identically_across_runs(tmp_path):
+    """`--dump-outputs DIR` (GFLA_BENCH_CPU_STUB, one rank): the arrays of the last timed step as DIR/<name>.npy in
+    float32, the same bytes from two runs with the same arguments; --steps is the number of timed steps."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(GFLA_BENCH_CPU_STUB="1", OMP_NUM_THREADS="1", BENCH_DETAIL=str(tmp_path / "detail.json"))
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads(res.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        dumps.append({f: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))})
+    assert set(dumps[0]) == {"output.npy", "grad_weight.npy", "grad_bias.npy"}
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, dumps[1][name]), name
+
+
+def test_dump_outputs_samples_large_arrays_within_the_budget(tmp_path):
+    """Arrays beyond their share of the budget become a fixed, seeded sample; small ones are written whole."""
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(1 << 20, dtype=torch.float32)
+    results = {"big": big, "small": torch.ones(3, 4, dtype=torch.float64), "none": None}
+    info = [bench.dump_outputs(str(tmp_path / d), results, budget=256 << 10) for d in ("a", "b")]
+    assert info[0] == info[1] and "sampled" in info[0]["big"] and "sampled" not in info[0]["small"] and "none" not in info[0]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))) <= 256 << 10
+    a, b = np.load(str(tmp_path / "a" / "big.npy")), np.load(str(tmp_path / "b" / "big.npy"))
+    assert np.array_equal(a, b) and a.size == info[0]["big"]["sampled"] and np.all(np.diff(a) > 0)   # sorted distinct indices
+    small = np.load(str(tmp_path / "a" / "small.npy"))
+    assert small.dtype == np.float64 and small.shape == (3, 4)
