@@ -68,6 +68,8 @@ _SINGLE = {
     "gfla_mask_blend_fwd_bf16": [_ptr] * 6 + [_i64] * 3 + [_ptr],
     "gfla_mask_blend_bwd_f32": [_ptr] * 11 + [_i64] * 3 + [_ptr],
     "gfla_mask_blend_bwd_bf16": [_ptr] * 11 + [_i64] * 3 + [_ptr],
+    "gfla_gemm_f64_workspace_bytes": [_i64] * 3 + [_int],
+    "gfla_gemm_f64": [_ptr] * 6 + [_i64] * 3 + [_int, _int, _ptr, _ptr],
 }
 # bf16 storage exists for every entry point below; the backward ones return the reductions over channels (grad_flow,
 # grad_logits, grad_in2) in float32 (include/gfla_hip.h)
@@ -229,7 +231,8 @@ ABI_VERSION = 8
 PATH_BE_BWD_LDS, PATH_BE_BWD_GLOBAL, PATH_FC_FWD_MODE0, PATH_FC_BWD_MODE0, PATH_BE_FWD_PIX = 0, 1, 2, 7, 12
 # round 5: the big-plane kernels (few planes, each beyond the LDS budget; csrc/tile_map.h)
 PATH_BE_FWD_GPIX, PATH_BE_BWD_TILE, PATH_RS_FWD_BIG, PATH_RS_BWD1_TILE, PATH_RS_BWD2_BIG = 13, 14, 15, 16, 17
-PATH_FC_FWD_MODE5, PATH_FC_BWD_MODE5, PATH_COUNT = 18, 19, 20
+PATH_FC_FWD_MODE5, PATH_FC_BWD_MODE5 = 18, 19
+PATH_GEMM_F64, PATH_COUNT = 20, 21   # float64 FC layers of ExtractorAttn (csrc/gemm_f64.hip)
 
 
 def fc_path(mode, backward=False):

@@ -21,14 +21,15 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import _lib, fc_mfma
+from . import _lib, fc_f64, fc_mfma
 from .block_extractor import BlockExtractor
 from .local_attn_reshape import LocalAttnReshape
 
 _FUSED_MAX_K = 5  # kernel sizes the fused tail is instantiated for
 
-# What happens when a module's FC layers are NOT taken by this library's own MFMA kernels (kernel_size other than 3 / 5 --
-# the reference's constructor default is 4, base_function.py:791 --, float64 features, maps whose tiles exceed the LDS)
+# float64 features take the FP64 matrix-core path (fc_f64.py, every kernel size the fused block takes).  What happens when
+# a module's FC layers are NOT taken by this library's own kernels (float32 with kernel_size other than 3 / 5 -- the
+# reference's constructor default is 4, base_function.py:791 --, float32 maps whose tiles exceed the LDS)
 # and would run through torch.mm / F.conv2d, i.e. rocBLAS / MIOpen:
 #   "warn"  (package default, also after install())  warn once per module, then run the vendor path
 #   "error" (install(strict_mfma=True) / GFLA_STRICT_MFMA=1 / bench.py)  raise: nobody benchmarks or ships the vendor
@@ -222,10 +223,11 @@ class FcTailFunction(Function):
     """logits = conv1x1(lrelu(hs + ht + b0)) in one pass each way (csrc/fc_tail.hip; base_function.py:799-803).
 
     hs, ht: the two halves of the first FC convolution, (B, Hc, H, W); hs may be the permuted view of the
-    GEMM's (Hc, B, H, W) output -- it is read, and its gradient written, in that layout.  w1 (KK, Hc)."""
+    GEMM's (Hc, B, H, W) output -- it is read, and its gradient written, in that layout.  w1 (KK, Hc).
+    own_wgrad (float64 only): dW1 on this library's FP64 matrix-core GEMM (fc_f64.wgrad_fc1) instead of torch.bmm."""
 
     @staticmethod
-    def forward(ctx, hs, ht, b0, w1, b1, slope):
+    def forward(ctx, hs, ht, b0, w1, b1, slope, own_wgrad=False):
         _lib.require_gpu(hs, ht, w1)
         B, Hc, H, W = hs.shape
         if tuple(ht.shape) != (B, Hc, H, W):
@@ -243,6 +245,7 @@ class FcTailFunction(Function):
                   _lib.ptr(ht), _lib.ptr(b0), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(logits), B, Hc, H * W, KK,
                   float(slope))
         ctx.slope = slope
+        ctx.own_wgrad = bool(own_wgrad) and ht.dtype == torch.float64
         ctx.save_for_backward(hs, ht, b0, w1, b1)
         return logits
 
@@ -265,9 +268,11 @@ class FcTailFunction(Function):
         g_b0 = sums[:Hc] if want_b0 else None
         g_b1 = sums[Hc:] if want_b1 else None
         g_w1 = None
-        if need_w1:  # dW1 = sum_b g_logits_b act_b^T: a (KK x HW) x (HW x Hc) GEMM per sample
+        if need_w1 and ctx.own_wgrad:
+            g_w1 = fc_f64.wgrad_fc1(g_logits, act)
+        elif need_w1:  # dW1 = sum_b g_logits_b act_b^T: a (KK x HW) x (HW x Hc) GEMM per sample
             g_w1 = torch.bmm(g_logits.view(B, KK, H * W), act.view(B, Hc, H * W).transpose(1, 2)).sum(0)
-        return (g_hs if need_hs else None), g_ht, g_b0, g_w1, g_b1, None
+        return (g_hs if need_hs else None), g_ht, g_b0, g_w1, g_b1, None, None
 
 
 def _tail_slope(act):
@@ -291,7 +296,7 @@ def _tail_fusable(self, conv0, act, conv1, dtype, k):
 
 def _fc_layers_fit(source, target, flow_field, conv0, act, conv1, k):
     """The module IS the reference's ExtractorAttn layout (base_function.py:799-803) and the three maps line up: what
-    both MFMA evaluations (f32 and bf16 features) require."""
+    the MFMA evaluations (f32, bf16 and f64 features) require."""
     return (_tail_slope(act) is not None
             and source.shape == target.shape and source.shape[2:] == flow_field.shape[2:]
             and source.size(0) == flow_field.size(0) and flow_field.size(1) == 2
@@ -334,6 +339,35 @@ def _bf16_path_ok(self, source, target, flow_field, conv0, act, conv1, last, k):
     # the LDS-plane limit belongs to the bf16 aggregate backward only; the default backward (BF16_BACKWARD_F32_AGGREGATE)
     # goes through gfla_local_attn_aggregate_bwd_ws_f32, which has no such limit
     return not needs_bwd or BF16_BACKWARD_F32_AGGREGATE or _bf16_backward_supported(source.size(2), source.size(3))
+
+
+def _f64_path_ok(self, source, target, flow_field, conv0, act, conv1, k):
+    """float64 features and parameters in the reference's layout: both FC layers on gfla_gemm_f64 (fc_f64.py)."""
+    return (getattr(self, "fc_impl", "mfma") == "mfma"
+            and source.dtype == target.dtype == flow_field.dtype == torch.float64
+            and conv0.weight.dtype == conv1.weight.dtype == torch.float64
+            and _fc_layers_fit(source, target, flow_field, conv0, act, conv1, k)
+            and _tail_fusable(self, conv0, act, conv1, torch.float64, k))
+
+
+def _fused_attention_f64(self, source_c, target_c, flow_c, conv0, act, conv1, last, k):
+    """The library path's formulation (see _fused_attention) with every product on the FP64 matrix cores: the first
+    FC layer reads the two extractor outputs in place (Fc0F64Function), the tail's dW1 is gfla_gemm_f64 too."""
+    zero_flow = torch.zeros_like(flow_c)
+    link = None
+    if getattr(self, "unfold_gemm", True) and _lib.unfold_supported(source_c.size(2), source_c.size(3), k, 8):
+        link = _SourceGradLink() if getattr(self, "fuse_source_backward", True) else None
+        u_s = BlockExtractorUnfoldFunction.apply(source_c, flow_c, k, True, link)    # (C*k*k, B, H, W)
+        u_t = BlockExtractorUnfoldFunction.apply(target_c, zero_flow, k, True, None)
+        blocks = False
+    else:  # planes beyond the unfold kernels' LDS budget: the reference block layout, (B, C, H*k, W*k)
+        u_s = self.extractor(source_c, flow_c)
+        u_t = self.extractor(target_c, zero_flow)
+        blocks = True
+    hidden_s, hidden_t = fc_f64.Fc0F64Function.apply(conv0.weight, u_t, u_s, k, blocks)
+    logits = FcTailFunction.apply(hidden_s, hidden_t, conv0.bias, conv1.weight.view(conv1.out_channels, -1), conv1.bias,
+                                  _tail_slope(act), True)
+    return _aggregate(source_c, flow_c, logits, last, k, link)
 
 
 class FusedAttnFunction(Function):
@@ -537,6 +571,8 @@ def _fused_attention(self, source, target, flow_field):
         with torch.autocast(device_type="cuda", enabled=False):
             attn, result = _fused_attention_f32_module(self, source.float(), target.float(), flow_field.float())
         return attn.to(torch.bfloat16), result.to(torch.bfloat16)
+    if _f64_path_ok(self, source_c, target, flow_c, conv0, act, conv1, k):
+        return _fused_attention_f64(self, source_c, target.contiguous(), flow_c, conv0, act, conv1, last, k)
     mode = _mfma_mode(self, source_c, target, flow_c, conv0, act, conv1, k)
     if mode is not None:
         # both FC layers on the matrix cores: no block tensor, no library GEMM / convolution (fc_mfma.py)
@@ -552,7 +588,8 @@ def _fused_attention(self, source, target, flow_field):
     if getattr(self, "fc_impl", "mfma") == "mfma":   # not an explicit request for the vendor path
         policy = getattr(self, "vendor_fallback", VENDOR_FALLBACK)
         what = ("ExtractorAttn(kernel_size=%d, %s, %s): this configuration is not taken by the library's own MFMA kernels "
-                "(kernel_size 3 / 5, float32 or bfloat16 features, 128 hidden channels, maps whose tiles fit the LDS); its FC "
+                "(kernel_size 3 / 5, float32 or bfloat16 features, 128 hidden channels, maps whose tiles fit the LDS; float64 "
+                "features in the reference's layout); its FC "
                 "layers would run through torch.mm / F.conv2d (rocBLAS / MIOpen)" % (k, source.dtype, tuple(source.shape)))
         if policy == "error":
             raise VendorFallbackError(what + ".  Strict mode is on (install(strict_mfma=True) / GFLA_STRICT_MFMA); set module.vendor_fallback = "

@@ -41,9 +41,9 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     already importable.  Returns the reference's `model.networks.base_function` module when it
     could be imported, else None.
 
-    strict_mfma: an ExtractorAttn configuration this library's own MFMA kernels do not take (kernel_size other than
-    3 / 5 -- the reference's constructor default is 4 --, float64 features and gradcheck, maps too large for the LDS tiles)
-    runs its FC layers through rocBLAS / MIOpen, with ONE warning per module, and every such call is counted
+    strict_mfma: an ExtractorAttn configuration this library's own MFMA kernels do not take (float32 with kernel_size
+    other than 3 / 5 -- the reference's constructor default is 4 --, float32 maps too large for the LDS tiles; float64
+    features, gradcheck included, run on the FP64 matrix cores) runs its FC layers through rocBLAS / MIOpen, with ONE warning per module, and every such call is counted
     (extractor_attn.vendor_fallback_calls): a drop-in must not turn a working reference configuration into a failure.
     strict_mfma=True (or GFLA_STRICT_MFMA=1 in the environment) makes it RAISE extractor_attn.VendorFallbackError instead
     -- what a benchmark or a deployment that must not ship vendor kernels by accident wants (bench.py sets it).  None

@@ -129,7 +129,8 @@ enum gfla_path {
   GFLA_PATH_RS_BWD2_BIG = 17,  /*   resample2d d/d input2 */
   GFLA_PATH_FC_FWD_MODE5 = 18, /* round 6: gfla_fc_forward_f32 / gfla_fc_backward_f32 in arithmetic mode 5 */
   GFLA_PATH_FC_BWD_MODE5 = 19,
-  GFLA_PATH_COUNT = 20
+  GFLA_PATH_GEMM_F64 = 20,     /* gfla_gemm_f64 (float64 FC layers of ExtractorAttn on the FP64 matrix cores) */
+  GFLA_PATH_COUNT = 21
 };
 int64_t gfla_path_count(int path);
 
@@ -470,6 +471,23 @@ int gfla_replicate_pad_bwd_f32(const float *grad_padded, float *grad_in, int64_t
 int gfla_replicate_pad_bwd_f64(const double *grad_padded, double *grad_in, int64_t planes, int64_t H,
                                int64_t W, int pad_left, int pad_right, int pad_top, int pad_bottom,
                                gfla_stream_t stream);
+
+/* ---- float64 GEMM on the FP64 matrix cores (csrc/gemm_f64.hip): ExtractorAttn's FC layers in float64 -----------
+ *   C[m,n] = beta*C[m,n] + sum_k A[m,k] * B[k,n],   beta 0 or 1 (beta 0 never reads C).
+ * Each operand is a strided VIEW given by 12 int64 (host memory, read during the call):
+ *   {row d0, d1, d2, s0, s1, s2,  col d0, d1, d2, s0, s1, s2}
+ * the logical row index r = (r0*d1 + r1)*d2 + r2 sits at element offset r0*s0 + r1*s1 + r2*s2 from the operand's
+ * pointer (likewise the column), so d0*d1*d2 must equal the extent (M / K for A, K / N for B, M / N for C); every
+ * d >= 1.  C must not overlap A or B, and distinct (row, col) of C must be distinct elements.
+ * split_k: 0 auto, 1 off, s > 1 about s slices of K (each a multiple of 16 long) summed in a fixed order by a second
+ * pass: results are bit-identical from run to run.  workspace: gfla_gemm_f64_workspace_bytes(M, N, K, split_k) bytes
+ * (may be 0: then NULL is fine), 8-byte aligned; -1 for negative arguments.
+ * NULL -> -1; negative extents, beta other than 0 / 1, a view that does not tile its extent -> -2; extents beyond
+ * 2^31 -> -3. */
+int64_t gfla_gemm_f64_workspace_bytes(int64_t M, int64_t N, int64_t K, int split_k);
+int gfla_gemm_f64(double *c, const int64_t *c_view, const double *a, const int64_t *a_view, const double *b,
+                  const int64_t *b_view, int64_t M, int64_t N, int64_t K, int beta, int split_k, void *workspace,
+                  gfla_stream_t stream);
 
 /* ---- best-match cosine similarity of the sampling-correctness loss ----------------
  * Replaces, in PerceptualCorrectness.calculate_loss (external_function.py:255-268),
