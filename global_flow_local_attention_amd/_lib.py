@@ -61,6 +61,7 @@ _SINGLE = {
     "gfla_xcd_swizzle": [_i64, _i64],
     "gfla_local_attn_aggregate_fwd_ws_f32": [_ptr] * 6 + [_i64] * 6 + [_int, _int, _ptr],
     "gfla_local_attn_aggregate_fwd_ws_bf16": [_ptr] * 6 + [_i64] * 6 + [_int, _int, _ptr],
+    "gfla_local_attn_aggregate_fwd_ws_f16": [_ptr] * 6 + [_i64] * 6 + [_int, _int, _ptr],
     "gfla_local_attn_aggregate_bwd_ws_f32": [_ptr] * 8 + [_i64] * 6 + [_int, _int, _ptr],
     "gfla_resample2d_bwd_ws_f32": [_ptr] * 6 + [_i64] * 6 + [_int, _int, _int, _ptr],
     "gfla_convert_multi": [_ptr, _ptr, _i64] * 4 + [_int, _ptr],
@@ -68,10 +69,13 @@ _SINGLE = {
     "gfla_mask_blend_fwd_bf16": [_ptr] * 6 + [_i64] * 3 + [_ptr],
     "gfla_mask_blend_bwd_f32": [_ptr] * 11 + [_i64] * 3 + [_ptr],
     "gfla_mask_blend_bwd_bf16": [_ptr] * 11 + [_i64] * 3 + [_ptr],
+    "gfla_mask_blend_fwd_f16": [_ptr] * 6 + [_i64] * 3 + [_ptr],
+    "gfla_mask_blend_bwd_f16": [_ptr] * 11 + [_i64] * 3 + [_ptr],
+    "gfla_fc_forward_f16": [_ptr] * 9 + [_i64] * 4 + [_int, ctypes.c_double, _ptr],
     "gfla_gemm_f64_workspace_bytes": [_i64] * 3 + [_int],
     "gfla_gemm_f64": [_ptr] * 6 + [_i64] * 3 + [_int, _int, _ptr, _ptr],
 }
-# bf16 storage exists for every entry point below; the backward ones return the reductions over channels (grad_flow,
+# bf16 and f16 storage exist for every entry point below; the backward ones return the reductions over channels (grad_flow,
 # grad_logits, grad_in2) in float32 (include/gfla_hip.h)
 _FWD_ONLY_BF16 = set()
 
@@ -80,7 +84,7 @@ def exported_symbols():
     """Every symbol include/gfla_hip.h declares."""
     names = ["gfla_abi_version", "gfla_status_string", "gfla_set_tuning", "gfla_path_count", "gfla_unfold_supported"]
     for base in _SIGNATURES:
-        for sfx in ("f32", "f64", "bf16"):
+        for sfx in ("f32", "f64", "bf16", "f16"):
             if sfx == "bf16" and base in _FWD_ONLY_BF16:
                 continue
             names.append("%s_%s" % (base, sfx))
@@ -111,7 +115,7 @@ def lib():
         handle.gfla_path_count.restype = _i64
         handle.gfla_unfold_supported.argtypes = [_i64, _i64, _int, _int]
         for base, args in _SIGNATURES.items():
-            for sfx in ("f32", "f64", "bf16"):
+            for sfx in ("f32", "f64", "bf16", "f16"):
                 if sfx == "bf16" and base in _FWD_ONLY_BF16:
                     continue
                 fn = getattr(handle, "%s_%s" % (base, sfx))
@@ -125,7 +129,9 @@ def lib():
     return _lib
 
 
-_SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}
+_SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
+# 16-bit storage types: fp32 arithmetic inside, reductions over channels in float32
+HALF_TYPES = (torch.bfloat16, torch.float16)
 
 
 def suffix(t, what, allow_bf16=True):
@@ -134,7 +140,7 @@ def suffix(t, what, allow_bf16=True):
     try:
         sfx = _SUFFIX[t.dtype]
     except KeyError:
-        raise TypeError("%s: unsupported dtype %s (float32, float64, bfloat16 forward)" % (what, t.dtype))
+        raise TypeError("%s: unsupported dtype %s (float32, float64, bfloat16, float16)" % (what, t.dtype))
     if sfx == "bf16" and not allow_bf16:
         raise TypeError("%s: bfloat16 is forward-only in this library (use float32 for training)" % what)
     return sfx
@@ -142,8 +148,8 @@ def suffix(t, what, allow_bf16=True):
 
 def reduction_like(t):
     """Zeroed buffer for a gradient that is a reduction over channels (grad_flow, grad_logits, grad_in2): float32 when the
-    storage type is bfloat16 (the bf16 backward entry points accumulate these in float32), t's dtype otherwise."""
-    return torch.zeros(t.shape, dtype=torch.float32 if t.dtype == torch.bfloat16 else t.dtype, device=t.device)
+    storage type is 16-bit (the bf16 / f16 backward entry points accumulate these in float32), t's dtype otherwise."""
+    return torch.zeros(t.shape, dtype=torch.float32 if t.dtype in HALF_TYPES else t.dtype, device=t.device)
 
 
 def scatter_workspace(ref_tensor, B, H, W, entries):
@@ -153,13 +159,13 @@ def scatter_workspace(ref_tensor, B, H, W, entries):
 
 
 def aggregate_fwd(source, flow, logits, out, attn, k, apply_softmax):
-    """softmax + aggregate forward.  f32 / bf16 storage: the coefficient-table kernels (scratch from the caching
+    """softmax + aggregate forward.  f32 / bf16 / f16 storage: the coefficient-table kernels (scratch from the caching
     allocator, csrc/local_attn_aggregate.hip); f64: the plain entry point."""
     b, c, hs, ws = source.shape
     h, w = flow.shape[2], flow.shape[3]
     sfx = suffix(source, "local_attn_aggregate")
     tail = (b, c, hs, ws, h, w, int(k), 1 if apply_softmax else 0)
-    if sfx in ("f32", "bf16"):
+    if sfx in ("f32", "bf16", "f16"):
         n = lib().gfla_aggregate_fwd_workspace_bytes(int(b), int(h), int(w), int(k))
         scratch = torch.empty(max(int(n), 16), dtype=torch.uint8, device=source.device)
         call("gfla_local_attn_aggregate_fwd_ws_" + sfx, source, ptr(source), ptr(flow), ptr(logits), ptr(out), ptr(attn),
@@ -196,14 +202,21 @@ def call(name, ref_tensor, *args):
         raise err("%s failed: %s (status %d)" % (name, lib().gfla_status_string(status).decode(), status))
 
 
+# gfla_convert_multi's flag per (from, to) pair
+_CONVERT_FLAG = {(torch.bfloat16, torch.float32): 0, (torch.float32, torch.bfloat16): 1,
+                 (torch.float16, torch.float32): 2, (torch.float32, torch.float16): 3}
+
+
 def convert_many(tensors, dtype):
-    """[t.to(dtype) for t in tensors] for bfloat16 <-> float32 CUDA tensors, up to four per launch (gfla_convert_multi);
-    None entries pass through.  Anything else (other dtypes, CPU tensors, nothing to convert) goes to torch."""
+    """[t.to(dtype) for t in tensors] for bfloat16 / float16 <-> float32 CUDA tensors, up to four per launch
+    (gfla_convert_multi); None entries pass through.  Anything else (other dtypes, CPU tensors, nothing to convert) goes to
+    torch."""
     out = list(tensors)
     todo = [i for i, t in enumerate(out) if t is not None and t.dtype != dtype]
-    pair_ok = all(out[i].is_cuda and {out[i].dtype, dtype} == {torch.bfloat16, torch.float32} for i in todo)
+    pair_ok = all(out[i].is_cuda and (out[i].dtype, dtype) in _CONVERT_FLAG for i in todo)
     if not todo or not pair_ok or len({out[i].dtype for i in todo}) != 1:
         return [None if t is None else t.to(dtype) for t in out]
+    flag = _CONVERT_FLAG[(out[todo[0]].dtype, dtype)]
     for at in range(0, len(todo), 4):
         grp = todo[at:at + 4]
         srcs = [out[i].contiguous() for i in grp]
@@ -211,7 +224,7 @@ def convert_many(tensors, dtype):
         args = []
         for j in range(4):
             args += [ptr(srcs[j]), ptr(dsts[j]), srcs[j].numel()] if j < len(grp) else [None, None, 0]
-        call("gfla_convert_multi", srcs[0], *args, 1 if dtype == torch.bfloat16 else 0)
+        call("gfla_convert_multi", srcs[0], *args, flag)
         for i, d in zip(grp, dsts):
             out[i] = d
     return out
@@ -232,7 +245,8 @@ PATH_BE_BWD_LDS, PATH_BE_BWD_GLOBAL, PATH_FC_FWD_MODE0, PATH_FC_BWD_MODE0, PATH_
 # round 5: the big-plane kernels (few planes, each beyond the LDS budget; csrc/tile_map.h)
 PATH_BE_FWD_GPIX, PATH_BE_BWD_TILE, PATH_RS_FWD_BIG, PATH_RS_BWD1_TILE, PATH_RS_BWD2_BIG = 13, 14, 15, 16, 17
 PATH_FC_FWD_MODE5, PATH_FC_BWD_MODE5 = 18, 19
-PATH_GEMM_F64, PATH_COUNT = 20, 21   # float64 FC layers of ExtractorAttn (csrc/gemm_f64.hip)
+PATH_GEMM_F64 = 20   # float64 FC layers of ExtractorAttn (csrc/gemm_f64.hip)
+PATH_FC_PACK_F16, PATH_COUNT = 21, 22   # gfla_fc_forward_f16: activation records packed straight from the float16 maps
 
 
 def fc_path(mode, backward=False):

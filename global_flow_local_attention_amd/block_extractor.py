@@ -53,7 +53,7 @@ class BlockExtractorFunction(Function):
         source, flow_field = ctx.saved_tensors
         want_source, want_flow = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         g_source = torch.zeros_like(source) if want_source else None
-        g_flow = _lib.reduction_like(flow_field) if want_flow else None  # float32 accumulator for bf16 storage
+        g_flow = _lib.reduction_like(flow_field) if want_flow else None  # float32 accumulator for 16-bit storage
         grad_patches = grad_patches.contiguous()  # the reference drops this result (:32-33)
         if (want_source or want_flow) and grad_patches.numel() > 0 and source.numel() > 0:
             B, C, Hs, Ws = source.shape
@@ -63,17 +63,20 @@ class BlockExtractorFunction(Function):
                           _lib.ptr(source), _lib.ptr(flow_field), _lib.ptr(grad_patches),
                           _lib.ptr(g_source), _lib.ptr(g_flow), B, C, Hs, Ws, Hf, Wf, ctx.kernel_size)
             except _lib.Unsupported:
-                if source.dtype != torch.bfloat16:
+                if source.dtype not in _lib.HALF_TYPES:
                     raise
-                # bfloat16 planes beyond the LDS budget (e.g. one (1,64,256,176) map): the bf16 backward exists for the
+                # 16-bit planes beyond the LDS budget (e.g. one (1,64,256,176) map): the bf16 / f16 backward exists for the
                 # planes-in-LDS kernels only -- the tile kernels accumulate into float32 / float64 windows and flush with float
-                # atomics.  Storage is widened for this call: the float32 kernels run on exact up-casts of the bf16 values, the
-                # source gradient is rounded to bf16 once at the end (one rounding per element, as the bf16 kernels do).
+                # atomics.  Storage is widened for this call: the float32 kernels run on exact up-casts of the 16-bit values,
+                # the source gradient is rounded to the storage type once at the end (one rounding per element, as the 16-bit
+                # kernels do).  The flow accumulator starts again from zero: a refused call must leave no partial sums.
                 s32, f32_, gp32 = _lib.convert_many([source, flow_field, grad_patches], torch.float32)
                 gs32 = torch.zeros_like(s32) if want_source else None
+                if g_flow is not None:
+                    g_flow.zero_()
                 _lib.call(_ENTRY_BWD + "f32", s32, _lib.ptr(s32), _lib.ptr(f32_), _lib.ptr(gp32), _lib.ptr(gs32),
                           _lib.ptr(g_flow), B, C, Hs, Ws, Hf, Wf, ctx.kernel_size)
-                g_source = None if gs32 is None else _lib.convert_many([gs32], torch.bfloat16)[0]
+                g_source = None if gs32 is None else _lib.convert_many([gs32], source.dtype)[0]
         if g_flow is not None and g_flow.dtype != flow_field.dtype:
             g_flow = g_flow.to(flow_field.dtype)
         return g_source, g_flow, None

@@ -154,6 +154,16 @@ class PerceptualCorrectness(nn.Module):
     def calculate_loss(self, flow, layer, mask=None, use_bilinear_sampling=False):
         target_feat = self.target_vgg[layer]
         source_feat = self.source_vgg[layer]
+        half = _lib.HALF_TYPES
+        if target_feat.dtype in half or source_feat.dtype in half or flow.dtype in half:
+            # 16-bit features (torch.autocast): the loss is evaluated in float32 on the library's own kernels (max_cosine,
+            # resample2d, the fused correctness map) and returned in float32, as autocast returns losses
+            with torch.autocast(device_type=target_feat.device.type, enabled=False):
+                return self._loss(flow.float(), target_feat.float(), source_feat.float(),
+                                  None if mask is None else mask.float(), use_bilinear_sampling)
+        return self._loss(flow, target_feat, source_feat, mask, use_bilinear_sampling)
+
+    def _loss(self, flow, target_feat, source_feat, mask, use_bilinear_sampling):
         b, c, h, w = target_feat.shape
         flow = F.interpolate(flow, [h, w])
 

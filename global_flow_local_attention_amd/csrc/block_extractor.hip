@@ -668,6 +668,7 @@ static int block_extractor_unfold_bwd(const T *src, const T *flow, const T *gout
 }  // namespace gfla
 
 using gfla::bf16_t;
+using gfla::f16_t;
 
 extern "C" {
 int gfla_block_extractor_fwd_f32(const float *s, const float *f, float *o, int64_t B, int64_t C,
@@ -743,5 +744,34 @@ int gfla_block_extractor_unfold_bwd_f64(const double *s, const double *f, const 
                                         double *gf, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
                                         int64_t Wf, int k, int layout, gfla_stream_t st) {
   return gfla::block_extractor_unfold_bwd<double>(s, f, go, gs, gf, B, C, Hs, Ws, Hf, Wf, k, layout, st);
+}
+/* f16 storage: the bf16 entry points' twins (same kernels, IEEE binary16 loads and stores) */
+int gfla_block_extractor_fwd_f16(const uint16_t *s, const uint16_t *f, uint16_t *o, int64_t B,
+                                 int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
+                                 gfla_stream_t st) {
+  return gfla::block_extractor_fwd<f16_t>(reinterpret_cast<const f16_t *>(s),
+                                          reinterpret_cast<const f16_t *>(f),
+                                          reinterpret_cast<f16_t *>(o), B, C, Hs, Ws, Hf, Wf, k, st);
+}
+int gfla_block_extractor_bwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *go, uint16_t *gs, float *gf,
+                                 int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
+                                 gfla_stream_t st) {
+  return gfla::block_extractor_bwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
+                                          reinterpret_cast<const f16_t *>(go), reinterpret_cast<f16_t *>(gs), gf, B, C,
+                                          Hs, Ws, Hf, Wf, k, st);
+}
+int gfla_block_extractor_unfold_fwd_f16(const uint16_t *s, const uint16_t *f, uint16_t *o, int64_t B,
+                                        int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k, int layout,
+                                        gfla_stream_t st) {
+  return gfla::block_extractor_unfold_fwd<f16_t>(reinterpret_cast<const f16_t *>(s),
+                                                 reinterpret_cast<const f16_t *>(f),
+                                                 reinterpret_cast<f16_t *>(o), B, C, Hs, Ws, Hf, Wf, k, layout, st);
+}
+int gfla_block_extractor_unfold_bwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *go, uint16_t *gs,
+                                        float *gf, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
+                                        int64_t Wf, int k, int layout, gfla_stream_t st) {
+  return gfla::block_extractor_unfold_bwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
+                                                 reinterpret_cast<const f16_t *>(go), reinterpret_cast<f16_t *>(gs), gf,
+                                                 B, C, Hs, Ws, Hf, Wf, k, layout, st);
 }
 }

@@ -178,10 +178,16 @@ static int fc_wino_jobs(const WnConvJob *jobs, int njobs, const uint32_t *const 
   return fc_wino16_conv_jobs(j16, njobs, B, nch, k, amax_w, stream);
 }
 
+// source16 / target16 (gfla_fc_forward_f16; source and target are then NULL): float16 features, mode 1 only -- the records
+// are packed straight from the f16 maps, unscaled, and only the weights get a max |x| pass
 static int fc_forward(const float *source, const float *target, const float *flow, const float *w0, const float *b0,
                       const float *w1, const float *b1, void *ws_, float *logits, int64_t B, int C, int H, int W,
-                      int k, float slope, int mode_, hipStream_t stream) {
-  if (!source || !target || !flow || !w0 || !w1 || !ws_ || !logits) return GFLA_ERR_NULL_POINTER;
+                      int k, float slope, int mode_, hipStream_t stream, const uint16_t *source16 = nullptr,
+                      const uint16_t *target16 = nullptr) {
+  const bool f16 = source16 != nullptr;
+  if (f16 ? !target16 : (!source || !target)) return GFLA_ERR_NULL_POINTER;
+  if (!flow || !w0 || !w1 || !ws_ || !logits) return GFLA_ERR_NULL_POINTER;
+  if (f16 && mode_ != 1) return GFLA_ERR_UNSUPPORTED;
   GFLA_TRY(fc_args_ok(B, C, H, W, k, mode_));
   if (B == 0) return GFLA_OK;
   note_path(mode_ == 5 ? GFLA_PATH_FC_FWD_MODE5 : GFLA_PATH_FC_FWD_MODE0 + mode_);
@@ -194,15 +200,21 @@ static int fc_forward(const float *source, const float *target, const float *flo
   const uint32_t *a_w = mode ? amax + kAmaxW : nullptr;
   if (mode || w16) {   // the f16-split modes scale by max |x|; the float32 modes never read the slots
     if (hipMemsetAsync(amax, 0, kAmaxSlots * 4, stream) != hipSuccess) return GFLA_ERR_LAUNCH;
-    GFLA_TRY(fc_maxabs_multi(source, B * (int64_t)C * H * W, amax + kAmaxSrc, target, B * (int64_t)C * H * W, amax + kAmaxTgt,
-                             w0, (int64_t)kFcHidden * 2 * C * k * k, amax + kAmaxW, stream));
+    if (f16)   // (zero activation slots: scale 1 for every kernel that reads them, forward and backward)
+      GFLA_TRY(fc_maxabs(w0, (int64_t)kFcHidden * 2 * C * k * k, amax + kAmaxW, stream));
+    else
+      GFLA_TRY(fc_maxabs_multi(source, B * (int64_t)C * H * W, amax + kAmaxSrc, target, B * (int64_t)C * H * W, amax + kAmaxTgt,
+                               w0, (int64_t)kFcHidden * 2 * C * k * k, amax + kAmaxW, stream));
   }
   const bool hyb = fc_hyb(mode_) && fc_hyb_fits(L, k), hyb_f = hyb && fc_hyb_fwd(mode_, k);
   if (hyb)   // mode 2's packs of the sets the direct kernels take (scaled by the slot kAmaxW)
     GFLA_TRY(fc_pack_weights(w0, amax + kAmaxW, hyb_f ? ws + L.wf_t : nullptr, hyb_f ? ws + L.wf_s : nullptr, ws + L.wd_t, ws + L.wd_s,
                              C, k, 2, stream));
   if (wino && !hyb_f) GFLA_TRY(fc_wino_pack_all(L, w0, ws, C, k, stream, w16, hyb));
-  GFLA_TRY(fc_pack_act2(source, a_src, ws + L.xs, L.hs, target, a_tgt, ws + L.xt, L.ht, B, C, H, W, mode, stream));
+  if (f16)
+    GFLA_TRY(fc_pack_act2_f16(source16, ws + L.xs, L.hs, target16, ws + L.xt, L.ht, B, C, H, W, stream));
+  else
+    GFLA_TRY(fc_pack_act2(source, a_src, ws + L.xs, L.hs, target, a_tgt, ws + L.xt, L.ht, B, C, H, W, mode, stream));
   float *gs = reinterpret_cast<float *>(ws + L.gs), *gt = reinterpret_cast<float *>(ws + L.gt);
   const PackedDesc xs = fc_desc_packed(ws + L.xs, B, L.nch_c, L.hs.Sx, mode);
   const PackedDesc xt = fc_desc_packed(ws + L.xt, B, L.nch_c, L.ht.Sx, mode);
@@ -494,6 +506,13 @@ int gfla_fc_forward_f32(const float *source, const float *target, const float *f
                         gfla_stream_t stream) {
   return fc_forward(source, target, flow, w0, b0, w1, b1, workspace, logits, B, (int)C, (int)H, (int)W, kernel_size,
                     (float)slope, mode, static_cast<hipStream_t>(stream));
+}
+
+int gfla_fc_forward_f16(const uint16_t *source, const uint16_t *target, const float *flow, const float *w0,
+                        const float *b0, const float *w1, const float *b1, void *workspace, float *logits, int64_t B,
+                        int64_t C, int64_t H, int64_t W, int kernel_size, double slope, gfla_stream_t stream) {
+  return fc_forward(nullptr, nullptr, flow, w0, b0, w1, b1, workspace, logits, B, (int)C, (int)H, (int)W, kernel_size,
+                    (float)slope, 1, static_cast<hipStream_t>(stream), source, target);
 }
 
 int gfla_fc_backward_f32(void *workspace, const float *flow, const float *w1, const float *grad_logits,

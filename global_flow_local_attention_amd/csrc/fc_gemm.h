@@ -157,6 +157,8 @@ int fc_pack_z(const float *z, const uint32_t *amax, void *out, int64_t B, int64_
               hipStream_t stream);
 int fc_pack_z2(const float *z_s, const uint32_t *amax_s, void *out_s, int64_t S_s, const float *z_t, const uint32_t *amax_t,
                void *out_t, int64_t S_t, int64_t B, int Cz, int mode, hipStream_t stream);
+int fc_pack_act2_f16(const uint16_t *src_s, void *out_s, const FcHalf &gs, const uint16_t *src_t, void *out_t,
+                     const FcHalf &gt, int64_t B, int C, int H, int W, hipStream_t stream);
 int fc_unpack_act(const void *x16, const uint32_t *amax, float *x32, int64_t B, int nch, int64_t S, hipStream_t stream);
 int fc_pack_weights(const float *w0, const uint32_t *amax, void *wf_t, void *wf_s, void *wd_t, void *wd_s, int C,
                     int k, int mode, hipStream_t stream);

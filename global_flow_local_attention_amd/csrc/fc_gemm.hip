@@ -255,6 +255,61 @@ int fc_pack_act2(const float *src_s, const uint32_t *amax_s, void *out_s, const 
   return fc_pack_act_launch(jobs, 2, B, C, H, W, mode, stream);
 }
 
+// ------------------------------------------------------------- pack: NCHW f16 -> one-f16-term records (mode 1)
+// float16 features (gfla_fc_forward_f16): a stored f16 value IS the one f16 term of mode 1, so the records take its bits
+// as they are -- unscaled (the activations' max |x| slots stay zero: scale 1 downstream), no float32 copy in between.
+// Layout, padding and thread mapping as fc_pack_act_kernel<1>.
+struct PackJob16 {
+  const uint16_t *src;
+  unsigned char *out;
+  int Hp, Wp, pad_t, pad_l;
+  int64_t S;
+};
+struct PackJobs16 {
+  PackJob16 j[2];
+};
+__global__ __launch_bounds__(256) void fc_pack_act_f16_kernel(PackJobs16 jobs, int nb0, int C, int H, int W, int nch) {
+  const bool second = (int)blockIdx.z >= nb0;
+  const PackJob16 &J = jobs.j[second ? 1 : 0];
+  const uint16_t *__restrict__ src = J.src;
+  const int Hp = J.Hp, Wp = J.Wp, pad_t = J.pad_t, pad_l = J.pad_l;
+  const int64_t S = J.S;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (m, half)
+  const int64_t m = idx >> 1;
+  const int half = (int)(idx & 1);
+  if (m >= S) return;
+  const int cc = blockIdx.y;
+  const int64_t b = (int)blockIdx.z - (second ? nb0 : 0);
+  uint32_t v[4] = {0u, 0u, 0u, 0u};
+  if (m < (int64_t)Hp * Wp) {
+    const int yp = (int)(m / Wp), xp = (int)(m - (int64_t)yp * Wp);
+    const int y = clampi(yp - pad_t, 0, H - 1), x = clampi(xp - pad_l, 0, W - 1);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = cc * kFcChunk + half * 8 + e;
+      if (c < C) v[e >> 1] |= (uint32_t)src[((b * C + c) * H + y) * (int64_t)W + x] << (16 * (e & 1));
+    }
+  }
+  unsigned char *dst = J.out + (((b * nch + cc) * S + m) * kFcChunk + half * 8) * 2;
+  *reinterpret_cast<uint4 *>(dst) = make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+// both halves of a layer in one launch
+int fc_pack_act2_f16(const uint16_t *src_s, void *out_s, const FcHalf &gs, const uint16_t *src_t, void *out_t,
+                     const FcHalf &gt, int64_t B, int C, int H, int W, hipStream_t stream) {
+  if (B <= 0) return GFLA_OK;
+  const int nch = (int)ceil_div(C, kFcChunk);
+  if (nch > 65535 || 2 * B > 65535) return GFLA_ERR_UNSUPPORTED;
+  PackJobs16 jobs;
+  jobs.j[0] = PackJob16{src_s, static_cast<unsigned char *>(out_s), gs.Hp, gs.Wp, gs.pad_t, gs.pad_l, gs.Sx};
+  jobs.j[1] = PackJob16{src_t, static_cast<unsigned char *>(out_t), gt.Hp, gt.Wp, gt.pad_t, gt.pad_l, gt.Sx};
+  const int64_t smax = gs.Sx > gt.Sx ? gs.Sx : gt.Sx;
+  const dim3 grid((unsigned)ceil_div(2 * smax, 256), (unsigned)nch, (unsigned)(2 * B));
+  note_path(GFLA_PATH_FC_PACK_F16);
+  fc_pack_act_f16_kernel<<<grid, 256, 0, stream>>>(jobs, (int)B, C, H, W, nch);
+  return launch_status();
+}
+
 // ------------------------------------------------------------- pack: f32 (B, S, Cz) pixel-major -> f16 records
 // (mode 2/3 only; mode 0 reads the f32 map in place).  A thread owns one pixel and walks its chunks: the reads of
 // a wave hit every 64-byte line of the map exactly once (through L2), the stores are contiguous per chunk.

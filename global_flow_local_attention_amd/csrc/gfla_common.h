@@ -14,7 +14,7 @@ constexpr int kNumXCD = 8;
 constexpr int kWavesPerCU = 32;
 
 // ---- storage <-> arithmetic types --------------------------------------------------------
-// f32 and bf16 storage compute in float (the reference's float instantiation), f64 in double.
+// f32, bf16 and f16 storage compute in float (the reference's float instantiation), f64 in double.
 struct bf16_t {
   uint16_t bits;
   bf16_t() = default;
@@ -58,6 +58,30 @@ struct Num<bf16_t> {
 };
 __host__ __device__ inline bf16_t::bf16_t(float v) : bits(Num<bf16_t>::pack(v)) {}
 
+// IEEE binary16 storage: the same interface as bf16_t.  Loads widen exactly (v_cvt_f32_f16); stores round once to nearest
+// even (v_cvt_f16_f32): overflow gives +-inf, NaN stays NaN, f16 subnormals are kept (the f16/f64 denormal mode of the
+// gfx950 default is "preserve").
+struct f16_t {
+  uint16_t bits;
+  f16_t() = default;
+  __host__ __device__ explicit f16_t(float v);
+  static __host__ __device__ __forceinline__ f16_t from_bits(uint16_t b) {
+    f16_t r;
+    r.bits = b;
+    return r;
+  }
+};
+template <>
+struct Num<f16_t> {
+  using acc = float;
+  static __device__ __forceinline__ float ld(const f16_t *p) { return (float)__builtin_bit_cast(_Float16, p->bits); }
+  static __host__ __device__ __forceinline__ uint16_t pack(float v) {  // round-to-nearest-even
+    return __builtin_bit_cast(uint16_t, (_Float16)v);
+  }
+  static __device__ __forceinline__ f16_t from(float v) { return f16_t::from_bits(pack(v)); }
+};
+__host__ __device__ inline f16_t::f16_t(float v) : bits(Num<f16_t>::pack(v)) {}
+
 // Vector of V storage elements written with ONE store instruction (V*sizeof(T) in {4,8,16}).
 template <typename T, int V>
 struct alignas(sizeof(T) * V) Pack {
@@ -85,6 +109,7 @@ __device__ __forceinline__ void atomic_add(double *p, double v) {
 // logits, (dx,dy,sigma)) targets a float32 buffer; the host side returns GFLA_ERR_UNSUPPORTED for anything else.
 // This overload only lets the shared templates compile.
 __device__ __forceinline__ void atomic_add(bf16_t *, bf16_t) { __builtin_trap(); }
+__device__ __forceinline__ void atomic_add(f16_t *, f16_t) { __builtin_trap(); }   // (f16 storage: the same rule)
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -531,6 +531,9 @@ __device__ __forceinline__ void agg_chunk_load(const T *__restrict__ g, int n, f
     const int i = min(j * (int)blockDim.x + (int)threadIdx.x, n - 1);
     if constexpr (sizeof(T) == 4) {
       pre[j] = reinterpret_cast<const f32x2 *>(g)[i];
+    } else if constexpr (std::is_same<T, f16_t>::value) {
+      const unsigned raw = reinterpret_cast<const unsigned *>(g)[i];  // two f16
+      pre[j] = f32x2{Num<f16_t>::ld(reinterpret_cast<const f16_t *>(&raw)), Num<f16_t>::ld(reinterpret_cast<const f16_t *>(&raw) + 1)};
     } else {
       const unsigned raw = reinterpret_cast<const unsigned *>(g)[i];  // two bf16
       pre[j] = f32x2{__uint_as_float(raw << 16), __uint_as_float(raw & 0xffff0000u)};
@@ -1282,6 +1285,8 @@ template int rs_bwd2_stream<float>(const float *, const float *, const float *, 
                                    int64_t, int64_t, hipStream_t);
 template int rs_bwd2_stream<bf16_t>(const bf16_t *, const bf16_t *, const bf16_t *, float *, int64_t, int64_t, int64_t,
                                     int64_t, int64_t, int64_t, hipStream_t);
+template int rs_bwd2_stream<f16_t>(const f16_t *, const f16_t *, const f16_t *, float *, int64_t, int64_t, int64_t,
+                                   int64_t, int64_t, int64_t, hipStream_t);
 
 // In place: glogits holds ga (d/d a_ij); turn it into d/d logit_ij = a_ij * (ga_ij - sum_mn a_mn ga_mn).
 template <typename T, int K>
@@ -1519,7 +1524,7 @@ static int aggregate_bwd(const T *src, const T *flow, const T *attn, const T *go
     return st;
   }
   if constexpr (sizeof(T) == 2) {
-    return GFLA_ERR_UNSUPPORTED;  // bf16 storage: the planes-in-LDS kernels only
+    return GFLA_ERR_UNSUPPORTED;  // bf16 / f16 storage: the planes-in-LDS kernels only
   } else {
     AggGeo g = agg_geometry(B, C, H, W, 32, 2 * kNumCU * kWavesPerCU);
     if (g.blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
@@ -1556,6 +1561,7 @@ static int local_attn_source_bwd(const T *src, const T *flow, const T *gunf, con
 }  // namespace gfla
 
 using gfla::bf16_t;
+using gfla::f16_t;
 
 extern "C" {
 int gfla_local_attn_aggregate_fwd_f32(const float *s, const float *f, const float *l, float *o, float *a,
@@ -1659,5 +1665,35 @@ int gfla_local_attn_source_bwd_f64(const double *s, const double *f, const doubl
                                    const double *go, double *gs, double *gf, int64_t B, int64_t C, int64_t Hs,
                                    int64_t Ws, int64_t H, int64_t W, int k, int layout, gfla_stream_t st) {
   return gfla::local_attn_source_bwd<double>(s, f, gu, a, go, gs, gf, B, C, Hs, Ws, H, W, k, layout, st);
+}
+/* f16 storage: the bf16 entry points' twins (same kernels, IEEE binary16 loads and stores) */
+int gfla_local_attn_aggregate_fwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *l,
+                                      uint16_t *o, uint16_t *a, int64_t B, int64_t C, int64_t Hs,
+                                      int64_t Ws, int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
+  return gfla::aggregate_fwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
+                                    reinterpret_cast<const f16_t *>(l), reinterpret_cast<f16_t *>(o),
+                                    reinterpret_cast<f16_t *>(a), B, C, Hs, Ws, H, W, k, sm, st);
+}
+int gfla_local_attn_aggregate_fwd_ws_f16(const uint16_t *s, const uint16_t *f, const uint16_t *l, uint16_t *o,
+                                         uint16_t *a, void *workspace, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
+                                         int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
+  return gfla::aggregate_fwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
+                                    reinterpret_cast<const f16_t *>(l), reinterpret_cast<f16_t *>(o),
+                                    reinterpret_cast<f16_t *>(a), B, C, Hs, Ws, H, W, k, sm, st, workspace);
+}
+int gfla_local_attn_aggregate_bwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *a, const uint16_t *go,
+                                      uint16_t *gs, float *gf, float *gl, int64_t B, int64_t C, int64_t Hs,
+                                      int64_t Ws, int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
+  return gfla::aggregate_bwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
+                                    reinterpret_cast<const f16_t *>(a), reinterpret_cast<const f16_t *>(go),
+                                    reinterpret_cast<f16_t *>(gs), gf, gl, B, C, Hs, Ws, H, W, k, sm, st);
+}
+int gfla_local_attn_source_bwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *gu, const uint16_t *a,
+                                   const uint16_t *go, uint16_t *gs, float *gf, int64_t B, int64_t C, int64_t Hs,
+                                   int64_t Ws, int64_t H, int64_t W, int k, int layout, gfla_stream_t st) {
+  return gfla::local_attn_source_bwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
+                                            reinterpret_cast<const f16_t *>(gu), reinterpret_cast<const f16_t *>(a),
+                                            reinterpret_cast<const f16_t *>(go), reinterpret_cast<f16_t *>(gs), gf, B, C,
+                                            Hs, Ws, H, W, k, layout, st);
 }
 }

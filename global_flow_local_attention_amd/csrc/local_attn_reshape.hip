@@ -73,7 +73,7 @@ static int reshape(bool fwd, const T *a, T *bptr, int64_t B, int64_t H, int64_t 
 
 }  // namespace gfla
 
-// The permutation only moves bit patterns, so bf16 reuses the 16-bit integer instantiation.
+// The permutation only moves bit patterns, so bf16 and f16 reuse the 16-bit integer instantiation.
 extern "C" {
 int gfla_local_attn_reshape_fwd_f32(const float *in, float *out, int64_t B, int64_t H, int64_t W, int k,
                                     gfla_stream_t st) {
@@ -97,6 +97,14 @@ int gfla_local_attn_reshape_bwd_f64(const double *go, double *gi, int64_t B, int
 }
 int gfla_local_attn_reshape_bwd_bf16(const uint16_t *go, uint16_t *gi, int64_t B, int64_t H, int64_t W,
                                      int k, gfla_stream_t st) {
+  return gfla::reshape<uint16_t>(false, go, gi, B, H, W, k, st);
+}
+int gfla_local_attn_reshape_fwd_f16(const uint16_t *in, uint16_t *out, int64_t B, int64_t H, int64_t W, int k,
+                                    gfla_stream_t st) {
+  return gfla::reshape<uint16_t>(true, in, out, B, H, W, k, st);
+}
+int gfla_local_attn_reshape_bwd_f16(const uint16_t *go, uint16_t *gi, int64_t B, int64_t H, int64_t W, int k,
+                                    gfla_stream_t st) {
   return gfla::reshape<uint16_t>(false, go, gi, B, H, W, k, st);
 }
 }

@@ -5,7 +5,7 @@
 // Nine elementwise torch kernels forward and ~14 backward per layer and frame; at the face model's batch they are
 // launch-sized (5-13 us each: 16 % of the bf16 face step's GPU time, profiles/r4_face_bf16_kernel_stats.txt).  One kernel
 // each way here.  Forward: every intermediate is rounded to the storage type exactly where the op-by-op evaluation rounds
-// it (f32: separate multiply and add, no contraction; bf16: round-to-nearest-even after every op), so the result is the
+// it (f32: separate multiply and add, no contraction; bf16 / f16: round-to-nearest-even after every op), so the result is the
 // op-by-op result bit for bit.  Backward: d/d out, d/d attn_p, d/d attn_r per element; d/d mask_p, d/d mask_r are sums
 // over the channels, accumulated in float32 (thread = pixel x channel chunk, one atomic per thread and mask).
 #include "gfla_common.h"
@@ -19,6 +19,10 @@ __device__ __forceinline__ float rnd(float v) {   // round a float result to the
 template <>
 __device__ __forceinline__ float rnd<bf16_t>(float v) {
   return __uint_as_float((uint32_t)Num<bf16_t>::pack(v) << 16);
+}
+template <>
+__device__ __forceinline__ float rnd<f16_t>(float v) {
+  return (float)(_Float16)v;
 }
 
 constexpr int kBlendChunk = 16;   // channels per thread
@@ -115,12 +119,35 @@ struct ConvertJob {
 struct ConvertJobs {
   ConvertJob j[4];
 };
-template <bool TO_BF16>
+// KIND: 0 bfloat16 -> float32, 1 float32 -> bfloat16, 2 float16 -> float32, 3 float32 -> float16 (gfla_convert_multi's flag)
+template <int KIND>
 __global__ __launch_bounds__(256) void convert_multi_kernel(ConvertJobs jobs) {
   const ConvertJob &J = jobs.j[blockIdx.y];
   const int64_t n = J.n, stride = (int64_t)gridDim.x * 256;
   const int64_t n4 = ((reinterpret_cast<uintptr_t>(J.src) | reinterpret_cast<uintptr_t>(J.dst)) & 15) == 0 ? n >> 2 : 0;
-  if constexpr (TO_BF16) {   // float32 -> bfloat16, round to nearest even (torch's conversion)
+  if constexpr (KIND == 3) {   // float32 -> float16, round to nearest even (v_cvt_pk_f16_f32; torch's conversion)
+    const float4 *s4 = static_cast<const float4 *>(J.src);
+    uint2 *d4 = static_cast<uint2 *>(J.dst);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+      const float4 v = s4[i];
+      d4[i] = make_uint2((uint32_t)Num<f16_t>::pack(v.x) | (uint32_t)Num<f16_t>::pack(v.y) << 16,
+                         (uint32_t)Num<f16_t>::pack(v.z) | (uint32_t)Num<f16_t>::pack(v.w) << 16);
+    }
+    const float *s = static_cast<const float *>(J.src);
+    uint16_t *d = static_cast<uint16_t *>(J.dst);
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) d[i] = Num<f16_t>::pack(s[i]);
+  } else if constexpr (KIND == 2) {   // float16 -> float32 (exact)
+    const f16_t *s = static_cast<const f16_t *>(J.src);
+    const uint2 *s4 = static_cast<const uint2 *>(J.src);
+    float4 *d4 = static_cast<float4 *>(J.dst);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+      const uint2 v = s4[i];
+      const f16_t *h = reinterpret_cast<const f16_t *>(&v);
+      d4[i] = make_float4(Num<f16_t>::ld(h), Num<f16_t>::ld(h + 1), Num<f16_t>::ld(h + 2), Num<f16_t>::ld(h + 3));
+    }
+    float *d = static_cast<float *>(J.dst);
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) d[i] = Num<f16_t>::ld(s + i);
+  } else if constexpr (KIND == 1) {   // float32 -> bfloat16, round to nearest even (torch's conversion)
     const float4 *s4 = static_cast<const float4 *>(J.src);
     uint2 *d4 = static_cast<uint2 *>(J.dst);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
@@ -149,10 +176,11 @@ __global__ __launch_bounds__(256) void convert_multi_kernel(ConvertJobs jobs) {
 }  // namespace gfla
 
 using gfla::bf16_t;
+using gfla::f16_t;
 
 extern "C" {
 /* dst_i[0..n_i) = convert(src_i[0..n_i)) for up to four tensors (unused jobs: n = 0); to_bf16 = 0: bfloat16 -> float32,
- * 1: float32 -> bfloat16 (round to nearest even). */
+ * 1: float32 -> bfloat16 (round to nearest even), 2: float16 -> float32, 3: float32 -> float16 (round to nearest even). */
 int gfla_convert_multi(const void *s0, void *d0, int64_t n0, const void *s1, void *d1, int64_t n1, const void *s2, void *d2,
                        int64_t n2, const void *s3, void *d3, int64_t n3, int to_bf16, gfla_stream_t st) {
   gfla::ConvertJobs jobs;
@@ -173,10 +201,15 @@ int gfla_convert_multi(const void *s0, void *d0, int64_t n0, const void *s1, voi
   int64_t blocks = gfla::ceil_div(most, 256 * 8);
   if (blocks > 4 * gfla::kNumCU) blocks = 4 * gfla::kNumCU;
   const dim3 grid((unsigned)blocks, (unsigned)nj);
-  if (to_bf16)
-    gfla::convert_multi_kernel<true><<<grid, 256, 0, static_cast<hipStream_t>(st)>>>(jobs);
+  const hipStream_t stream = static_cast<hipStream_t>(st);
+  if (to_bf16 == GFLA_CONVERT_F32_TO_F16)
+    gfla::convert_multi_kernel<3><<<grid, 256, 0, stream>>>(jobs);
+  else if (to_bf16 == GFLA_CONVERT_F16_TO_F32)
+    gfla::convert_multi_kernel<2><<<grid, 256, 0, stream>>>(jobs);
+  else if (to_bf16)
+    gfla::convert_multi_kernel<1><<<grid, 256, 0, stream>>>(jobs);
   else
-    gfla::convert_multi_kernel<false><<<grid, 256, 0, static_cast<hipStream_t>(st)>>>(jobs);
+    gfla::convert_multi_kernel<0><<<grid, 256, 0, stream>>>(jobs);
   return gfla::launch_status();
 }
 
@@ -201,5 +234,19 @@ int gfla_mask_blend_bwd_bf16(const uint16_t *out, const uint16_t *ap, const uint
   auto m = [](uint16_t *p) { return reinterpret_cast<bf16_t *>(p); };
   return gfla::mask_blend_bwd<bf16_t>(c(out), c(ap), c(ar), c(mp), c(mr), c(g), m(g_out), m(g_ap), m(g_ar), g_mp, g_mr, B, C,
                                       HW, st);
+}
+/* f16 storage: the bf16 entry points' twins (same kernels, IEEE binary16 loads and stores) */
+int gfla_mask_blend_fwd_f16(const uint16_t *out, const uint16_t *ap, const uint16_t *ar, const uint16_t *mp,
+                            const uint16_t *mr, uint16_t *y, int64_t B, int64_t C, int64_t HW, gfla_stream_t st) {
+  auto c = [](const uint16_t *p) { return reinterpret_cast<const f16_t *>(p); };
+  return gfla::mask_blend_fwd<f16_t>(c(out), c(ap), c(ar), c(mp), c(mr), reinterpret_cast<f16_t *>(y), B, C, HW, st);
+}
+int gfla_mask_blend_bwd_f16(const uint16_t *out, const uint16_t *ap, const uint16_t *ar, const uint16_t *mp,
+                            const uint16_t *mr, const uint16_t *g, uint16_t *g_out, uint16_t *g_ap, uint16_t *g_ar,
+                            float *g_mp, float *g_mr, int64_t B, int64_t C, int64_t HW, gfla_stream_t st) {
+  auto c = [](const uint16_t *p) { return reinterpret_cast<const f16_t *>(p); };
+  auto m = [](uint16_t *p) { return reinterpret_cast<f16_t *>(p); };
+  return gfla::mask_blend_bwd<f16_t>(c(out), c(ap), c(ar), c(mp), c(mr), c(g), m(g_out), m(g_ap), m(g_ar), g_mp, g_mr, B, C,
+                                     HW, st);
 }
 }

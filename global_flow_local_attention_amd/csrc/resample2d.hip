@@ -1077,6 +1077,7 @@ static int resample2d_bwd(const T *in1, const T *in2, const T *gout, T *gin1, ty
 }  // namespace gfla
 
 using gfla::bf16_t;
+using gfla::f16_t;
 
 extern "C" {
 int gfla_resample2d_fwd_f32(const float *a, const float *b, float *o, int64_t B, int64_t C, int64_t Hi,
@@ -1172,5 +1173,20 @@ int gfla_resample2d_bwd_f64(const double *a, const double *b, const double *go, 
                             int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k,
                             int d, int trunc, gfla_stream_t st) {
   return gfla::resample2d_bwd<double>(a, b, go, g1, g2, B, C, Hi, Wi, H, W, k, d, trunc, st);
+}
+/* f16 storage: the bf16 entry points' twins (same kernels, IEEE binary16 loads and stores) */
+int gfla_resample2d_fwd_f16(const uint16_t *a, const uint16_t *b, uint16_t *o, int64_t B, int64_t C,
+                            int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int d,
+                            gfla_stream_t st) {
+  return gfla::resample2d_fwd<f16_t>(reinterpret_cast<const f16_t *>(a),
+                                     reinterpret_cast<const f16_t *>(b), reinterpret_cast<f16_t *>(o),
+                                     B, C, Hi, Wi, H, W, k, d, st);
+}
+int gfla_resample2d_bwd_f16(const uint16_t *a, const uint16_t *b, const uint16_t *go, uint16_t *g1, float *g2, int64_t B,
+                            int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int d, int trunc,
+                            gfla_stream_t st) {
+  return gfla::resample2d_bwd<f16_t>(reinterpret_cast<const f16_t *>(a), reinterpret_cast<const f16_t *>(b),
+                                     reinterpret_cast<const f16_t *>(go), reinterpret_cast<f16_t *>(g1), g2, B, C, Hi,
+                                     Wi, H, W, k, d, trunc, st);
 }
 }

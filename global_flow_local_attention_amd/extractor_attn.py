@@ -321,22 +321,24 @@ def _mfma_mode(self, source, target, flow_field, conv0, act, conv1, k):
 
 
 def _bf16_backward_supported(hs, ws):
-    """bf16 features: the aggregation's backward keeps a (double accumulator + f32 source) plane pair per position in
-    LDS; larger maps have no bf16 backward.  The library answers (gfla_aggregate_bwd_supported) -- its LDS budget is
+    """16-bit features: the aggregation's backward keeps a (double accumulator + f32 source) plane pair per position in
+    LDS; larger maps have no bf16 / f16 backward.  The library answers (gfla_aggregate_bwd_supported) -- its LDS budget is
     tunable, a constant duplicated here would drift."""
     return bool(_lib.lib().gfla_aggregate_bwd_supported(int(hs), int(ws), 2))
 
 
-def _bf16_path_ok(self, source, target, flow_field, conv0, act, conv1, last, k):
-    if not (source.dtype == torch.bfloat16 and target.dtype == torch.bfloat16
-            and flow_field.dtype in (torch.bfloat16, torch.float32)
+def _half_path_ok(self, source, target, flow_field, conv0, act, conv1, last, k):
+    """16-bit features (bf16 or f16 source and target of one dtype; flow in that dtype or float32) that the 16-bit
+    pipeline (FusedAttn16Function) takes."""
+    if not (source.dtype in _lib.HALF_TYPES and target.dtype == source.dtype
+            and flow_field.dtype in (source.dtype, torch.float32)
             and getattr(self, "fc_impl", "mfma") == "mfma" and isinstance(last, nn.Softmax) and last.dim == 1
             and _fc_layers_fit(source, target, flow_field, conv0, act, conv1, k)
             and fc_mfma.supported(source.size(1), source.size(2), source.size(3), k, 1)):
         return False
     needs_bwd = torch.is_grad_enabled() and (source.requires_grad or target.requires_grad or flow_field.requires_grad
                                              or conv0.weight.requires_grad or conv1.weight.requires_grad)
-    # the LDS-plane limit belongs to the bf16 aggregate backward only; the default backward (BF16_BACKWARD_F32_AGGREGATE)
+    # the LDS-plane limit belongs to the 16-bit aggregate backward only; the default backward (BF16_BACKWARD_F32_AGGREGATE)
     # goes through gfla_local_attn_aggregate_bwd_ws_f32, which has no such limit
     return not needs_bwd or BF16_BACKWARD_F32_AGGREGATE or _bf16_backward_supported(source.size(2), source.size(3))
 
@@ -446,42 +448,57 @@ def _zeros_f32(dev, *wanted_shapes):
     return out
 
 
-# bf16 features: the aggregation's backward in float32 on up-cast operands (matrix-core scatter) instead of the _bf16 entry
-# point (LDS-atomic scatter); False = round 3's evaluation, kept for A/B and for the parity tests of the _bf16 entry points
+# 16-bit features: the aggregation's backward in float32 on up-cast operands (matrix-core scatter) instead of the _bf16 /
+# _f16 entry point (LDS-atomic scatter); False = round 3's evaluation, kept for A/B and for the parity tests of those entry
+# points
 BF16_BACKWARD_F32_AGGREGATE = True
 
 
-class FusedAttnBf16Function(Function):
-    """ExtractorAttn.forward (softmax=True) for bfloat16 FEATURES (BASELINE config 5: mixed-precision face model).
-    Storage is bf16 -- source, target, flow in; result, attention and the feature-map gradients out -- and nothing is
-    ever widened in HBM except the inputs of the FC layers:
-      * FC layers: gfla_fc_{forward,backward}_f32 in arithmetic mode 1 -- ONE f16 term per operand, which represents a
-        bf16 value exactly, f32 accumulation in the MFMA -- at the full f16 matrix-core rate (16x the f32 one);
-      * softmax / aggregate and their backward: the _bf16 entry points (f32 arithmetic, f64-in-LDS scatter);
+class FusedAttn16Function(Function):
+    """ExtractorAttn.forward (softmax=True) for 16-bit FEATURES -- bfloat16 (BASELINE config 5: mixed-precision face model)
+    or float16 (torch.autocast's default).  Storage is the features' dtype -- source, target, flow in; result, attention
+    and the feature-map gradients out -- and nothing is widened in HBM except what the FC layers read:
+      * FC layers in arithmetic mode 1 -- ONE f16 term per operand, f32 accumulation in the MFMA -- at the full f16
+        matrix-core rate (16x the f32 one).  bf16: gfla_fc_forward_f32 on float32 copies (a bf16 value is one f16 term
+        after scaling by max |x|).  f16: gfla_fc_forward_f16 packs the records straight from the f16 maps (a stored f16
+        value IS one f16 term: no copy, no max |x| pass);  the backward is gfla_fc_backward_f32 on that workspace;
+      * softmax / aggregate and their backward: the 16-bit entry points (f32 arithmetic, f64-in-LDS scatter);
+      * the logits are rounded to the storage type before the softmax, as autocast's conv1 would round them;
       * reductions over channels (d flow, d logits) and all parameter gradients are float32 inside, cast at the end.
-    The FC parameters may be f32 (autocast-style master weights) or bf16."""
+    The FC parameters may be f32 (autocast-style master weights) or the features' dtype."""
 
     @staticmethod
     def forward(ctx, source, target, flow, w0, b0, w1, b1, kernel_size, slope):
         k = int(kernel_size)
+        dt = source.dtype
         _lib.require_gpu(source, target, flow, w0, w1)
         B, C, H, W = source.shape
         if tuple(target.shape) != (B, C, H, W) or tuple(flow.shape) != (B, 2, H, W):
-            raise ValueError("ExtractorAttn (bf16): source, target and flow must share B, C and H, W")
+            raise ValueError("ExtractorAttn (%s): source, target and flow must share B, C and H, W" % dt)
         source, flow = source.contiguous(), flow.contiguous()
         f32 = lambda t: None if t is None else t.detach().float().contiguous()
-        # (one launch for the three widenings: the call is launch-bound at the face model's batch)
-        s32, t32, fl32 = _lib.convert_many([source.detach(), target.detach().contiguous(), flow.detach()], torch.float32)
         w0c, w1c, b0c, b1c = f32(w0), f32(w1).reshape(k * k, 128), f32(b0), f32(b1)
         mode = 1
         ws = torch.empty(fc_mfma.workspace_bytes(B, C, H, W, k, mode, 0), dtype=torch.uint8, device=source.device)
-        logits32 = s32.new_empty((B, k * k, H, W))
-        _lib.call("gfla_fc_forward_f32", s32, _lib.ptr(s32), _lib.ptr(t32), _lib.ptr(fl32), _lib.ptr(w0c), _lib.ptr(b0c),
-                  _lib.ptr(w1c), _lib.ptr(b1c), _lib.ptr(ws), _lib.ptr(logits32), B, C, H, W, k, float(slope), mode)
-        logits = logits32.to(torch.bfloat16)
+        logits32 = torch.empty((B, k * k, H, W), dtype=torch.float32, device=source.device)
+        if dt == torch.float16:
+            # the records come straight from the f16 maps; only the 2-channel flow is widened (the sampling tail and the
+            # backward read it in float32)
+            t16 = target.detach().contiguous()
+            fl32 = _lib.convert_many([flow.detach()], torch.float32)[0]
+            _lib.call("gfla_fc_forward_f16", source, _lib.ptr(source), _lib.ptr(t16), _lib.ptr(fl32), _lib.ptr(w0c),
+                      _lib.ptr(b0c), _lib.ptr(w1c), _lib.ptr(b1c), _lib.ptr(ws), _lib.ptr(logits32), B, C, H, W, k,
+                      float(slope))
+        else:
+            # (one launch for the three widenings: the call is launch-bound at the face model's batch)
+            s32, t32, fl32 = _lib.convert_many([source.detach(), target.detach().contiguous(), flow.detach()], torch.float32)
+            _lib.call("gfla_fc_forward_f32", s32, _lib.ptr(s32), _lib.ptr(t32), _lib.ptr(fl32), _lib.ptr(w0c),
+                      _lib.ptr(b0c), _lib.ptr(w1c), _lib.ptr(b1c), _lib.ptr(ws), _lib.ptr(logits32), B, C, H, W, k,
+                      float(slope), mode)
+        logits = logits32.to(dt)
         out = torch.empty_like(source)
         attn = torch.empty_like(logits)
-        flow_b = flow if flow.dtype == torch.bfloat16 else flow.to(torch.bfloat16)
+        flow_b = flow if flow.dtype == dt else flow.to(dt)
         _lib.aggregate_fwd(source, flow_b, logits, out, attn, k, True)
         ctx.save_for_backward(source, flow_b, fl32, attn, w1c, ws)
         ctx.dims = (B, C, H, W, k, float(slope), mode)
@@ -512,11 +529,11 @@ class FusedAttnBf16Function(Function):
                       _lib.ptr(go32), _lib.ptr(g_s32), _lib.ptr(gf32), _lib.ptr(gl32), _lib.ptr(table), B, C, H, W, H, W, k, 1)
             gs = None
         else:
-            g_out = g_out.contiguous().to(torch.bfloat16)
-            gs = torch.zeros_like(source) if need[0] else None                   # bf16, accumulated into
+            g_out = g_out.contiguous().to(source.dtype)
+            gs = torch.zeros_like(source) if need[0] else None                   # 16-bit, accumulated into
             gf32 = zeros32((B, 2, H, W), need[2])
             gl32 = torch.zeros((B, k * k, H, W), dtype=torch.float32, device=dev)
-            _lib.call("gfla_local_attn_aggregate_bwd_bf16", source, _lib.ptr(source), _lib.ptr(flow_b), _lib.ptr(attn),
+            _lib.call("gfla_local_attn_aggregate_bwd_" + _lib.suffix(source, "ExtractorAttn backward"), source, _lib.ptr(source), _lib.ptr(flow_b), _lib.ptr(attn),
                       _lib.ptr(g_out), _lib.ptr(gs), _lib.ptr(gf32), _lib.ptr(gl32), B, C, H, W, H, W, k, 1)
             g_s32 = new32((B, C, H, W), need[0])
         g_t32 = new32((B, C, H, W), need[1])
@@ -536,12 +553,18 @@ class FusedAttnBf16Function(Function):
             g_source = g_s32
         else:
             g_source = gs.float() + g_s32
-        if target_dtype == flow_dtype == torch.bfloat16:   # the three feature-map gradients narrowed by one launch
-            g_source, g_target, g_flow = _lib.convert_many([g_source, g_t32, gf32], torch.bfloat16)
+        dt = source.dtype
+        if target_dtype == flow_dtype == dt:   # the three feature-map gradients narrowed by one launch
+            g_source, g_target, g_flow = _lib.convert_many([g_source, g_t32, gf32], dt)
         else:
-            g_source, g_target, g_flow = cast(g_source, torch.bfloat16), cast(g_t32, target_dtype), cast(gf32, flow_dtype)
+            g_source, g_target, g_flow = cast(g_source, dt), cast(g_t32, target_dtype), cast(gf32, flow_dtype)
         return (g_source, g_target, g_flow, cast(g_w0, pdt[0]), cast(g_b0, pdt[1]), cast(g_w1, pdt[2]), cast(g_b1, pdt[3]),
                 None, None)
+
+
+# (the names of the bf16-only era)
+FusedAttnBf16Function = FusedAttn16Function
+_bf16_path_ok = _half_path_ok
 
 
 def _fused_attention(self, source, target, flow_field):
@@ -556,21 +579,21 @@ def _fused_attention(self, source, target, flow_field):
         return _unfused_attention(self, source, target, flow_field)
     source_c = source.contiguous()
     flow_c = flow_field.contiguous()
-    if source.dtype == torch.bfloat16:
-        if _bf16_path_ok(self, source_c, target, flow_c, conv0, act, conv1, last, k):
-            result, attn = FusedAttnBf16Function.apply(source_c, target, flow_c, conv0.weight, conv0.bias, conv1.weight,
-                                                       conv1.bias, k, _tail_slope(act))
+    if source.dtype in _lib.HALF_TYPES:
+        if _half_path_ok(self, source_c, target, flow_c, conv0, act, conv1, last, k):
+            result, attn = FusedAttn16Function.apply(source_c, target, flow_c, conv0.weight, conv0.bias, conv1.weight,
+                                                     conv1.bias, k, _tail_slope(act))
             return attn, result
-        # a bf16 map the bf16 kernels do not take (shape mismatch, planes beyond the LDS backward): evaluate the block in
-        # float32 -- every gradient exists there -- and hand the result back in bf16
+        # a 16-bit map the 16-bit kernels do not take (shape or dtype mismatch, planes beyond the LDS backward): evaluate the
+        # block in float32 -- every gradient exists there -- and hand the result back in the source's dtype
         if not getattr(self, "_bf16_warned", False):
             import warnings
-            warnings.warn("ExtractorAttn: bfloat16 features of shape %s are evaluated in float32 (the bf16 kernels do not "
-                          "take this shape)" % (tuple(source.shape),))
+            warnings.warn("ExtractorAttn: %s features of shape %s are evaluated in float32 (the 16-bit kernels do not "
+                          "take this shape or dtype mix)" % (source.dtype, tuple(source.shape)))
             self._bf16_warned = True
         with torch.autocast(device_type="cuda", enabled=False):
             attn, result = _fused_attention_f32_module(self, source.float(), target.float(), flow_field.float())
-        return attn.to(torch.bfloat16), result.to(torch.bfloat16)
+        return attn.to(source.dtype), result.to(source.dtype)
     if _f64_path_ok(self, source_c, target, flow_c, conv0, act, conv1, k):
         return _fused_attention_f64(self, source_c, target.contiguous(), flow_c, conv0, act, conv1, last, k)
     mode = _mfma_mode(self, source_c, target, flow_c, conv0, act, conv1, k)
@@ -588,7 +611,7 @@ def _fused_attention(self, source, target, flow_field):
     if getattr(self, "fc_impl", "mfma") == "mfma":   # not an explicit request for the vendor path
         policy = getattr(self, "vendor_fallback", VENDOR_FALLBACK)
         what = ("ExtractorAttn(kernel_size=%d, %s, %s): this configuration is not taken by the library's own MFMA kernels "
-                "(kernel_size 3 / 5, float32 or bfloat16 features, 128 hidden channels, maps whose tiles fit the LDS; float64 "
+                "(kernel_size 3 / 5, float32, bfloat16 or float16 features, 128 hidden channels, maps whose tiles fit the LDS; float64 "
                 "features in the reference's layout); its FC "
                 "layers would run through torch.mm / F.conv2d (rocBLAS / MIOpen)" % (k, source.dtype, tuple(source.shape)))
         if policy == "error":
@@ -658,7 +681,7 @@ def _f32_twins(fc):
 
 
 def _fused_attention_f32_module(self, source, target, flow_field):
-    """_fused_attention on float32 inputs with the module's parameters viewed as float32 (bf16 modules).  A shallow shadow
+    """_fused_attention on float32 inputs with the module's parameters viewed as float32 (bf16 / f16 modules).  A shallow shadow
     of the module is built PER CALL (so attributes set at any time -- fc_mode, vendor_fallback, fc_impl, training -- are
     seen), around cached meta-device twins of the convolutions that carry the differentiable float32 views of the bf16
     parameters only for the duration of the call: nothing non-leaf stays reachable from the module afterwards (deepcopy

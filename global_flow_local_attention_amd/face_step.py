@@ -75,7 +75,7 @@ class MaskBlendFunction(Function):
 
 
 def _blend_fusable(out, attn_p, attn_r, mask_p, mask_r):
-    return (out.is_cuda and out.dtype in (torch.float32, torch.bfloat16) and out.dim() == 4
+    return (out.is_cuda and out.dtype in (torch.float32, torch.bfloat16, torch.float16) and out.dim() == 4
             and attn_p.shape == out.shape == attn_r.shape and attn_p.dtype == out.dtype == attn_r.dtype
             and mask_p.dtype == out.dtype == mask_r.dtype
             and tuple(mask_p.shape) == (out.size(0), 1, out.size(2), out.size(3)) == tuple(mask_r.shape))

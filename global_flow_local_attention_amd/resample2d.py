@@ -48,7 +48,7 @@ class Resample2dFunction(Function):
         # d/d input1 is handed over UNINITIALISED (flag bit 1 below): the library overwrites it where every element has one
         # writer and zero-fills it itself where it has to accumulate with atomics
         g1 = torch.empty_like(input1) if want1 else None
-        g2 = _lib.reduction_like(input2) if want2 else None  # float32 accumulator for bf16 storage
+        g2 = _lib.reduction_like(input2) if want2 else None  # float32 accumulator for 16-bit storage
         grad_warped = grad_warped.contiguous()
         if (want1 or want2) and grad_warped.numel() > 0 and input1.numel() > 0:
             _, C, Hi, Wi = input1.shape
@@ -73,16 +73,17 @@ class Resample2dFunction(Function):
             try:
                 run(input1, input2, grad_warped, g1, g2, sfx)
             except _lib.Unsupported:
-                if sfx != "bf16":
+                if sfx not in ("bf16", "f16"):
                     raise
-                # bfloat16 planes beyond the LDS budget: the bf16 backward exists for the planes-in-LDS kernels only; storage is
-                # widened for this call (exact up-casts; d/d input1 rounded to bf16 once at the end) -- block_extractor.py
+                # 16-bit planes beyond the LDS budget: the bf16 / f16 backward exists for the planes-in-LDS kernels only; storage
+                # is widened for this call (exact up-casts; d/d input1 rounded to the storage type once at the end) --
+                # block_extractor.py
                 i1, i2, gw = _lib.convert_many([input1, input2, grad_warped], torch.float32)
                 g1_32 = torch.empty_like(i1) if want1 else None
                 if g2 is not None:
                     g2.zero_()   # (a first, refused call may not have touched it; the float32 kernels accumulate into it)
                 run(i1, i2, gw, g1_32, g2, "f32")
-                g1 = None if g1_32 is None else _lib.convert_many([g1_32], torch.bfloat16)[0]
+                g1 = None if g1_32 is None else _lib.convert_many([g1_32], input1.dtype)[0]
         elif g1 is not None:
             g1.zero_()  # nothing was launched (an empty input2 / gradient): d/d input1 is zero, not uninitialised memory
         if g2 is not None and g2.dtype != input2.dtype:

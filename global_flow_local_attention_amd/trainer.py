@@ -12,7 +12,10 @@ bucketed all-reduce launched from autograd hooks (dist.GradBucketReducer), overl
   backward (reducer hooks), optimizer step.  The adversarial and VGG style/content terms need the reference's
   discriminators / a pretrained VGG19 and are injected as callables (stubbed to zero by default, as BASELINE config 4
   prescribes); the L1 reconstruction, sampling-correctness and affine-regularisation terms use this package's ops.
+  `amp="fp16"` / `"bf16"` runs the generator and the losses under torch.autocast (fp16 with a GradScaler).
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -63,11 +66,22 @@ class TrainerShell(object):
     """net_G: the reference generator (e.g. PoseGenerator built after gfla.install()); its forward is called as
     net_G(*inputs) and must return (generated, flow_fields, masks) like generator.py:13-36.
     lambdas: weights of the loss terms (pose_model.py:34-41 defaults).  gan_loss / style_content_loss: callables
-    (generated, target) -> scalar; None = 0 (stubbed)."""
+    (generated, target) -> scalar; None = 0 (stubbed).
+    amp: None (float32 step, the default), "fp16" -- the forward and the loss terms under torch.autocast("cuda",
+    float16), the backward through a torch.amp.GradScaler -- or "bf16" (autocast bfloat16, no scaler).  With the scaler the
+    bucketed all-reduce carries SCALED gradients: an inf / NaN on any rank reaches every rank through the sum, so every
+    rank's scaler skips the same step."""
+
+    AMP_DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
 
     def __init__(self, net_G, lr=1e-4, betas=(0.0, 0.999), lambda_rec=5.0, lambda_correct=5.0, lambda_regularization=0.0025,
                  correctness=None, regularization=None, gan_loss=None, style_content_loss=None, attn_layer=(2, 3),
-                 bucket_mb=32.0):
+                 bucket_mb=32.0, amp=None):
+        if amp is not None and amp not in self.AMP_DTYPES:
+            raise ValueError("TrainerShell: amp must be None, 'fp16' or 'bf16' (got %r)" % (amp,))
+        self.amp = amp
+        self.scaler = torch.amp.GradScaler("cuda") if amp == "fp16" else None
+        self.skipped_steps = 0   # steps the scaler skipped (inf / NaN in the gradients)
         self.net_G = net_G
         self.optimizer_G = torch.optim.Adam([p for p in net_G.parameters() if p.requires_grad], lr=lr, betas=betas)
         self.l1 = nn.L1Loss()
@@ -88,19 +102,32 @@ class TrainerShell(object):
     def optimize_parameters(self, inputs, target, source=None):
         """One generator step on THIS rank's (already sharded) batch.  Returns the loss terms as floats."""
         self.optimizer_G.zero_grad(set_to_none=True)
-        generated, flow_fields, _masks = self.net_G(*inputs)
-        terms = {"app_gen": self.l1(generated, target) * self.lambdas["rec"]}                       # pose_model.py:165
-        if self.correctness is not None and source is not None:                                      # :158-159
-            terms["correctness_gen"] = self.correctness(target, source, flow_fields, self.attn_layer) * self.lambdas["correct"]
-        if self.regularization is not None:                                                          # :161-162
-            terms["regularization"] = self.regularization(flow_fields) * self.lambdas["regularization"]
-        if self.gan_loss is not None:                                                                # :150-153
-            terms["ad_gen"] = self.gan_loss(generated, target)
-        if self.style_content_loss is not None:                                                      # :168-176
-            terms["style_content_gen"] = self.style_content_loss(generated, target)
-        total = sum(terms.values())
-        total.backward()          # the reducer's hooks launch each bucket's all-reduce as soon as it is complete
-        self.reducer.finish()
-        self.optimizer_G.step()
+        amp = (torch.autocast("cuda", dtype=self.AMP_DTYPES[self.amp]) if self.amp is not None
+               else contextlib.nullcontext())
+        with amp:
+            generated, flow_fields, _masks = self.net_G(*inputs)
+            terms = {"app_gen": self.l1(generated, target) * self.lambdas["rec"]}                   # pose_model.py:165
+            if self.correctness is not None and source is not None:                                  # :158-159
+                terms["correctness_gen"] = (self.correctness(target, source, flow_fields, self.attn_layer)
+                                            * self.lambdas["correct"])
+            if self.regularization is not None:                                                      # :161-162
+                terms["regularization"] = self.regularization(flow_fields) * self.lambdas["regularization"]
+            if self.gan_loss is not None:                                                            # :150-153
+                terms["ad_gen"] = self.gan_loss(generated, target)
+            if self.style_content_loss is not None:                                                  # :168-176
+                terms["style_content_gen"] = self.style_content_loss(generated, target)
+            total = sum(terms.values())
+        if self.scaler is not None:
+            self.scaler.scale(total).backward()   # scaled gradients through the reducer's hooks
+            self.reducer.finish()
+            scale = self.scaler.get_scale()
+            self.scaler.step(self.optimizer_G)    # unscales; skips the step if any gradient is inf / NaN
+            self.scaler.update()
+            if self.scaler.get_scale() < scale:
+                self.skipped_steps += 1
+        else:
+            total.backward()      # the reducer's hooks launch each bucket's all-reduce as soon as it is complete
+            self.reducer.finish()
+            self.optimizer_G.step()
         self.losses = {k: float(v.detach()) for k, v in terms.items()}
         return self.losses

@@ -26,8 +26,9 @@
  *   - return 0 on success, a negative gfla_status otherwise (the reference returns 1 always and
  *     swallows launch errors, block_extractor_cuda.cc:11, block_extractor_kernel.cu:215);
  *   - suffix = storage type: _f32, _f64 (the two types the reference dispatches,
- *     AT_DISPATCH_FLOATING_TYPES) and _bf16 (new; forward AND backward, fp32 arithmetic inside, reductions over
- *     channels returned in float32).  bf16 buffers are raw uint16_t bit patterns.
+ *     AT_DISPATCH_FLOATING_TYPES), _bf16 and _f16 (new, 16-bit storage: forward AND backward, fp32 arithmetic inside,
+ *     reductions over channels returned in float32).  bf16 / f16 buffers are raw uint16_t bit patterns; f16 is IEEE
+ *     binary16 (stores round to nearest even, overflow to +-inf, subnormals kept).
  */
 #ifndef GFLA_HIP_H_
 #define GFLA_HIP_H_
@@ -57,7 +58,8 @@ typedef void *gfla_stream_t; /* hipStream_t */
  *   7: round 5 (path ids 13-17, tuning keys 30-41: the big-plane kernels of csrc/tile_map.h; gfla_big_plane_geometry,
  *      gfla_xcd_swizzle)
  *   8: round 6 (arithmetic mode 5 of gfla_fc_*: Winograd domain with two-term f16 operands on the f16 matrix cores,
- *      csrc/fc_wino16.hip; path ids 18 / 19; tuning keys 43, 46, 49, 52) */
+ *      csrc/fc_wino16.hip; path ids 18 / 19; tuning keys 43, 46, 49, 52); float16 storage (the _f16 entry points,
+ *      gfla_fc_forward_f16, gfla_convert_multi flags 2 / 3, path id 21) only ADDS symbols and ids and keeps 8 */
 #define GFLA_ABI_VERSION 8
 int gfla_abi_version(void);
 const char *gfla_status_string(int status);
@@ -130,7 +132,8 @@ enum gfla_path {
   GFLA_PATH_FC_FWD_MODE5 = 18, /* round 6: gfla_fc_forward_f32 / gfla_fc_backward_f32 in arithmetic mode 5 */
   GFLA_PATH_FC_BWD_MODE5 = 19,
   GFLA_PATH_GEMM_F64 = 20,     /* gfla_gemm_f64 (float64 FC layers of ExtractorAttn on the FP64 matrix cores) */
-  GFLA_PATH_COUNT = 21
+  GFLA_PATH_FC_PACK_F16 = 21,  /* gfla_fc_forward_f16: activation records packed straight from the float16 maps */
+  GFLA_PATH_COUNT = 22
 };
 int64_t gfla_path_count(int path);
 
@@ -161,6 +164,7 @@ int64_t gfla_xcd_swizzle(int64_t block, int64_t nwg);
 GFLA_DECL_BLOCK_EXTRACTOR(f32, float)
 GFLA_DECL_BLOCK_EXTRACTOR(f64, double)
 GFLA_DECL_BLOCK_EXTRACTOR(bf16, uint16_t)
+GFLA_DECL_BLOCK_EXTRACTOR(f16, uint16_t)
 #undef GFLA_DECL_BLOCK_EXTRACTOR
 
 #define GFLA_DECL_BLOCK_EXTRACTOR_BWD(SFX, T)                                                      \
@@ -193,6 +197,7 @@ int gfla_unfold_supported(int64_t Hs, int64_t Ws, int kernel_size, int elem_size
 GFLA_DECL_UNFOLD_FWD(f32, float)
 GFLA_DECL_UNFOLD_FWD(f64, double)
 GFLA_DECL_UNFOLD_FWD(bf16, uint16_t)
+GFLA_DECL_UNFOLD_FWD(f16, uint16_t)
 #undef GFLA_DECL_UNFOLD_FWD
 
 #define GFLA_DECL_UNFOLD_BWD(SFX, T)                                                               \
@@ -220,6 +225,7 @@ GFLA_DECL_UNFOLD_BWD(f64, double)
 GFLA_DECL_RESHAPE(f32, float)
 GFLA_DECL_RESHAPE(f64, double)
 GFLA_DECL_RESHAPE(bf16, uint16_t)
+GFLA_DECL_RESHAPE(f16, uint16_t)
 #undef GFLA_DECL_RESHAPE
 
 /* ---- resample2d --------------------------------------------------------------------------
@@ -243,6 +249,7 @@ GFLA_DECL_RESHAPE(bf16, uint16_t)
 GFLA_DECL_RESAMPLE_FWD(f32, float)
 GFLA_DECL_RESAMPLE_FWD(f64, double)
 GFLA_DECL_RESAMPLE_FWD(bf16, uint16_t)
+GFLA_DECL_RESAMPLE_FWD(f16, uint16_t)
 #undef GFLA_DECL_RESAMPLE_FWD
 
 #define GFLA_DECL_RESAMPLE_BWD(SFX, T)                                                             \
@@ -278,9 +285,10 @@ GFLA_DECL_RESAMPLE_BWD(f64, double)
 GFLA_DECL_AGGREGATE_FWD(f32, float)
 GFLA_DECL_AGGREGATE_FWD(f64, double)
 GFLA_DECL_AGGREGATE_FWD(bf16, uint16_t)
+GFLA_DECL_AGGREGATE_FWD(f16, uint16_t)
 #undef GFLA_DECL_AGGREGATE_FWD
 
-/* Forward with scratch (f32 / bf16 storage): softmax, tap geometry and the (k+1)x(k+1) patch coefficients of every
+/* Forward with scratch (f32 / bf16 / f16 storage): softmax, tap geometry and the (k+1)x(k+1) patch coefficients of every
  * flow pixel are computed ONCE (a table of (k+1)(k+2) floats + one word per pixel in `workspace`,
  * gfla_aggregate_fwd_workspace_bytes(B, H, W, k) bytes, 16-byte aligned) instead of once per channel group, and the
  * aggregation reads patch rows from LDS with paired 64-bit reads.  workspace == NULL, even k or Ws < k + 1: the
@@ -302,6 +310,10 @@ int gfla_local_attn_aggregate_fwd_ws_bf16(const uint16_t *source, const uint16_t
                                           uint16_t *out, uint16_t *attn_out, void *workspace, int64_t B, int64_t C,
                                           int64_t Hs, int64_t Ws, int64_t H, int64_t W, int kernel_size,
                                           int apply_softmax, gfla_stream_t stream);
+int gfla_local_attn_aggregate_fwd_ws_f16(const uint16_t *source, const uint16_t *flow, const uint16_t *logits,
+                                         uint16_t *out, uint16_t *attn_out, void *workspace, int64_t B, int64_t C,
+                                         int64_t Hs, int64_t Ws, int64_t H, int64_t W, int kernel_size,
+                                         int apply_softmax, gfla_stream_t stream);
 
 #define GFLA_DECL_AGGREGATE_BWD(SFX, T)                                                            \
   int gfla_local_attn_aggregate_bwd_##SFX(const T *source, const T *flow, const T *attn,           \
@@ -337,6 +349,28 @@ int gfla_local_attn_source_bwd_bf16(const uint16_t *source, const uint16_t *flow
 int gfla_resample2d_bwd_bf16(const uint16_t *in1, const uint16_t *in2, const uint16_t *grad_out, uint16_t *grad_in1,
                              float *grad_in2, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
                              int kernel_size, int dilation, int trunc_compat, gfla_stream_t stream);
+
+/* f16 storage for the same backward entry points: the bf16 signatures and rules, IEEE binary16 feature maps. */
+#define GFLA_DECL_BWD16(SFX, T)                                                                                        \
+  int gfla_block_extractor_bwd_##SFX(const T *source, const T *flow, const T *grad_out, T *grad_source, float *grad_flow, \
+                                     int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf,               \
+                                     int kernel_size, gfla_stream_t stream);                                             \
+  int gfla_block_extractor_unfold_bwd_##SFX(const T *source, const T *flow, const T *grad_unfold, T *grad_source,        \
+                                            float *grad_flow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,  \
+                                            int64_t Wf, int kernel_size, int layout, gfla_stream_t stream);              \
+  int gfla_local_attn_aggregate_bwd_##SFX(const T *source, const T *flow, const T *attn, const T *grad_out,             \
+                                          T *grad_source, float *grad_flow, float *grad_logits, int64_t B, int64_t C,    \
+                                          int64_t Hs, int64_t Ws, int64_t H, int64_t W, int kernel_size,                 \
+                                          int apply_softmax, gfla_stream_t stream);                                      \
+  int gfla_local_attn_source_bwd_##SFX(const T *source, const T *flow, const T *grad_unfold, const T *attn,             \
+                                       const T *grad_out, T *grad_source, float *grad_flow, int64_t B, int64_t C,        \
+                                       int64_t Hs, int64_t Ws, int64_t H, int64_t W, int kernel_size, int layout,        \
+                                       gfla_stream_t stream);                                                            \
+  int gfla_resample2d_bwd_##SFX(const T *in1, const T *in2, const T *grad_out, T *grad_in1, float *grad_in2, int64_t B, \
+                                int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int kernel_size, int dilation,  \
+                                int trunc_compat, gfla_stream_t stream);
+GFLA_DECL_BWD16(f16, uint16_t)
+#undef GFLA_DECL_BWD16
 
 /* ---- scatters as block-sparse products on the matrix cores (csrc/patch_mfma.hip) -----------------------------
  * The two backward passes that scatter into a feature plane -- the aggregation's d/d source and resample2d's
@@ -434,6 +468,14 @@ int gfla_fc_backward_f32(void *workspace, const float *flow, const float *w1, co
                          void *scratch, float *grad_source, float *grad_target, float *grad_flow, float *grad_w0,
                          float *grad_b0, float *grad_w1, float *grad_b1, int64_t B, int64_t C, int64_t H,
                          int64_t W, int kernel_size, double slope, int mode, int flags, gfla_stream_t stream);
+/* float16 FEATURES: the forward of arithmetic mode 1 with the activation records packed straight from the f16 maps (an f16
+ * value IS one f16 term: written unscaled, no max |x| pass over the features, no float32 copy of source or target).
+ * source, target (B,C,H,W) f16; flow (B,2,H,W) float32 (the sampling tail and the backward read it in float32); w0, b0,
+ * w1, b1, logits float32.  The workspace is mode 1's (gfla_fc_workspace_bytes(..., 1, 0)) and gfla_fc_backward_f32(...,
+ * mode = 1, ...) takes it as it stands.  Dispatch trace: GFLA_PATH_FC_FWD_MODE1 and GFLA_PATH_FC_PACK_F16. */
+int gfla_fc_forward_f16(const uint16_t *source, const uint16_t *target, const float *flow, const float *w0,
+                        const float *b0, const float *w1, const float *b1, void *workspace, float *logits,
+                        int64_t B, int64_t C, int64_t H, int64_t W, int kernel_size, double slope, gfla_stream_t stream);
 /* Pieces of the above for the parity tests.  gfla_fc_geometry: out[0..12] = Hp, Wp, Ho, Wo, pad_top, pad_left, M,
  * Md, lead, Sx, Sz, Mg, Mdg of one half (is_source: the source half is extended by k-1, the target half padded by
  * k/2).  gfla_fc_conv_fwd: out (B, Mg, 128) = the convolved map of one half, row yo*Wo + xo.  gfla_fc_conv_bwd:
@@ -523,6 +565,10 @@ int gfla_correctness_map_bwd_f32(const float *warped, const float *target, const
  * operands and narrows three gradients per call; at the face model's batch every one of them was a launch of its own. */
 int gfla_convert_multi(const void *src0, void *dst0, int64_t n0, const void *src1, void *dst1, int64_t n1, const void *src2,
                        void *dst2, int64_t n2, const void *src3, void *dst3, int64_t n3, int to_bf16, gfla_stream_t stream);
+/* to_bf16 (the flag word above) also takes GFLA_CONVERT_F16_TO_F32 (float16 -> float32, exact) and GFLA_CONVERT_F32_TO_F16
+ * (float32 -> float16, round to nearest even, overflow to +-inf, subnormals kept).  0 and 1 keep their meaning. */
+#define GFLA_CONVERT_F16_TO_F32 2
+#define GFLA_CONVERT_F32_TO_F16 3
 
 /* ---- mask blend of the face model's attention pair (generator.py:496-499; csrc/mask_blend.hip, round 4) ----
  *   y = (out*(1-mask_p) + attn_p*mask_p) + (out*(1-mask_r) + attn_r*mask_r)
@@ -540,6 +586,12 @@ int gfla_mask_blend_bwd_bf16(const uint16_t *out, const uint16_t *attn_p, const 
                              const uint16_t *mask_r, const uint16_t *grad_y, uint16_t *g_out, uint16_t *g_attn_p,
                              uint16_t *g_attn_r, float *g_mask_p, float *g_mask_r, int64_t B, int64_t C, int64_t HW,
                              gfla_stream_t stream);
+int gfla_mask_blend_fwd_f16(const uint16_t *out, const uint16_t *attn_p, const uint16_t *attn_r, const uint16_t *mask_p,
+                            const uint16_t *mask_r, uint16_t *y, int64_t B, int64_t C, int64_t HW, gfla_stream_t stream);
+int gfla_mask_blend_bwd_f16(const uint16_t *out, const uint16_t *attn_p, const uint16_t *attn_r, const uint16_t *mask_p,
+                            const uint16_t *mask_r, const uint16_t *grad_y, uint16_t *g_out, uint16_t *g_attn_p,
+                            uint16_t *g_attn_r, float *g_mask_p, float *g_mask_r, int64_t B, int64_t C, int64_t HW,
+                            gfla_stream_t stream);
 
 #ifdef __cplusplus
 }
