@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the GFLA feature-warping hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch of B synthetic images
@@ -28,7 +28,9 @@ convolution, modes 3 / 2 (f16-split operands, f32 accumulation) are labelled exp
 `python bench.py --gpus N` without a torchrun environment spawns its own N ranks (self_spawn); the torchrun form of
 the contract works as well.
 
-Rank 0 prints ONE JSON line (contract in the task statement) that additionally carries
+Rank 0 prints ONE JSON line, the headline (metric, value, unit, ms_per_step, ...).  A plain run does only what that
+headline needs: it sets up, runs W untimed and K timed steps, writes --dump-outputs if asked, and prints the line.
+With --full the line additionally carries
   "roofline":     the dominant gfx950 kernel of the step -- an MFMA kernel: executed FLOPs / HIP-event duration
                   against the 157.3 TFLOP/s f32 matrix-core peak
   "kernels":      per C-ABI entry point of the step: HIP-event time, algorithmic bytes and FLOPs; and per internal
@@ -41,6 +43,8 @@ Rank 0 prints ONE JSON line (contract in the task statement) that additionally c
   "variants":     the same step with the other FC arithmetic modes / stream arrangements (not the headline)
   "cpu_baseline": the reference composition with the CPU oracle kernels on the host cores,
                   timed on a bounded sample of the same workload (rank 0, N=1 only)
+  "dist":         N > 1: the process group's fingerprint and the all-gather of the generated tiles
+All of these run after the timed region; --no-cpu-baseline / --no-variants / --no-legs leave parts of them out.
 """
 import argparse
 import json
@@ -1281,16 +1285,18 @@ def run(args, make_hotpath, make_resample, rank, world, device, on_gpu=True, dat
     if dump_dir and rank == 0:
         dumped = dump_outputs(dump_dir, hp.named_results(last[0]))
     del last[:]
+    # Everything from here to the printed line is --full only: the headline needs none of it.
+    full = getattr(args, "full", False)
     # The oracle check runs AFTER the timed region: it is 16 OpenMP threads of host work, and worker threads still spinning
     # behind their last parallel region compete with the launching thread -- a timed region started right behind the
     # check was measured at 5.4 / 6.2 ms per step instead of 4.7 on two occasions.  It still fails the run on a mismatch.
     check = None
-    if rank == 0 and world == 1 and on_gpu and not args.no_cpu_baseline and not custom:
+    if full and rank == 0 and world == 1 and on_gpu and not args.no_cpu_baseline and not custom:
         check = oracle_check(hp, resample)
         time.sleep(1.0)  # let the host threads of the check go idle before the variants / legs are timed
 
     rows, probes = [], []
-    if on_gpu:
+    if full and on_gpu:
         # instrumented pass: the same K steps with every C-ABI call bracketed by HIP events
         with KernelTimer() as kt:
             for _ in range(args.steps):
@@ -1300,7 +1306,7 @@ def run(args, make_hotpath, make_resample, rank, world, device, on_gpu=True, dat
             probes = fc_kernel_probes(hp)
 
     variants = {}
-    if on_gpu and args.fc_impl == "mfma" and not args.no_variants and not custom:
+    if full and on_gpu and args.fc_impl == "mfma" and not args.no_variants and not custom:
         notes = {0: "float32, DIRECT convolution kernels (a k-ordered fma chain per output): the same step without the "
                     "Winograd-domain formulation",
                  4: "float32 operands on f32 MFMA, Winograd-domain convolutions and weight gradient (the default of rounds 3-5)",
@@ -1448,13 +1454,13 @@ def run(args, make_hotpath, make_resample, rank, world, device, on_gpu=True, dat
         line["variants"] = variants
     if dumped is not None:
         line["dumped_outputs"] = {"dir": dump_dir, "arrays": dumped}
-    if world > 1:   # every rank takes part (collectives); the fingerprint proves N ranks met on the backend
+    if full and world > 1:   # every rank takes part (collectives); the fingerprint proves N ranks met on the backend
         line["dist"] = dist_leg(args, rank, world, device, on_gpu, barrier,
                                 tile_shape=None if on_gpu else (args.batch, 3, 8, 6))
-    if rank == 0 and world == 1 and on_gpu and not custom and not getattr(args, "no_legs", False):
+    if full and rank == 0 and world == 1 and on_gpu and not custom and not getattr(args, "no_legs", False):
         # the north star's own figure: block_extractor (reference layout) + local-attention forward against the HBM roofline
         line["north_star"] = op_roofline(device, B=args.batch)
-    if rank == 0 and world == 1 and on_gpu and not custom and not getattr(args, "no_legs", False) \
+    if full and rank == 0 and world == 1 and on_gpu and not custom and not getattr(args, "no_legs", False) \
             and not getattr(args, "with_losses", False):
         line["legs"] = extra_legs(args, device)
     if check is not None:
@@ -1465,7 +1471,7 @@ def run(args, make_hotpath, make_resample, rank, world, device, on_gpu=True, dat
     if getattr(args, "one_stream", False):
         line["streams"] = "--one-stream: warps issued on the attention layers' stream (trace run; the headline uses two)"
     if rank == 0:
-        if world == 1 and on_gpu and not args.no_cpu_baseline and not custom:
+        if full and world == 1 and on_gpu and not args.no_cpu_baseline and not custom:
             line["cpu_baseline"] = cpu_baseline(args.cpu_budget)
         print(compact_line(line, write_detail(line))[1], flush=True)
     return line
@@ -1579,12 +1585,17 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (oracle check + baseline)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the labelled variants (other FC arithmetic modes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: the oracle check, per-kernel times and the "
+                         "roofline, the variants, the north star, the legs of the other BASELINE configs, the CPU baseline "
+                         "and, for N > 1, the process-group fingerprint (`dist`).  Off by default: a plain run times the "
+                         "headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU legs (oracle check + baseline)")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the labelled variants (other FC arithmetic modes)")
     ap.add_argument("--tuning", default="", help="library tuning keys for A/B runs: key=value[,key=value...] (include/gfla_hip.h)")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the compact legs for the other BASELINE configs (config-3 inference, with-losses, trainer "
-                         "step, face bf16) that the default N=1 run appends under `legs`")
+                    help="--full: skip the compact legs for the other BASELINE configs (config-3 inference, with-losses, "
+                         "trainer step, face bf16) that an N=1 run appends under `legs`, and the north star")
     ap.add_argument("--no-vgg-grad", action="store_true",
                     help="treat the VGG features fed to Resample2d as constants (what the reference's training step "
                          "does: they come from a frozen VGG of the input images), i.e. skip d/d input1")

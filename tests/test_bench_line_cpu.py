@@ -42,13 +42,13 @@ def test_compact_line_sheds_optional_objects_before_it_overflows():
 
 
 def test_last_stdout_line_of_an_n2_run_is_short_and_detail_goes_to_a_file(tmp_path):
-    """`python bench.py --gpus 2` on two gloo ranks (GFLA_BENCH_CPU_STUB): exactly one JSON line on stdout, < 4 KB, with
-    the `dist` fingerprint; the full record is in the detail file."""
+    """`python bench.py --gpus 2 --full` on two gloo ranks (GFLA_BENCH_CPU_STUB): exactly one JSON line on stdout, < 4 KB,
+    with the `dist` fingerprint; the full record is in the detail file."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     detail = str(tmp_path / "detail.json")
     env.update(GFLA_BENCH_CPU_STUB="1", OMP_NUM_THREADS="1", BENCH_DETAIL=detail)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--batch", "4"], env=env, capture_output=True, text=True, timeout=300)
+                          "--batch", "4", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     last = res.stdout.strip().splitlines()[-1]
     assert len(last) < 4096
@@ -58,6 +58,21 @@ def test_last_stdout_line_of_an_n2_run_is_short_and_detail_goes_to_a_file(tmp_pa
     assert line["n_gpus"] == 2 and line["dist"]["world_size_seen_by_group"] == 2
     full = json.load(open(detail))
     assert full["value"] == line["value"] and "kernels" in full
+
+
+def test_a_plain_n2_run_prints_the_headline_without_the_dist_leg(tmp_path):
+    """Without --full the same N = 2 run prints the contract's keys and nothing the headline does not need."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(GFLA_BENCH_CPU_STUB="1", OMP_NUM_THREADS="1", BENCH_DETAIL=str(tmp_path / "detail.json"))
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                          "--batch", "4"], env=env, capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    line = json.loads(lines[0])
+    for k in REQUIRED:
+        assert k in line, k
+    assert line["n_gpus"] == 2 and line["steps"] == 2 and line["value"] > 0 and "dist" not in line
 
 
 def test_dump_outputs_writes_the_last_step_identically_across_runs(tmp_path):

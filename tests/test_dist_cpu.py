@@ -172,12 +172,13 @@ def _bench_worker(rank, world, port, ret):
     from global_flow_local_attention_amd import dist as gd
     import torch.distributed as dist
     r, w, _ = gd.init_from_env(backend="gloo")
-    args = bench.parse_args(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "4", "--no-cpu-baseline"])
+    args = bench.parse_args(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "4", "--no-cpu-baseline",
+                             "--full"])
     line = bench.run(args, lambda mode: _StubHotPath(r), lambda: (lambda t: t * 2.0), r, w, torch.device("cpu"),
                      on_gpu=False)
     assert line["n_gpus"] == world and line["steps"] == 3 and line["warmup"] == 1
     assert line["config"]["global_batch"] == 4 * world and line["value"] > 0 and line["scaling"] == "weak"
-    # the N > 1 leg the first multi-GPU run will record: process-group fingerprint + the all-gather of generated tiles
+    # the N > 1 leg of --full: process-group fingerprint + the all-gather of generated tiles
     d = line["dist"]
     assert d["backend"] == "gloo" and d["world_size_seen_by_group"] == world
     assert d["allreduce_of_rank_ids"] == d["allreduce_expected"] == world * (world + 1) / 2.0
@@ -207,13 +208,14 @@ def test_bench_control_flow_world2_gloo():
 def test_bench_self_spawn_world2_gloo():
     """`python bench.py --gpus 2` with NO torchrun environment (the shape of the N=1 command with a different N) must not
     exit with a usage error: it spawns its own ranks under torch.distributed.run and rank 0 prints ONE JSON line with
-    n_gpus = 2.  GFLA_BENCH_CPU_STUB swaps the GPU workload for a stand-in so the launcher runs where there is no GPU."""
+    n_gpus = 2 (--full: and the `dist` leg).  GFLA_BENCH_CPU_STUB swaps the GPU workload for a stand-in so the launcher
+    runs where there is no GPU."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GFLA_BENCH_CPU_STUB="1", OMP_NUM_THREADS="1")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--batch", "4"], env=env, capture_output=True, text=True, timeout=300)
+                          "--batch", "4", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout

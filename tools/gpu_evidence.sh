@@ -15,9 +15,9 @@ timeout 600 python -m pytest tests/test_bench_shapes_gpu.py tests/test_fc_wino_g
 for M in 4 0; do
   timeout 300 python tools/bench_inference.py --fc-mode $M > $OUT/inference_config3_mode$M.jsonl 2> $OUT/inference_mode$M.err; echo "inference mode $M rc=$?"; tail -1 $OUT/inference_config3_mode$M.jsonl | cut -c1-300
 done
-timeout 600 python bench.py --workload trainer_step --no-variants --no-legs > $OUT/bench_trainer_step.json 2> $OUT/bench_trainer_step.err; echo "trainer_step rc=$?"; cut -c1-400 $OUT/bench_trainer_step.json
-GFLA_DIST_BACKEND=gloo GFLA_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-variants --no-legs > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err; echo "2-rank rc=$?"; cut -c1-300 $OUT/bench_2rank_gloo.json
-GFLA_DIST_BACKEND=gloo GFLA_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 3 --warmup 1 --workload trainer_step --no-cpu-baseline --no-variants --no-legs > $OUT/bench_trainer_2rank_gloo.json 2> $OUT/bench_trainer_2rank_gloo.err; echo "2-rank trainer rc=$?"; cut -c1-300 $OUT/bench_trainer_2rank_gloo.json
+timeout 600 python bench.py --full --workload trainer_step --no-variants --no-legs > $OUT/bench_trainer_step.json 2> $OUT/bench_trainer_step.err; echo "trainer_step rc=$?"; cut -c1-400 $OUT/bench_trainer_step.json
+GFLA_DIST_BACKEND=gloo GFLA_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-variants --no-legs > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err; echo "2-rank rc=$?"; cut -c1-300 $OUT/bench_2rank_gloo.json
+GFLA_DIST_BACKEND=gloo GFLA_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --steps 3 --warmup 1 --workload trainer_step --no-cpu-baseline --no-variants --no-legs > $OUT/bench_trainer_2rank_gloo.json 2> $OUT/bench_trainer_2rank_gloo.err; echo "2-rank trainer rc=$?"; cut -c1-300 $OUT/bench_trainer_2rank_gloo.json
 # Winograd convolution (k = 5, forward of the source half = which 0): whole kernel, then with parts compiled out
 {
   echo "fc_wino_conv_kernel<5> at C128 64x44 B=32 (tools/probe_wino.py, PROBE_K=5, 10 launches each; which 0..3 = forward t/s, data gradient t/s)"

@@ -1,5 +1,5 @@
 #!/usr/bin/env bash
-# Round-end evidence in one GPU call: the default bench; HBM traffic counters of the bench step (-> profiles/pmc_traffic.json,
+# Round-end evidence in one GPU call: the full bench (--full); HBM traffic counters of the bench step (-> profiles/pmc_traffic.json,
 # which bench.py's roofline.traffic reads) and of the north star's two forward ops; MFMA-pipe utilisation of the FC kernels;
 # LDS counters of the block_extractor forward and aggregation forward kernels; kernel trace of the default bench
 # (steady-state per-step table).  Counter passes are separate rocprofv3 runs with --kernel-trace only.
@@ -9,10 +9,10 @@ TAG="${1:-final}"
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-# the default bench FIRST: after rocprofv3 --pmc passes in the same job the f32-MFMA kernels run ~10 % slower for a while
+# the full bench FIRST: after rocprofv3 --pmc passes in the same job the f32-MFMA kernels run ~10 % slower for a while
 # (the last stdout line is the short one; the full record is written to the detail file)
-( time BENCH_DETAIL=$OUT/bench_detail.json timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err ) 2> $OUT/bench.time; echo "bench rc=$?"; cut -c1-300 $OUT/bench.json; cat $OUT/bench.time | tail -3
-BENCH="python $PWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-variants --no-legs"
+( time BENCH_DETAIL=$OUT/bench_detail.json timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err ) 2> $OUT/bench.time; echo "bench rc=$?"; cut -c1-300 $OUT/bench.json; cat $OUT/bench.time | tail -3
+BENCH="python $PWD/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-variants --no-legs"
 NS="python $PWD/tools/bench_north_star.py --sweep none --iters 3"
 for C in FETCH_SIZE WRITE_SIZE; do
   (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d /tmp/fin_$C -o pmc -- $BENCH > $OUT/pmc_$C.log 2>&1); echo "$C rc=$?"
@@ -35,6 +35,6 @@ python tools/pmc_summary.py "$F" "$W" $OUT/config2_pmc_traffic.json "$TAG config
 bash tools/gpu_pmc_fc.sh $TAG/mfma --no-variants --no-legs > $OUT/mfma.log 2>&1; grep -E "fc_conv|fc_wgrad|fc_wino" $OUT/mfma/pmc_set1.txt 2>/dev/null | cut -c1-250 | head -12
 bash tools/gpu_pmc_lds.sh $TAG/ns_lds "_kernel" -- $NS > /dev/null 2>&1
 grep -E "be_fwd|agg_" $OUT/ns_lds/pmc_summary.txt | cut -c1-330
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fin_trace -o bench -- python $OLDPWD/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-variants --no-legs > $OUT/rocprof_bench.log 2>&1); echo "trace rc=$?"
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fin_trace -o bench -- python $OLDPWD/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-variants --no-legs > $OUT/rocprof_bench.log 2>&1); echo "trace rc=$?"
 cp /tmp/fin_trace/bench_kernel_stats.csv $OUT/ 2>/dev/null
 python tools/trace_steps.py /tmp/fin_trace/bench_kernel_trace.csv "fc_tail_fwd_kernel<3>" > $OUT/steady_state_steps.txt 2>&1; head -50 $OUT/steady_state_steps.txt

@@ -11,7 +11,7 @@ for SET in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
            "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VMEM SQ_WAVES" \
            "GRBM_GUI_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_INSTS_SALU SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM SQ_INSTS_SMEM SQ_WAVE_CYCLES"; do
   i=$((i+1))
-  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d /tmp/sq_${TAG}_$i -o pmc -- python $OLDPWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OLDPWD/$OUT/sq_$i.log 2>&1); echo "set $i rc=$?"
+  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d /tmp/sq_${TAG}_$i -o pmc -- python $OLDPWD/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OLDPWD/$OUT/sq_$i.log 2>&1); echo "set $i rc=$?"
   f=$(find /tmp/sq_${TAG}_$i -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && python - "$f" > $OUT/sq_set$i.txt <<'PY'
 import csv, sys, collections
