@@ -232,8 +232,7 @@ struct Wn16ConvJob {   // WnConvJob with the two-term f16 weights of fc_wino16_p
   int ldo, n_valid, M, Wv, Wp;
   int64_t S;
 };
-int fc_wino16_pack_weights(const float *w0, const uint32_t *amax_w, float *u_ft, float *u_fs, float *u_dt, float *u_ds, int C,
-                           int k, hipStream_t stream);
+int fc_wino16_pack_weights(const float *w0, const uint32_t *amax_w, float *u_ft, float *u_fs, int C, int k, hipStream_t stream);
 bool fc_wino16_fits(int M, int Wv, int Wp, int k);
 int fc_wino16_conv_jobs(const Wn16ConvJob *jobs, int njobs, int64_t B, int nch, int k, const uint32_t *amax_w,
                         hipStream_t stream);

@@ -1,5 +1,6 @@
 // Winograd-domain convolutions of ExtractorAttn's first FC layer with TWO-TERM f16 OPERANDS on the f16 matrix cores
-// (arithmetic mode 5), gfx950.
+// (arithmetic mode 5), gfx950.  Mode 5 runs only the k = 3 forward here (csrc/fc_block.hip: fc_plan); the formulation below
+// covers both kernel sizes.
 //
 // Same formulation, tiling and staging as fc_wino.hip (F(2x2,5x5) / F(4x4,3x3) on the points {0, 1, -1, 2, -1/2, inf}; reference
 // base_function.py:799-807): the transforms B^T d B and A^T M A stay float32 on the vector ALUs.  What changes is the 36
@@ -27,12 +28,12 @@
 
 namespace gfla {
 
-// ---- weights: conv0.weight (128, 2C, k, k) -> U = G w G^T * scale as (hi, lo) words in B-fragment order --------------
+// ---- weights: conv0.weight (128, 2C, 3, 3) -> U = G w G^T * scale as (hi, lo) words in B-fragment order --------------
 // U16[ntile][step = ci >> 3][point][g = (ci >> 2) & 1][n = co & 63][ci & 3]: a lane of channel block nb (n = 32 nb + lane & 31,
 // g = lane >> 5) loads its 16 bytes of a (step, point) with one request; a wave's request is two runs of 512 bytes.
-template <int KS>
 __global__ __launch_bounds__(256) void fc_wino16_pack_w_kernel(const float *__restrict__ w0, WnPackJobs jobs, int C,
                                                                const uint32_t *__restrict__ amax_w) {
+  constexpr int KS = 3;
   const WnPackJob jb = jobs.j[blockIdx.y];
   const int nch = (jb.n_in + kFcChunk - 1) / kFcChunk, ntn = (jb.n_out + kWnN - 1) / kWnN;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (in channel, out channel), out fastest
@@ -45,10 +46,7 @@ __global__ __launch_bounds__(256) void fc_wino16_pack_w_kernel(const float *__re
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
       float v = 0.f;
-      if (ci < jb.n_in && co < jb.n_out) {
-        v = jb.dgrad ? w0[(((int64_t)ci * 2 * C + jb.c_off + co) * KS + (KS - 1 - i)) * KS + (KS - 1 - j)]
-                     : w0[(((int64_t)co * 2 * C + jb.c_off + ci) * KS + i) * KS + j];
-      }
+      if (ci < jb.n_in && co < jb.n_out) v = w0[(((int64_t)co * 2 * C + jb.c_off + ci) * KS + i) * KS + j];
       w[i][j] = v * su;
     }
   float t[6][KS];  // G w: columns first
@@ -73,27 +71,14 @@ __global__ __launch_bounds__(256) void fc_wino16_pack_w_kernel(const float *__re
   }
 }
 
-// the four weight sets of one layer (same slots and sizes as fc_wino_pack_weights: fc_wino_wpack_bytes)
-int fc_wino16_pack_weights(const float *w0, const uint32_t *amax_w, float *u_ft, float *u_fs, float *u_dt, float *u_ds, int C,
-                           int k, hipStream_t stream) {
+// the two forward weight sets of one layer (k = 3; same slots and sizes as fc_wino_pack_weights: fc_wino_wpack_bytes)
+int fc_wino16_pack_weights(const float *w0, const uint32_t *amax_w, float *u_ft, float *u_fs, int C, int k, hipStream_t stream) {
+  if (k != 3) return GFLA_ERR_UNSUPPORTED;
   WnPackJobs jobs;
   jobs.j[0] = WnPackJob{u_ft, 0, 0, C, kFcHidden};
   jobs.j[1] = WnPackJob{u_fs, C, 0, C, kFcHidden};
-  jobs.j[2] = WnPackJob{u_dt, 0, 1, kFcHidden, C};
-  jobs.j[3] = WnPackJob{u_ds, C, 1, kFcHidden, C};
-  int64_t most = 0;
-  for (int q = 0; q < 4; ++q) {
-    const int64_t n = ceil_div(jobs.j[q].n_out, kWnN) * kWnN * ceil_div(jobs.j[q].n_in, kFcChunk) * kFcChunk;
-    if (jobs.j[q].U && n > most) most = n;
-  }
-  if (most == 0) return GFLA_OK;
-  const dim3 grid((unsigned)ceil_div(most, 256), 4);
-  if (k == 5)
-    fc_wino16_pack_w_kernel<5><<<grid, 256, 0, stream>>>(w0, jobs, C, amax_w);
-  else if (k == 3)
-    fc_wino16_pack_w_kernel<3><<<grid, 256, 0, stream>>>(w0, jobs, C, amax_w);
-  else
-    return GFLA_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)ceil_div(ceil_div(kFcHidden, kWnN) * kWnN * ceil_div(C, kFcChunk) * kFcChunk, 256), 2);
+  fc_wino16_pack_w_kernel<<<grid, 256, 0, stream>>>(w0, jobs, C, amax_w);
   return launch_status();
 }
 
@@ -128,7 +113,7 @@ struct WnAT<4> {
 template <int PG_>
 struct PgTag { static constexpr int value = PG_; };
 
-// DBG (timing ablations, `make PROBES=1` builds only, tuning key 20; results are garbage): 1 no transform, 2 no MFMAs / A reads,
+// DBG (timing ablations; results are garbage -- no launcher instantiates them since k = 5 left this kernel): 1 no transform, 2 no MFMAs / A reads,
 // 4 no B reloads, 8 no raw staging, 32 transform without the f16 split (hi only), 64 no epilogue
 extern unsigned long long *g_wino_stamps;   // fc_wino.hip (DBG & 16: per-wave phase times, s_memtime; tools/probe_wino_phases.py)
 template <int KS, bool DB = true, int DBG = 0>
@@ -501,58 +486,28 @@ static unsigned wn16_lds_bytes(int k, const WnGeo &g, bool double_raw) {
   return main_loop > exchange ? main_loop : exchange;
 }
 
-template <int K_>
 static int wn16_launch(const Wn16ConvJob *jobs, int njobs, int64_t B, int nch, const uint32_t *amax_w, hipStream_t stream) {
   Wn16KArgs a[2];
   int64_t wgs[2] = {0, 0};
   bool db = tuning(21) != 1;
   unsigned lds = 0;
-  for (int j = 0; j < njobs; ++j) db = db && wn16_lds_bytes(K_, wn_geometry<K_>(jobs[j].M, jobs[j].Wv, jobs[j].Wp), true) <= kWnLdsLimit;
+  for (int j = 0; j < njobs; ++j) db = db && wn16_lds_bytes(3, wn_geometry<3>(jobs[j].M, jobs[j].Wv, jobs[j].Wp), true) <= kWnLdsLimit;
   for (int j = 0; j < 2; ++j) {
     const Wn16ConvJob &J = jobs[j < njobs ? j : 0];
-    const WnGeo g = wn_geometry<K_>(J.M, J.Wv, J.Wp);
+    const WnGeo g = wn_geometry<3>(J.M, J.Wv, J.Wp);
     const int ntn = (int)ceil_div(J.n_valid, kWnN);
     const int64_t groups = B * g.ngroups;
     a[j] = Wn16KArgs{J.X, J.U, J.amax_x, J.out, J.out_bs, J.ldo, J.n_valid, J.M / J.Wv, J.Wv, J.Wp, g, ntn, groups, J.S};
     if (j < njobs) {
       wgs[j] = ceil_div(groups, 8) * 8 * ntn;
-      lds = std::max(lds, wn16_lds_bytes(K_, g, db));
+      lds = std::max(lds, wn16_lds_bytes(3, g, db));
     }
   }
   if (wgs[0] + wgs[1] > 0x7fffffffLL || lds > kWnLdsLimit) return GFLA_ERR_UNSUPPORTED;
-#define GFLA_W16_LAUNCH(D_)                                                                                              \
-  {                                                                                                                     \
-    auto kern = fc_wino16_conv_kernel<K_, true, D_>;                                                                    \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    kern<<<dim3((unsigned)(wgs[0] + wgs[1])), kWnThreads, lds, stream>>>(a[0], a[1], (unsigned)wgs[0], nch, amax_w, g_wino_stamps); \
-  }
-  if (db) {
-#ifdef GFLA_PROBES
-    switch (K_ == 5 ? tuning(20) : 0) {
-      case 1: GFLA_W16_LAUNCH(1) break;
-      case 2: GFLA_W16_LAUNCH(2) break;
-      case 3: GFLA_W16_LAUNCH(3) break;
-      case 4: GFLA_W16_LAUNCH(4) break;
-      case 8: GFLA_W16_LAUNCH(8) break;
-      case 16: GFLA_W16_LAUNCH(16) break;
-      case 32: GFLA_W16_LAUNCH(32) break;
-      case 64: GFLA_W16_LAUNCH(64) break;
-      case 128: GFLA_W16_LAUNCH(128) break;
-      case 256: GFLA_W16_LAUNCH(256) break;
-      case 384: GFLA_W16_LAUNCH(384) break;
-      case 67: GFLA_W16_LAUNCH(67) break;
-      case 79: GFLA_W16_LAUNCH(79) break;
-      default: GFLA_W16_LAUNCH(0) break;
-    }
-#else
-    GFLA_W16_LAUNCH(0)
-#endif
-#undef GFLA_W16_LAUNCH
-  } else {
-    auto kern = fc_wino16_conv_kernel<K_, false>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    kern<<<dim3((unsigned)(wgs[0] + wgs[1])), kWnThreads, lds, stream>>>(a[0], a[1], (unsigned)wgs[0], nch, amax_w, nullptr);
-  }
+  auto kern = db ? fc_wino16_conv_kernel<3, true> : fc_wino16_conv_kernel<3, false>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  kern<<<dim3((unsigned)(wgs[0] + wgs[1])), kWnThreads, lds, stream>>>(a[0], a[1], (unsigned)wgs[0], nch, amax_w,
+                                                                         db ? g_wino_stamps : nullptr);
   return launch_status();
 }
 
@@ -566,14 +521,14 @@ bool fc_wino16_fits(int M, int Wv, int Wp, int k) {
 // fc_wino16_pack_weights and the max |x| slot of every job's input
 int fc_wino16_conv_jobs(const Wn16ConvJob *jobs, int njobs, int64_t B, int nch, int k, const uint32_t *amax_w, hipStream_t stream) {
   if (B <= 0 || njobs <= 0) return GFLA_OK;
-  if (njobs > 2 || !amax_w) return GFLA_ERR_UNSUPPORTED;
+  if (njobs > 2 || !amax_w || k != 3) return GFLA_ERR_UNSUPPORTED;   // (k = 5 runs on the direct kernels: fc_block.hip)
   for (int j = 0; j < njobs; ++j)
     if (!jobs[j].amax_x || !fc_wino16_fits(jobs[j].M, jobs[j].Wv, jobs[j].Wp, k)) return GFLA_ERR_UNSUPPORTED;
   if (njobs == 2 && tuning(21) == 2) {
     const int st = fc_wino16_conv_jobs(jobs, 1, B, nch, k, amax_w, stream);
     return st != GFLA_OK ? st : fc_wino16_conv_jobs(jobs + 1, 1, B, nch, k, amax_w, stream);
   }
-  return k == 5 ? wn16_launch<5>(jobs, njobs, B, nch, amax_w, stream) : wn16_launch<3>(jobs, njobs, B, nch, amax_w, stream);
+  return wn16_launch(jobs, njobs, B, nch, amax_w, stream);
 }
 
 }  // namespace gfla

@@ -116,10 +116,7 @@ class LocalAttnAggregateFunction(Function):
             sfx = _lib.suffix(source, "local_attn_aggregate backward")
             tail = (b, c, hs, ws, h, w, ctx.kernel_size, 1 if ctx.apply_softmax else 0)
             if sfx == "f32" and ns:  # d/d source as a block-sparse product on the matrix cores (csrc/patch_mfma.hip)
-                scratch = _lib.scatter_workspace(source, b, h, w, (ctx.kernel_size + 1) ** 2)
-                _lib.call("gfla_local_attn_aggregate_bwd_ws_f32", source, _lib.ptr(source), _lib.ptr(flow_field),
-                          _lib.ptr(attn), _lib.ptr(grad_out), _lib.ptr(gs), _lib.ptr(gf), _lib.ptr(gl),
-                          _lib.ptr(scratch), *tail)
+                fc_mfma.aggregate_backward_f32(source, flow_field, attn, grad_out, gs, gf, gl, ctx.kernel_size, ctx.apply_softmax)
             else:
                 _lib.call("gfla_local_attn_aggregate_bwd_" + sfx, source, _lib.ptr(source), _lib.ptr(flow_field),
                           _lib.ptr(attn), _lib.ptr(grad_out), _lib.ptr(gs), _lib.ptr(gf), _lib.ptr(gl), *tail)
@@ -386,20 +383,12 @@ class FusedAttnFunction(Function):
         k, mode = int(kernel_size), int(mode)
         fc_mfma._check(source, target, flow, w0, w1, k)
         source, target, flow = source.contiguous(), target.contiguous(), flow.contiguous()
-        w0c, w1c = w0.contiguous(), w1.reshape(k * k, 128).contiguous()
-        b0c = None if b0 is None else b0.contiguous()
-        b1c = None if b1 is None else b1.contiguous()
-        B, C, H, W = source.shape
-        ws = torch.empty(fc_mfma.workspace_bytes(B, C, H, W, k, mode, 0), dtype=torch.uint8, device=source.device)
-        logits = source.new_empty((B, k * k, H, W))
-        _lib.call("gfla_fc_forward_f32", source, _lib.ptr(source), _lib.ptr(target), _lib.ptr(flow), _lib.ptr(w0c),
-                  _lib.ptr(b0c), _lib.ptr(w1c), _lib.ptr(b1c), _lib.ptr(ws), _lib.ptr(logits), B, C, H, W, k,
-                  float(slope), mode)
-        out = source.new_empty((B, C, H, W))
+        logits, ws, w1c = fc_mfma.forward_call(source, target, flow, w0, b0, w1, b1, k, slope, mode)
+        out = torch.empty_like(source)
         attn = torch.empty_like(logits)
         _lib.aggregate_fwd(source, flow, logits, out, attn, k, True)
         ctx.save_for_backward(source, flow, attn, w1c, ws)
-        ctx.dims = (B, C, H, W, k, float(slope), mode)
+        ctx.dims = tuple(source.shape) + (k, float(slope), mode)
         ctx.w_shapes = (w0.shape, w1.shape, b0 is not None, b1 is not None)
         ctx.mark_non_differentiable(attn)
         return out, attn
@@ -407,33 +396,15 @@ class FusedAttnFunction(Function):
     @staticmethod
     def backward(ctx, g_out, _g_attn):
         source, flow, attn, w1c, ws = ctx.saved_tensors
-        B, C, H, W, k, slope, mode = ctx.dims
-        w0_shape, w1_shape, has_b0, has_b1 = ctx.w_shapes
+        B, C, H, W, k = ctx.dims[:5]
         need = ctx.needs_input_grad
-        g_out = g_out.contiguous()
-        dev = source.device
-
-        def out(shape, wanted):
-            return torch.empty(shape, dtype=torch.float32, device=dev) if wanted else None
-
         # the aggregation's own gradients first (d/d logits feeds the FC backward; source / flow are accumulated into by
         # its kernels, so they start at zero), then the FC layers' backward ADDS its source / flow gradients on top
-        g_source, g_flow, g_logits = _zeros_f32(dev, ((B, C, H, W), need[0]), ((B, 2, H, W), need[2]), (attn.shape, True))
-        table = _lib.scatter_workspace(source, B, H, W, (k + 1) ** 2) if need[0] else None
-        _lib.call("gfla_local_attn_aggregate_bwd_ws_f32", source, _lib.ptr(source), _lib.ptr(flow), _lib.ptr(attn),
-                  _lib.ptr(g_out), _lib.ptr(g_source), _lib.ptr(g_flow), _lib.ptr(g_logits), _lib.ptr(table),
-                  B, C, H, W, H, W, k, 1)
-        g_target = out((B, C, H, W), need[1])
-        g_w0 = out(w0_shape, need[3])
-        g_b0 = out((128,), need[4] and has_b0)
-        g_w1 = out(w1_shape, need[5])
-        g_b1 = out((k * k,), need[6] and has_b1)
-        scratch = torch.empty(fc_mfma.workspace_bytes(B, C, H, W, k, mode, 1), dtype=torch.uint8, device=dev)
-        _lib.call("gfla_fc_backward_f32", flow, _lib.ptr(ws), _lib.ptr(flow), _lib.ptr(w1c), _lib.ptr(g_logits),
-                  _lib.ptr(scratch), _lib.ptr(g_source), _lib.ptr(g_target), _lib.ptr(g_flow), _lib.ptr(g_w0),
-                  _lib.ptr(g_b0), _lib.ptr(g_w1), _lib.ptr(g_b1), B, C, H, W, k, slope, mode,
-                  3)  # GFLA_FC_ACCUMULATE_SOURCE | GFLA_FC_ACCUMULATE_FLOW
-        return g_source, g_target, g_flow, g_w0, g_b0, g_w1, g_b1, None, None, None
+        g_source, g_flow, g_logits = _zeros_f32(source.device, ((B, C, H, W), need[0]), ((B, 2, H, W), need[2]),
+                                                (attn.shape, True))
+        fc_mfma.aggregate_backward_f32(source, flow, attn, g_out.contiguous(), g_source, g_flow, g_logits, k)
+        return fc_mfma.backward_call(ws, flow, w1c, g_logits, ctx.dims, ctx.w_shapes, need, flags=3, g_source=g_source,
+                                     g_flow=g_flow) + (None, None, None)
 
 
 def _zeros_f32(dev, *wanted_shapes):
@@ -476,25 +447,16 @@ class FusedAttn16Function(Function):
         if tuple(target.shape) != (B, C, H, W) or tuple(flow.shape) != (B, 2, H, W):
             raise ValueError("ExtractorAttn (%s): source, target and flow must share B, C and H, W" % dt)
         source, flow = source.contiguous(), flow.contiguous()
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()
-        w0c, w1c, b0c, b1c = f32(w0), f32(w1).reshape(k * k, 128), f32(b0), f32(b1)
         mode = 1
-        ws = torch.empty(fc_mfma.workspace_bytes(B, C, H, W, k, mode, 0), dtype=torch.uint8, device=source.device)
-        logits32 = torch.empty((B, k * k, H, W), dtype=torch.float32, device=source.device)
         if dt == torch.float16:
             # the records come straight from the f16 maps; only the 2-channel flow is widened (the sampling tail and the
             # backward read it in float32)
-            t16 = target.detach().contiguous()
             fl32 = _lib.convert_many([flow.detach()], torch.float32)[0]
-            _lib.call("gfla_fc_forward_f16", source, _lib.ptr(source), _lib.ptr(t16), _lib.ptr(fl32), _lib.ptr(w0c),
-                      _lib.ptr(b0c), _lib.ptr(w1c), _lib.ptr(b1c), _lib.ptr(ws), _lib.ptr(logits32), B, C, H, W, k,
-                      float(slope))
+            logits32, ws, w1c = fc_mfma.forward_call(source, target.detach().contiguous(), fl32, w0, b0, w1, b1, k, slope, mode)
         else:
             # (one launch for the three widenings: the call is launch-bound at the face model's batch)
             s32, t32, fl32 = _lib.convert_many([source.detach(), target.detach().contiguous(), flow.detach()], torch.float32)
-            _lib.call("gfla_fc_forward_f32", s32, _lib.ptr(s32), _lib.ptr(t32), _lib.ptr(fl32), _lib.ptr(w0c),
-                      _lib.ptr(b0c), _lib.ptr(w1c), _lib.ptr(b1c), _lib.ptr(ws), _lib.ptr(logits32), B, C, H, W, k,
-                      float(slope), mode)
+            logits32, ws, w1c = fc_mfma.forward_call(s32, t32, fl32, w0, b0, w1, b1, k, slope, mode)
         logits = logits32.to(dt)
         out = torch.empty_like(source)
         attn = torch.empty_like(logits)
@@ -510,12 +472,10 @@ class FusedAttn16Function(Function):
     @staticmethod
     def backward(ctx, g_out, _g_attn):
         source, flow_b, fl32, attn, w1c, ws = ctx.saved_tensors
-        B, C, H, W, k, slope, mode = ctx.dims
+        B, C, H, W, k = ctx.dims[:5]
         w0_shape, w1_shape, has_b0, has_b1, flow_dtype, target_dtype, pdt = ctx.meta
         need = ctx.needs_input_grad
         dev = source.device
-        new32 = lambda shape, wanted: torch.empty(shape, dtype=torch.float32, device=dev) if wanted else None
-        zeros32 = lambda shape, wanted: torch.zeros(shape, dtype=torch.float32, device=dev) if wanted else None
         f32_aggregate = BF16_BACKWARD_F32_AGGREGATE
         if f32_aggregate:
             # The aggregation's backward in float32 on up-cast operands (round 4): its d/d source then runs as the
@@ -524,28 +484,19 @@ class FusedAttn16Function(Function):
             # gradients on top in the same float32 buffers -- one rounding to bf16 at the very end instead of two.
             g_s32, gf32, gl32 = _zeros_f32(dev, ((B, C, H, W), need[0]), ((B, 2, H, W), need[2]), ((B, k * k, H, W), True))
             s32, attn32, go32 = _lib.convert_many([source, attn, g_out.contiguous()], torch.float32)
-            table = _lib.scatter_workspace(s32, B, H, W, (k + 1) ** 2) if need[0] else None
-            _lib.call("gfla_local_attn_aggregate_bwd_ws_f32", s32, _lib.ptr(s32), _lib.ptr(fl32), _lib.ptr(attn32),
-                      _lib.ptr(go32), _lib.ptr(g_s32), _lib.ptr(gf32), _lib.ptr(gl32), _lib.ptr(table), B, C, H, W, H, W, k, 1)
+            fc_mfma.aggregate_backward_f32(s32, fl32, attn32, go32, g_s32, gf32, gl32, k)
             gs = None
         else:
             g_out = g_out.contiguous().to(source.dtype)
             gs = torch.zeros_like(source) if need[0] else None                   # 16-bit, accumulated into
-            gf32 = zeros32((B, 2, H, W), need[2])
+            gf32 = torch.zeros((B, 2, H, W), dtype=torch.float32, device=dev) if need[2] else None
             gl32 = torch.zeros((B, k * k, H, W), dtype=torch.float32, device=dev)
             _lib.call("gfla_local_attn_aggregate_bwd_" + _lib.suffix(source, "ExtractorAttn backward"), source, _lib.ptr(source), _lib.ptr(flow_b), _lib.ptr(attn),
                       _lib.ptr(g_out), _lib.ptr(gs), _lib.ptr(gf32), _lib.ptr(gl32), B, C, H, W, H, W, k, 1)
-            g_s32 = new32((B, C, H, W), need[0])
-        g_t32 = new32((B, C, H, W), need[1])
-        g_w0 = new32(w0_shape, need[3])
-        g_b0 = new32((128,), need[4] and has_b0)
-        g_w1 = new32(w1_shape, need[5])
-        g_b1 = new32((k * k,), need[6] and has_b1)
-        scratch = torch.empty(fc_mfma.workspace_bytes(B, C, H, W, k, mode, 1), dtype=torch.uint8, device=dev)
+            g_s32 = None
         flags = (2 if need[2] else 0) | (1 if (f32_aggregate and need[0]) else 0)   # += grad_flow [| += grad_source]
-        _lib.call("gfla_fc_backward_f32", fl32, _lib.ptr(ws), _lib.ptr(fl32), _lib.ptr(w1c), _lib.ptr(gl32),
-                  _lib.ptr(scratch), _lib.ptr(g_s32), _lib.ptr(g_t32), _lib.ptr(gf32), _lib.ptr(g_w0), _lib.ptr(g_b0),
-                  _lib.ptr(g_w1), _lib.ptr(g_b1), B, C, H, W, k, slope, mode, flags)
+        g_s32, g_t32, gf32, g_w0, g_b0, g_w1, g_b1 = fc_mfma.backward_call(
+            ws, fl32, w1c, gl32, ctx.dims, (w0_shape, w1_shape, has_b0, has_b1), need, flags=flags, g_source=g_s32, g_flow=gf32)
         cast = lambda t, dt: None if t is None else t.to(dt)
         if not need[0]:
             g_source = None
@@ -560,11 +511,6 @@ class FusedAttn16Function(Function):
             g_source, g_target, g_flow = cast(g_source, dt), cast(g_t32, target_dtype), cast(gf32, flow_dtype)
         return (g_source, g_target, g_flow, cast(g_w0, pdt[0]), cast(g_b0, pdt[1]), cast(g_w1, pdt[2]), cast(g_b1, pdt[3]),
                 None, None)
-
-
-# (the names of the bf16-only era)
-FusedAttnBf16Function = FusedAttn16Function
-_bf16_path_ok = _half_path_ok
 
 
 def _fused_attention(self, source, target, flow_field):

@@ -11,7 +11,7 @@ convolution.  `mode` picks the arithmetic of the contraction (include/gfla_hip.h
   0  float32, direct convolution: a k-ordered fma chain per output (what mode 4 falls back to for maps its tiles do not fit);
   5  float32 tensors; every operand of a product as TWO f16 terms (hi + lo = the value to 2^-24 after a power-of-two scaling
      from the tensor's max |x|) on the f16 matrix cores, f32 accumulation -- THE DEFAULT (round 6).  Which kernel runs what is
-     decided per convolution by measurement (csrc/fc_block.hip: fc_hyb): the k = 5 convolutions and every data gradient on the
+     decided per convolution by measurement (csrc/fc_block.hip: fc_plan): the k = 5 convolutions and every data gradient on the
      direct kernels (three cross products, mode 2's arithmetic) reading the float32 maps in place; the k = 3 forward and the
      k = 5 weight gradient in the Winograd domain (all four cross products: csrc/fc_wino16.hip, fc_wino.hip); the k = 3 weight
      gradient is mode 4's kernel.  Same measured error as mode 4, same test bars;
@@ -87,46 +87,76 @@ def _check(source, target, flow, w0, w1, k):
             raise TypeError("fc_mfma: float32 only (got %s)" % t.dtype)
 
 
+def _f32c(t):
+    return None if t is None else t.detach().float().contiguous()
+
+
+def forward_call(source, target, flow, w0, b0, w1, b1, k, slope, mode):
+    """The FC forward on contiguous maps: gfla_fc_forward_f32 in `mode` for float32 source / target, gfla_fc_forward_f16
+    (mode 1: the records packed straight from the maps) for float16 ones; flow float32.  The parameters are taken as float32.
+    Returns (logits (B, k*k, H, W) float32, the workspace, conv1.weight as (k*k, 128)): what backward_call needs."""
+    B, C, H, W = source.shape
+    w0c, w1c, b0c, b1c = _f32c(w0), _f32c(w1).reshape(k * k, 128), _f32c(b0), _f32c(b1)
+    ws = torch.empty(workspace_bytes(B, C, H, W, k, mode, 0), dtype=torch.uint8, device=source.device)
+    logits = torch.empty((B, k * k, H, W), dtype=torch.float32, device=source.device)
+    P = _lib.ptr
+    if source.dtype == torch.float16:
+        assert mode == 1, "gfla_fc_forward_f16 feeds the mode-1 backward"
+        _lib.call("gfla_fc_forward_f16", source, P(source), P(target), P(flow), P(w0c), P(b0c), P(w1c), P(b1c), P(ws), P(logits),
+                  B, C, H, W, k, float(slope))
+    else:
+        _lib.call("gfla_fc_forward_f32", source, P(source), P(target), P(flow), P(w0c), P(b0c), P(w1c), P(b1c), P(ws), P(logits),
+                  B, C, H, W, k, float(slope), mode)
+    return logits, ws, w1c
+
+
+def backward_call(ws, flow, w1c, g_logits, dims, w_shapes, need, flags=0, g_source=None, g_flow=None):
+    """gfla_fc_backward_f32 on the workspace of forward_call.  dims = (B, C, H, W, k, slope, mode); w_shapes = (conv0.weight
+    shape, conv1.weight shape, has conv0.bias, has conv1.bias); need = the needs_input_grad of (source, target, flow, conv0.weight,
+    conv0.bias, conv1.weight, conv1.bias).  g_source / g_flow: float32 buffers the call adds into (flags
+    GFLA_FC_ACCUMULATE_SOURCE = 1 / GFLA_FC_ACCUMULATE_FLOW = 2); otherwise every wanted gradient gets a fresh float32 tensor.
+    Returns (g_source, g_target, g_flow, g_w0, g_b0, g_w1, g_b1)."""
+    B, C, H, W, k, slope, mode = dims
+    w0_shape, w1_shape, has_b0, has_b1 = w_shapes
+    dev = flow.device
+    g_logits = g_logits.contiguous()
+
+    def new(shape, wanted):
+        return torch.empty(shape, dtype=torch.float32, device=dev) if wanted else None
+
+    g = (new((B, C, H, W), need[0]) if g_source is None else g_source, new((B, C, H, W), need[1]),
+         new((B, 2, H, W), need[2]) if g_flow is None else g_flow, new(w0_shape, need[3]), new((128,), need[4] and has_b0),
+         new(w1_shape, need[5]), new((k * k,), need[6] and has_b1))
+    scratch = torch.empty(workspace_bytes(B, C, H, W, k, mode, 1), dtype=torch.uint8, device=dev)
+    _lib.call("gfla_fc_backward_f32", flow, _lib.ptr(ws), _lib.ptr(flow), _lib.ptr(w1c), _lib.ptr(g_logits),
+              _lib.ptr(scratch), *[_lib.ptr(t) for t in g], B, C, H, W, k, slope, mode, flags)
+    return g
+
+
+def aggregate_backward_f32(source, flow, attn, g_out, g_source, g_flow, g_logits, k, apply_softmax=True):
+    """gfla_local_attn_aggregate_bwd_ws_f32 on float32 operands: ADDS d/d source (the block-sparse product on the matrix
+    cores, through its scatter table) and d/d flow into g_source / g_flow and writes d/d logits; None = not wanted."""
+    b, c, hs, ws = source.shape
+    h, w = flow.shape[2:]
+    table = _lib.scatter_workspace(source, b, h, w, (k + 1) ** 2) if g_source is not None else None
+    _lib.call("gfla_local_attn_aggregate_bwd_ws_f32", source, _lib.ptr(source), _lib.ptr(flow), _lib.ptr(attn), _lib.ptr(g_out),
+              _lib.ptr(g_source), _lib.ptr(g_flow), _lib.ptr(g_logits), _lib.ptr(table), b, c, hs, ws, h, w, k,
+              1 if apply_softmax else 0)
+
+
 class FcMfmaFunction(Function):
     @staticmethod
     def forward(ctx, source, target, flow, w0, b0, w1, b1, kernel_size, slope, mode):
         k, mode = int(kernel_size), int(mode)
         _check(source, target, flow, w0, w1, k)
         source, target, flow = source.contiguous(), target.contiguous(), flow.contiguous()
-        w0c, w1c = w0.contiguous(), w1.reshape(k * k, 128).contiguous()
-        b0c = None if b0 is None else b0.contiguous()
-        b1c = None if b1 is None else b1.contiguous()
-        B, C, H, W = source.shape
-        ws = torch.empty(workspace_bytes(B, C, H, W, k, mode, 0), dtype=torch.uint8, device=source.device)
-        logits = source.new_empty((B, k * k, H, W))
-        _lib.call("gfla_fc_forward_f32", source, _lib.ptr(source), _lib.ptr(target), _lib.ptr(flow), _lib.ptr(w0c),
-                  _lib.ptr(b0c), _lib.ptr(w1c), _lib.ptr(b1c), _lib.ptr(ws), _lib.ptr(logits), B, C, H, W, k,
-                  float(slope), mode)
+        logits, ws, w1c = forward_call(source, target, flow, w0, b0, w1, b1, k, slope, mode)
         ctx.save_for_backward(flow, w1c, ws)
-        ctx.dims = (B, C, H, W, k, float(slope), mode)
+        ctx.dims = tuple(source.shape) + (k, float(slope), mode)
         ctx.w_shapes = (w0.shape, w1.shape, b0 is not None, b1 is not None)
         return logits
 
     @staticmethod
     def backward(ctx, g_logits):
         flow, w1c, ws = ctx.saved_tensors
-        B, C, H, W, k, slope, mode = ctx.dims
-        w0_shape, w1_shape, has_b0, has_b1 = ctx.w_shapes
-        need = ctx.needs_input_grad
-        g_logits = g_logits.contiguous()
-        dev = flow.device
-
-        def out(shape, wanted):
-            return torch.empty(shape, dtype=torch.float32, device=dev) if wanted else None
-
-        g_source, g_target = out((B, C, H, W), need[0]), out((B, C, H, W), need[1])
-        g_flow = out((B, 2, H, W), need[2])
-        g_w0 = out(w0_shape, need[3])
-        g_b0 = out((128,), need[4] and has_b0)
-        g_w1 = out(w1_shape, need[5])
-        g_b1 = out((k * k,), need[6] and has_b1)
-        scratch = torch.empty(workspace_bytes(B, C, H, W, k, mode, 1), dtype=torch.uint8, device=dev)
-        _lib.call("gfla_fc_backward_f32", flow, _lib.ptr(ws), _lib.ptr(flow), _lib.ptr(w1c), _lib.ptr(g_logits),
-                  _lib.ptr(scratch), _lib.ptr(g_source), _lib.ptr(g_target), _lib.ptr(g_flow), _lib.ptr(g_w0),
-                  _lib.ptr(g_b0), _lib.ptr(g_w1), _lib.ptr(g_b1), B, C, H, W, k, slope, mode, 0)
-        return g_source, g_target, g_flow, g_w0, g_b0, g_w1, g_b1, None, None, None
+        return backward_call(ws, flow, w1c, g_logits, ctx.dims, ctx.w_shapes, ctx.needs_input_grad) + (None, None, None)

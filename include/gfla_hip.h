@@ -77,7 +77,10 @@ const char *gfla_status_string(int status);
  *   key 6: resample2d fwd/bwd        0 auto, 1 force global kernels
  *   key 7: row windows for planes larger than the LDS budget   0 on, 1 off (use global kernels)
  *   key 10: LDS budget per workgroup in KB (0 = 64; up to 160)
- *   key 19: FC weight gradient in arithmetic mode 4   0 auto (Winograd domain), 1 direct, 3 Winograd for k = 5 only (round 3)
+ *   keys 19, 43, 49, 52: retired -- accepted and ignored.  They selected FC kernels that later rounds measured and replaced
+ *           (the direct weight gradient in mode 4; in mode 5 the two-term f16 Winograd kernels for the k = 3 data gradient and
+ *           for every convolution, the float32 k = 5 weight gradient).  The FC kernel plan is a function of the call's
+ *           shape and mode alone (csrc/fc_block.hip: fc_plan)
  *   key 20: timing ablations of the Winograd kernels -- only in `make PROBES=1` builds (results are garbage;
  *           tools/probe_wino.py); a default build ignores the key
  *   key 21: Winograd convolutions   1 single raw buffer, 2 one launch per half instead of both halves in one (also
@@ -96,14 +99,8 @@ const char *gfla_status_string(int status);
  *           ignores the key
  *   key 40: channels per pixel chunk of block_extractor's forward tiles (0 auto)
  *   key 41: 1 = block_extractor's backward tiles without the cross-lane fold of the patch rows (csrc/be_tile.h: BeLinks)
- *   key 43: arithmetic mode 5: 1 = the two-term f16 kernel also for the k = 3 data gradient (default: float32 Winograd kernel there)
  *   key 46: 1 = gfla_fc_backward_f32 scatters the gradient of the convolved source map with global float atomics (round 2)
  *           instead of the owner-computes kernel of round 6 (csrc/fc_sample.hip: fc_scatter_own_kernel)
- *   key 49: arithmetic mode 5: 1 = the k = 5 weight gradient on the float32 Winograd kernel (rounds 3-5) instead of the
- *           two-term f16 kernel (csrc/fc_wino.hip: fc_wino16_wgrad_kernel)
- *   key 52: arithmetic mode 5: 1 = Winograd-domain kernels for every convolution (the first half of round 6) instead of the
- *           hybrid dispatch (direct f16x2 kernels fed from the float32 maps for the k = 5 convolutions and all data gradients:
- *           csrc/fc_block.hip: fc_hyb, csrc/fc_conv_impl.h: SRC32)
  *   key 38: 1 = the first version of the gathers (taps read from global memory, no LDS window); key 33 = its channels per wave
  * (the other keys select experiments of individual kernels; see the tuning(...) calls in csrc/)                  */
 int gfla_set_tuning(int key, int value);

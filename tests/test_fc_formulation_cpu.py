@@ -121,3 +121,64 @@ def test_geometry_has_the_slack_the_kernels_read():
             assert g["Sz"] >= g["Md"] + 256 + halo      # the transposed convolution's last input tile
             assert g["Sz"] >= g["lead"] + (g["M"] + 63) // 64 * 64   # the weight gradient's last K step
             assert g["Ho"] == (H + k - 1 if src else H) and g["Wo"] == (W + k - 1 if src else W)
+
+
+def _wn16_fits_before(M, Wv, Wp, k):
+    """fc_wino16_fits (csrc/fc_wino16.hip with fc_wino_fits and the geometry of csrc/fc_wino_shared.h, tuning key 44 at its
+    default): the LDS of the Winograd-domain kernels at this shape, transcribed."""
+    if Wv <= 0 or Wv > Wp or M <= 0 or M % Wv:
+        return False
+    m, pitch = (2, 80) if k == 5 else (4, 72)
+    TH, TW = -(-(M // Wv) // m), -(-Wv // m)
+    ntiles = TH * TW
+
+    def span(tpg):
+        exact = 0
+        for grp in range(-(-ntiles // tpg)):
+            t0 = grp * tpg
+            t1 = min(t0 + tpg, ntiles) - 1
+            r0, r1 = t0 // TW, t1 // TW
+            for r in range(max(r0, r1 - 1), r1 + 1):
+                c = t1 - r1 * TW if r == r1 else TW - 1
+                exact = max(exact, (m * r + 5) * Wp + m * c + 5 + 1 - m * r0 * Wp)
+        return exact
+
+    sp = span(32)
+    whole = (32 // TW) * TW if TW < 32 else 32
+    if whole != 32 and whole >= 28 and -(-ntiles // whole) == -(-ntiles // 32):
+        sp = min(sp, span(whole))
+    raw = (sp * pitch + 15) & ~15
+    main = 2 * 36 * 32 * 8 * 4 + raw
+    return (max(main, 512 * 4 * m * m * 4) <= 160 * 1024 and
+            max(main, 3 * 2 * 4 * m * m * 64 * 4 * (4 if m == 2 else 1)) <= 160 * 1024)
+
+
+def _mode5_supported_before(C, H, W, k):
+    """gfla_fc_supported(.., mode 5) before the direct-kernel fit became an explicit condition: the Winograd-domain fits of
+    both halves' forward and data-gradient convolutions, and the row-buffer cap on W."""
+    if C > 4096 or H > 2048 or W > 2048:
+        return False
+    for src in (True, False):
+        lo = k // 2
+        pt, pb = (k - 1, k - 1) if src else (lo, k - 1 - lo)
+        Hp, Wp = H + pt + pb, W + pt + pb
+        Ho, Wo = Hp - k + 1, Wp - k + 1
+        if not (_wn16_fits_before(Ho * Wo, Wo, Wp, k) and _wn16_fits_before(Hp * Wp, Wp, Wp, k)):
+            return False
+    return 64 * (W + 1) * 4 <= 64 * 1024
+
+
+def test_mode5_direct_kernels_fit_wherever_mode5_was_supported():
+    """Mode 5 runs the k = 5 convolutions and every data gradient on the direct f16x2 kernels and has no Winograd-domain
+    fallback for them: fc_args_ok requires their fit explicitly.  That condition must change no answer of gfla_fc_supported:
+    the W cap (64 (W + 1) 4 <= 64 KB) keeps every direct tile within the LDS."""
+    from global_flow_local_attention_amd import fc_mfma
+    checked = 0
+    for k in (3, 5):
+        for W in range(1, 256):
+            for H in (1, 2, 3, 7, 13, 22, 32, 44, 64, 100, 200):
+                want = _mode5_supported_before(1, H, W, k)
+                for C in (1, 8, 128, 4096, 4097):
+                    assert fc_mfma.supported(C, H, W, k, 5) == (want and C <= 4096), (C, H, W, k)
+                    checked += 1
+    assert checked == 2 * 255 * 11 * 5

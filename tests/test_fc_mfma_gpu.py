@@ -266,7 +266,7 @@ def test_vendor_fallback_policy(gfla):
 # ------------------------------------------------------------------------------- bf16 features (BASELINE config 5)
 @pytest.mark.parametrize("k,C,H,W", [(3, 16, 12, 10), (5, 8, 11, 9)])
 def test_extractor_attn_bf16_features(lib, gfla, oracle, k, C, H, W):
-    """bf16 source / target / flow through ExtractorAttn (FusedAttnBf16Function: FC layers in arithmetic mode 1 --
+    """bf16 source / target / flow through ExtractorAttn (FusedAttn16Function: FC layers in arithmetic mode 1 --
     one f16 term per operand, exact for bf16 values -- aggregation in the _bf16 kernels) against the CPU oracle of the
     whole block evaluated in float32 on the bf16-rounded inputs: forward and feature-map gradients within 2^-6 of the largest
     entry, parameter gradients within 2^-5 (the logits are rounded to bf16 once before the softmax, as in any bf16 pipeline)."""
@@ -425,33 +425,31 @@ def test_owner_computes_scatter_non_finite_gradient(lib, gfla):
 @pytest.mark.parametrize("C,H,W", [(16, 64, 44), (24, 20, 26), (8, 9, 14), (16, 40, 66), (128, 64, 44)])
 def test_two_term_f16_weight_gradient_equals_float32(lib, gfla, C, H, W):
     """fc_wino16_wgrad_kernel (mode 5, k = 5: both operands of the Winograd-domain products as two f16 terms on
-    v_mfma_f32_16x16x32_f16) against the float32 kernel it replaces (tuning key 49 = 1) through the whole backward, one-row and
-    multi-row units, and against float64 where the host can afford it (test_fc_function_against_float64 runs in mode 5 too)."""
+    v_mfma_f32_16x16x32_f16) against the float32 kernel it replaces (mode 4's) through the whole backward, one-row and
+    multi-row units, and against float64 where the host can afford it (test_fc_function_against_float64 runs in mode 5 too).
+    The two modes' forwards differ in rounding, so a hidden activation within rounding of LeakyReLU's kink would take different
+    slopes on the two sides (seen at C 128, 64x44: 6.5e-3): conv0.bias is +-8 on even / odd channels, as in bench.py, which
+    keeps every pre-activation clear of 0 and both slopes in use."""
     B, k = 2, 5
     s, t = randn((B, C, H, W), seed=81).to(DEV), randn((B, C, H, W), seed=82).to(DEV)
     f = make_flow("smooth", B, H, W, seed=83).to(DEV)
     w0 = (randn((128, 2 * C, k, k), seed=84) / (2 * C * k * k) ** 0.5).to(DEV)
-    b0, b1 = (randn((128,), seed=85) * 0.1).to(DEV), (randn((k * k,), seed=87) * 0.1).to(DEV)
+    b0 = (torch.where(torch.arange(128) % 2 == 0, 8.0, -8.0) + randn((128,), seed=85) * 0.1).to(DEV)
+    b1 = (randn((k * k,), seed=87) * 0.1).to(DEV)
     w1 = (randn((k * k, 128, 1, 1), seed=86) / 128 ** 0.5).to(DEV)
     up = randn((B, k * k, H, W), seed=88).to(DEV)
     f16 = _fc_backward_raw(lib, 5, s, t, f, w0, b0, w1, b1, up, k)
-    old = gfla.set_tuning(49, 1)
-    try:
-        f32 = _fc_backward_raw(lib, 5, s, t, f, w0, b0, w1, b1, up, k)
-    finally:
-        gfla.set_tuning(49, old)
+    f32 = _fc_backward_raw(lib, 4, s, t, f, w0, b0, w1, b1, up, k)
     e = rel_err(f16[4].cpu(), f32[4].cpu())
     print("C %d %dx%d: f16 vs f32 weight gradient %.2e" % (C, H, W, e))
     assert torch.isfinite(f16[4]).all() and e <= 1e-5, e
-    for a, b_ in zip(f16[:4] + f16[5:], f32[:4] + f32[5:]):
-        assert torch.equal(a, b_)   # nothing else changes
 
 
 @pytest.mark.parametrize("k,C,H,W", [(5, 16, 40, 28), (3, 24, 33, 17), (5, 128, 64, 44)])
 def test_mode5_hybrid_dispatch_equals_the_winograd_form(lib, gfla, k, C, H, W):
-    """Mode 5's default dispatch (direct f16x2 kernels reading the float32 maps in place for the k = 5 convolutions and every data
-    gradient: fc_conv_kernel<..., SRC32>) against the all-Winograd form of the first half of round 6 (tuning key 52 = 1) through
-    the whole layer: two float32-grade evaluations of the same sums, a few 1e-6 of the largest entry apart."""
+    """Mode 5's dispatch (direct f16x2 kernels reading the float32 maps in place for the k = 5 convolutions and every data
+    gradient: fc_conv_kernel<..., SRC32>) against mode 4 (float32, Winograd domain throughout) through the whole layer: two
+    float32-grade evaluations of the same sums, a few 1e-6 of the largest entry apart."""
     B = 2
     s, t = randn((B, C, H, W), seed=91).to(DEV), randn((B, C, H, W), seed=92).to(DEV)
     f = make_flow("smooth", B, H, W, seed=93).to(DEV)
@@ -460,11 +458,7 @@ def test_mode5_hybrid_dispatch_equals_the_winograd_form(lib, gfla, k, C, H, W):
     w1 = (randn((k * k, 128, 1, 1), seed=96) / 128 ** 0.5).to(DEV)
     up = randn((B, k * k, H, W), seed=98).to(DEV)
     hyb = _fc_backward_raw(lib, 5, s, t, f, w0, b0, w1, b1, up, k)
-    old = gfla.set_tuning(52, 1)
-    try:
-        wino = _fc_backward_raw(lib, 5, s, t, f, w0, b0, w1, b1, up, k)
-    finally:
-        gfla.set_tuning(52, old)
+    wino = _fc_backward_raw(lib, 4, s, t, f, w0, b0, w1, b1, up, k)
     names = ("logits", "source", "target", "flow", "w0", "b0", "w1", "b1")
     for n_, a, b_ in zip(names, hyb, wino):
         e = rel_err(a.cpu(), b_.cpu())

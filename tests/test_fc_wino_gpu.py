@@ -59,21 +59,22 @@ SWEEP = [  # (k, B, C, H, W): ragged / tiny / odd / wide
 @pytest.mark.parametrize("is_source", [0, 1])
 @pytest.mark.parametrize("wmode", [4, 5, 52, 50])
 def test_winograd_half_on_ragged_shapes(gfla, k, B, C, H, W, is_source, wmode):
-    """wmode 5 = the default dispatch of mode 5 (later in round 6: the direct f16x2 kernels fed from the float32 maps for the
-    k = 5 convolutions and every data gradient, Winograd domain for the k = 3 forward and the weight gradients); 52 = mode 5
-    with Winograd-domain kernels for every convolution (tuning key 52 = 1: the first half of round 6); 50 = that with the
-    two-term f16 kernel forced for the k = 3 data gradient as well (key 43 = 1; the float32 Winograd kernel otherwise)."""
-    from global_flow_local_attention_amd import fc_mfma
-    force16, all_wino = wmode == 50, wmode in (50, 52)
-    wmode = 5 if all_wino else wmode
-    if force16 and k != 3:
-        pytest.skip("key 43 only changes k = 3")
-    old43, old52 = gfla.set_tuning(43, 1 if force16 else 0), gfla.set_tuning(52, 1 if all_wino else 0)
-    try:
+    """wmode 5 = the dispatch of mode 5 (the direct f16x2 kernels fed from the float32 maps for the k = 5 convolutions and
+    every data gradient, Winograd domain for the k = 3 forward and the weight gradients).  52 / 50 = mode 5 with the retired
+    tuning keys set: 52 = 1 (once all-Winograd convolutions), 50 = that and 19, 43, 49 = 1 as well.  The keys must change
+    nothing (the kernel plan is a function of the shape and mode alone): same float64 bars, and bit-equal to wmode 5."""
+    if wmode == 4 or wmode == 5:
         _ragged(gfla, k, B, C, H, W, is_source, wmode)
+        return
+    old = {key: gfla.set_tuning(key, 1) for key in ((52,) if wmode == 52 else (19, 43, 49, 52))}
+    try:
+        got = _ragged(gfla, k, B, C, H, W, is_source, 5)
     finally:
-        gfla.set_tuning(43, old43)
-        gfla.set_tuning(52, old52)
+        for key, value in old.items():
+            gfla.set_tuning(key, value)
+    want = _ragged(gfla, k, B, C, H, W, is_source, 5)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
 
 
 def _ragged(gfla, k, B, C, H, W, is_source, wmode):
@@ -97,6 +98,7 @@ def _ragged(gfla, k, B, C, H, W, is_source, wmode):
     assert e_f <= FWD_TOL and e_x <= GRAD_TOL and e_w <= GRAD_TOL, (e_f, e_x, e_w)
     other = gw[:, :C] if is_source else gw[:, C:]
     assert float(other.abs().max()) == 0.0
+    return fwd, gx, gw
 
 
 def test_mode4_falls_back_to_the_direct_kernels_where_its_tiles_do_not_fit(gfla):
@@ -230,9 +232,8 @@ WGRAD_SWEEP = SWEEP + [(3, 4, 32, 32, 22), (3, 2, 24, 12, 30), (5, 2, 16, 20, 26
 @pytest.mark.parametrize("is_source", [0, 1])
 @pytest.mark.parametrize("form", ["winograd", "winograd_units_of_16_tiles", "winograd_single_row_units"])
 def test_winograd_domain_weight_gradient_forms(gfla, k, B, C, H, W, is_source, form):
-    """The Winograd-domain weight gradient forced for every k (tuning key 19 = 2; the default takes it for k = 5 and wherever
-    multi-row units apply) with units of whole tile rows on narrow maps (the default: up to 32 tiles; key 29 = 2: up to 16)
-    and with round 3's single-row units (key 29 = 1), against float64 on the host."""
+    """The Winograd-domain weight gradient (mode 4, every k) with units of whole tile rows on narrow maps (the default: up
+    to 32 tiles; key 29 = 2: up to 16) and with round 3's single-row units (key 29 = 1), against float64 on the host."""
     from global_flow_local_attention_amd import fc_mfma
     if fc_mfma.resolve_mode(C, H, W, k, 4) != 4:
         pytest.skip("shape falls back to the direct kernels")
@@ -240,12 +241,11 @@ def test_winograd_domain_weight_gradient_forms(gfla, k, B, C, H, W, is_source, f
     w0 = (randn((128, 2 * C, k, k), seed=6) * 0.05).to(DEV)
     g = fc_mfma.geometry(H, W, k, is_source)
     dG = (randn((B, 128, g["Ho"], g["Wo"]), seed=7) * 1e-3).to(DEV)
-    old19, old29 = gfla.set_tuning(19, 2), gfla.set_tuning(29, {"winograd": 0, "winograd_units_of_16_tiles": 2, "winograd_single_row_units": 1}[form])
+    old29 = gfla.set_tuning(29, {"winograd": 0, "winograd_units_of_16_tiles": 2, "winograd_single_row_units": 1}[form])
     try:
         _, _, gw, _ = _run_half(B, C, H, W, k, is_source, 4, x, w0, dG)
         torch.cuda.synchronize()
     finally:
-        gfla.set_tuning(19, old19)
         gfla.set_tuning(29, old29)
     x64 = x.cpu().double()
     wh = (w0[:, C:] if is_source else w0[:, :C]).cpu().double().clone().requires_grad_()
