@@ -34,6 +34,8 @@ _SIGNATURES = {
 # entry points that exist in one precision only: full symbol name -> argument types
 _SINGLE = {
     "gfla_max_cosine_fwd_f32": [_ptr] * 5 + [_i64] * 4 + [ctypes.c_double, _ptr],
+    "gfla_max_cosine_fwd_f16": [_ptr] * 5 + [_i64] * 4 + [ctypes.c_double, _ptr],
+    "gfla_max_cosine_fwd_bf16": [_ptr] * 5 + [_i64] * 4 + [ctypes.c_double, _ptr],
     "gfla_max_cosine_workspace_bytes": [_i64] * 3,
     "gfla_fc_tail_fwd_f32": [_ptr, _i64, _i64] + [_ptr] * 5 + [_i64] * 3 + [_int, ctypes.c_double, _ptr],
     "gfla_fc_tail_fwd_f64": [_ptr, _i64, _i64] + [_ptr] * 5 + [_i64] * 3 + [_int, ctypes.c_double, _ptr],
@@ -43,6 +45,10 @@ _SINGLE = {
     "gfla_replicate_pad_bwd_f64": [_ptr] * 2 + [_i64] * 3 + [_int] * 4 + [_ptr],
     "gfla_correctness_map_fwd_f32": [_ptr] * 5 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
     "gfla_correctness_map_bwd_f32": [_ptr] * 9 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
+    "gfla_correctness_map_fwd_f16": [_ptr] * 5 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
+    "gfla_correctness_map_bwd_f16": [_ptr] * 9 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
+    "gfla_correctness_map_fwd_bf16": [_ptr] * 5 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
+    "gfla_correctness_map_bwd_bf16": [_ptr] * 9 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
     "gfla_fc_supported": [_i64] * 3 + [_int, _int],
     "gfla_fc_workspace_bytes": [_i64] * 4 + [_int] * 3,
     "gfla_fc_forward_f32": [_ptr] * 9 + [_i64] * 4 + [_int, ctypes.c_double, _int, _ptr],

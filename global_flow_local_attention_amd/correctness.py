@@ -8,8 +8,9 @@ Reference: `PerceptualCorrectness` (model/networks/external_function.py:223-319)
      similarity with the target features at the same position, and
   3. averages exp(-sample / (best + eps)), optionally under a mask (:270-277).
 
-Step 1 is `max_cosine_similarity` below: one fp32 MFMA kernel in libgfla_hip.so that keeps the
-similarity matrix in registers (gfla_max_cosine_fwd_f32).  Step 2 uses this package's Resample2d.
+Step 1 is `max_cosine_similarity` below: one MFMA kernel in libgfla_hip.so that keeps the
+similarity matrix in registers (gfla_max_cosine_fwd_f32; float16 / bfloat16 features run on the 16-bit
+matrix cores, gfla_max_cosine_fwd_f16 / _bf16).  Step 2 uses this package's Resample2d.
 """
 import torch
 import torch.nn as nn
@@ -26,23 +27,28 @@ class MaxCosineFunction(Function):
     best[b,j] = max_i <source[b,:,i]/(|.|+eps), target[b,:,j]/(|.|+eps)>  (external_function.py:260-268).
     Backward re-evaluates the winning pairs only (B*C*Nt work): the max routes the gradient to one source
     position per target position, exactly as torch.max(dim=1) does in the reference.
+
+    float32, or float16 / bfloat16 with source and target of one dtype.  For 16-bit features `best` is float32 (it
+    divides a loss term; the kernel accumulates in float32 and nothing is gained by rounding it), the backward is
+    evaluated in float32 and the gradients are returned in the features' dtype.
     """
 
     @staticmethod
     def forward(ctx, source, target, eps):
         _lib.require_gpu(source, target)
-        if source.dtype != torch.float32 or target.dtype != torch.float32:
-            raise TypeError("max_cosine_similarity: float32 features only (got %s, %s)" % (source.dtype, target.dtype))
+        if source.dtype != target.dtype or source.dtype not in (torch.float32,) + _lib.HALF_TYPES:
+            raise TypeError("max_cosine_similarity: float32, float16 or bfloat16 features, source and target of one dtype "
+                            "(got %s, %s)" % (source.dtype, target.dtype))
         assert source.is_contiguous() and target.is_contiguous()
         assert source.dim() == 3 and target.dim() == 3
         B, C, Ns = source.shape
         assert target.size(0) == B and target.size(1) == C
         Nt = target.size(2)
-        best = source.new_empty(B, Nt)
+        best = torch.empty(B, Nt, dtype=torch.float32, device=source.device)
         index = torch.empty(B, Nt, dtype=torch.int32, device=source.device)
         scratch = torch.empty(_lib.lib().gfla_max_cosine_workspace_bytes(B, Ns, Nt), dtype=torch.uint8,
                               device=source.device)
-        _lib.call("gfla_max_cosine_fwd_f32", source, _lib.ptr(source), _lib.ptr(target), _lib.ptr(scratch),
+        _lib.call("gfla_max_cosine_fwd_" + _lib.suffix(source, "max_cosine_similarity"), source, _lib.ptr(source), _lib.ptr(target), _lib.ptr(scratch),
                   _lib.ptr(best), _lib.ptr(index), B, C, Ns, Nt, float(eps))
         ctx.eps = eps
         ctx.save_for_backward(source, target, index)
@@ -55,36 +61,55 @@ class MaxCosineFunction(Function):
         need_s, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_s or need_t):
             return None, None, None
+        half = source.dtype in _lib.HALF_TYPES
         with torch.enable_grad():
-            s = source.detach().requires_grad_(need_s)
-            t = target.detach().requires_grad_(need_t)
-            winners = torch.gather(s, 2, index.long().unsqueeze(1).expand(-1, s.size(1), -1))
+            s = source.detach().requires_grad_(need_s and not half)
+            t = target.detach().requires_grad_(need_t and not half)
+            gather_at = index.long().unsqueeze(1).expand(-1, s.size(1), -1)
+            winners = torch.gather(s, 2, gather_at)
+            if half:
+                # the winners are gathered in the storage type (no float32 copy of the source map); from there on
+                # float32, with the winners and the target as the leaves
+                winners, t = winners.float().requires_grad_(need_s), t.float().requires_grad_(need_t)
+                leaf_s = winners
+            else:
+                leaf_s = s
             winners = winners / (winners.norm(dim=1, keepdim=True) + ctx.eps)
             t_unit = t / (t.norm(dim=1, keepdim=True) + ctx.eps)
             best = (winners * t_unit).sum(1)
-            wanted = [x for x, need in ((s, need_s), (t, need_t)) if need]
-            grads = list(torch.autograd.grad(best, wanted, grad_best))
+            wanted = [x for x, need in ((leaf_s, need_s), (t, need_t)) if need]
+            grads = list(torch.autograd.grad(best, wanted, grad_best.float() if half else grad_best))
+        if half:
+            if need_s:   # route the winners' gradients to their source positions: float32 sums, one rounding at the end
+                g_src = torch.zeros(source.shape, dtype=torch.float32, device=source.device)
+                grads[0] = g_src.scatter_add_(2, gather_at, grads[0])
+            grads = [g.to(source.dtype) for g in grads]
         return (grads.pop(0) if need_s else None), (grads.pop(0) if need_t else None), None
 
 
 class CorrectnessMapFunction(Function):
     """(warped (B,C,N), target (B,C,N), best (B,N), eps) -> exp(-cosine_similarity(warped, target) / (best + eps)),
-    external_function.py:275-276, as one pass forward and one backward."""
+    external_function.py:275-276, as one pass forward and one backward.
+
+    All float32, or a float32 `warped` with a float16 / bfloat16 `target`: the target is read in its storage type, the
+    loss map and the gradients of `warped` and `best` are float32, the gradient of `target` is returned in its dtype."""
 
     COS_EPS = 1e-8  # F.cosine_similarity's default
 
     @staticmethod
     def forward(ctx, warped, target, best, eps):
         _lib.require_gpu(warped, target, best)
+        if warped.dtype != torch.float32 or best.dtype != torch.float32 or \
+                target.dtype not in (torch.float32,) + _lib.HALF_TYPES:
+            raise TypeError("correctness map: float32 warped and best, float32 / float16 / bfloat16 target (got %s, %s, %s)"
+                            % (warped.dtype, target.dtype, best.dtype))
         for x in (warped, target, best):
-            if x.dtype != torch.float32:
-                raise TypeError("correctness map: float32 only (got %s)" % x.dtype)
             assert x.is_contiguous()
         B, C, N = warped.shape
         assert target.shape == warped.shape and best.shape == (B, N)
         loss_map = warped.new_empty(B, N)
         stats = warped.new_empty(B, N, 3)
-        _lib.call("gfla_correctness_map_fwd_f32", warped, _lib.ptr(warped), _lib.ptr(target), _lib.ptr(best),
+        _lib.call("gfla_correctness_map_fwd_" + _lib.suffix(target, "correctness map"), warped, _lib.ptr(warped), _lib.ptr(target), _lib.ptr(best),
                   _lib.ptr(loss_map), _lib.ptr(stats), B, C, N, CorrectnessMapFunction.COS_EPS, float(eps))
         ctx.eps = eps
         ctx.save_for_backward(warped, target, best, stats, loss_map)
@@ -99,7 +124,7 @@ class CorrectnessMapFunction(Function):
         g_target = torch.empty_like(target) if need[1] else None
         g_best = torch.empty_like(best) if need[2] else None
         if any(need[:3]):
-            _lib.call("gfla_correctness_map_bwd_f32", warped, _lib.ptr(warped), _lib.ptr(target), _lib.ptr(best),
+            _lib.call("gfla_correctness_map_bwd_" + _lib.suffix(target, "correctness map"), warped, _lib.ptr(warped), _lib.ptr(target), _lib.ptr(best),
                       _lib.ptr(stats), _lib.ptr(loss_map), _lib.ptr(grad_map.contiguous()), _lib.ptr(g_warped),
                       _lib.ptr(g_target), _lib.ptr(g_best), B, C, N, CorrectnessMapFunction.COS_EPS, float(ctx.eps))
         return g_warped, g_target, g_best, None
@@ -124,9 +149,19 @@ class PerceptualCorrectness(nn.Module):
     its weights are part of this package.  `calculate_loss` works on `self.target_vgg` /
     `self.source_vgg` exactly as the reference's does, so it can also be driven with precomputed
     features.
+
+    `half_features`: what `calculate_loss` does with float16 / bfloat16 features (torch.autocast).  "float32" (default):
+    features, flow and mask are up-cast and the float32 kernels run.  "native": the best match runs on the 16-bit
+    features as they are (16-bit matrix cores) and the target map is never up-cast; only the source map is, once, for the
+    warp, which stays in float32 with the float32 flow (a 16-bit flow of 32-64 px has steps of 0.25-0.5 px in bfloat16).
+    The loss map, the mask arithmetic and the returned loss are float32 either way.  "native" covers the path the trainer
+    uses (Resample2d warp, fused loss map, source and target of one 16-bit dtype); `use_bilinear_sampling`, `fused = False`
+    and mixed feature dtypes are evaluated as under "float32".
     """
 
-    def __init__(self, layer=['rel1_1', 'relu2_1', 'relu3_1', 'relu4_1'], vgg=None):
+    HALF_FEATURES = ("float32", "native")
+
+    def __init__(self, layer=['rel1_1', 'relu2_1', 'relu3_1', 'relu4_1'], vgg=None, half_features="float32"):
         super(PerceptualCorrectness, self).__init__()
         if isinstance(vgg, nn.Module):
             self.add_module('vgg', vgg)
@@ -139,6 +174,9 @@ class PerceptualCorrectness(nn.Module):
         # whose grid_sample had no align_corners argument and behaved as align_corners=True
         self.align_corners = True
         self.fused = True   # False: cosine_similarity / exp through torch ops, as the reference writes them
+        if half_features not in self.HALF_FEATURES:
+            raise ValueError("half_features: one of %s (got %r)" % (self.HALF_FEATURES, half_features))
+        self.half_features = half_features
 
     def __call__(self, target, source, flow_list, used_layers, mask=None, use_bilinear_sampling=False):
         if self.vgg is None:
@@ -159,6 +197,10 @@ class PerceptualCorrectness(nn.Module):
             # 16-bit features (torch.autocast): the loss is evaluated in float32 on the library's own kernels (max_cosine,
             # resample2d, the fused correctness map) and returned in float32, as autocast returns losses
             with torch.autocast(device_type=target_feat.device.type, enabled=False):
+                if self.half_features == "native" and target_feat.dtype in half and \
+                        source_feat.dtype == target_feat.dtype and not use_bilinear_sampling and self.fused:
+                    return self._loss(flow.float(), target_feat, source_feat, None if mask is None else mask.float(),
+                                      use_bilinear_sampling)
                 return self._loss(flow.float(), target_feat.float(), source_feat.float(),
                                   None if mask is None else mask.float(), use_bilinear_sampling)
         return self._loss(flow, target_feat, source_feat, mask, use_bilinear_sampling)
@@ -171,6 +213,9 @@ class PerceptualCorrectness(nn.Module):
         if use_bilinear_sampling:
             warped = self.bilinear_warp(source_feat, flow)
         else:
+            # 16-bit features (half_features="native"): the warp itself stays float32, on one up-cast of the source map
+            if source_feat.dtype in _lib.HALF_TYPES:
+                source_feat = source_feat.float()
             warped = self.resample(source_feat, flow).view(b, c, -1)                  # :273
         if self.fused and warped.dtype == torch.float32:
             loss_map = CorrectnessMapFunction.apply(warped.contiguous(), target_feat.reshape(b, c, -1).contiguous(),

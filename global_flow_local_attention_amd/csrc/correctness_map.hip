@@ -6,7 +6,8 @@
 // torch evaluates this as ~10 elementwise/reduction kernels forward and as many backward, each a pass
 // over the (B,C,N) features.  Here: one pass forward (three channel sums per position, exp) and one
 // pass backward (the per-position factors once, then one fused multiply-add per feature element).
-// All of it is HBM-bound: 2 reads of (B,C,N) forward; 2 reads + 1..2 writes backward.
+// All of it is HBM-bound: 2 reads of (B,C,N) forward; 2 reads + 1..2 writes backward.  The target map may be in 16-bit
+// storage (the _f16 / _bf16 entries): it is read as it is, never copied to float32.
 //
 // cosine_similarity semantics are those of the torch this package runs on (2.x): each norm is clamped from
 // below by eps_cos (1e-8), and the clamp is not differentiated:
@@ -17,8 +18,10 @@ namespace gfla {
 
 constexpr int kSlices = 4;  // channel slices per position (256 threads = 64 positions x 4 slices)
 
+// TT: storage type of the target map (float, f16_t, bf16_t); the warped map and every output but grad_target are float32.
+template <typename TT>
 __global__ __launch_bounds__(256) void correctness_map_fwd_kernel(const float *__restrict__ x,
-                                                                 const float *__restrict__ t,
+                                                                 const TT *__restrict__ t,
                                                                  const float *__restrict__ best,
                                                                  float *__restrict__ loss_map,
                                                                  float *__restrict__ stats, int C, int N,
@@ -32,7 +35,7 @@ __global__ __launch_bounds__(256) void correctness_map_fwd_kernel(const float *_
     const int64_t base = b * C * (int64_t)N + n;
 #pragma unroll 4
     for (int c = slice; c < C; c += kSlices) {
-      const float xv = x[base + (int64_t)c * N], tv = t[base + (int64_t)c * N];
+      const float xv = x[base + (int64_t)c * N], tv = Num<TT>::ld(t + base + (int64_t)c * N);
       sxt = fmaf(xv, tv, sxt);
       sxx = fmaf(xv, xv, sxx);
       stt = fmaf(tv, tv, stt);
@@ -56,14 +59,14 @@ __global__ __launch_bounds__(256) void correctness_map_fwd_kernel(const float *_
   }
 }
 
-template <bool GX, bool GT>
+template <typename TT, bool GX, bool GT>
 __global__ __launch_bounds__(256) void correctness_map_bwd_kernel(const float *__restrict__ x,
-                                                                 const float *__restrict__ t,
+                                                                 const TT *__restrict__ t,
                                                                  const float *__restrict__ best,
                                                                  const float *__restrict__ stats,
                                                                  const float *__restrict__ loss_map,
                                                                  const float *__restrict__ grad_map,
-                                                                 float *__restrict__ gx, float *__restrict__ gt,
+                                                                 float *__restrict__ gx, TT *__restrict__ gt,
                                                                  float *__restrict__ gbest, int C, int N,
                                                                  float eps_cos, float eps) {
   const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
@@ -86,9 +89,9 @@ __global__ __launch_bounds__(256) void correctness_map_bwd_kernel(const float *_
 #pragma unroll 4
   for (int c = slice; c < C; c += kSlices) {
     const int64_t o = base + (int64_t)c * N;
-    const float xv = x[o], tv = t[o];
+    const float xv = x[o], tv = Num<TT>::ld(t + o);
     if (GX) gx[o] = fmaf(tv, cross, -xv * selfx);
-    if (GT) gt[o] = fmaf(xv, cross, -tv * selft);
+    if (GT) gt[o] = (TT)fmaf(xv, cross, -tv * selft);   // float32 arithmetic, one rounding at the store
   }
 }
 
@@ -98,36 +101,31 @@ static int map_check(int64_t B, int64_t C, int64_t N) {
   return GFLA_OK;
 }
 
-}  // namespace gfla
-
-extern "C" {
-int gfla_correctness_map_fwd_f32(const float *warped, const float *target, const float *best, float *loss_map,
-                                 float *stats, int64_t B, int64_t C, int64_t N, double eps_cos, double eps,
-                                 gfla_stream_t stream) {
-  using namespace gfla;
+template <typename TT>
+static int map_fwd(const float *warped, const TT *target, const float *best, float *loss_map, float *stats, int64_t B,
+                   int64_t C, int64_t N, double eps_cos, double eps, gfla_stream_t stream) {
   if (!warped || !target || !best || !loss_map || !stats) return GFLA_ERR_NULL_POINTER;
   if (int rc = map_check(B, C, N)) return rc;
   if (B == 0 || N == 0) return GFLA_OK;
-  correctness_map_fwd_kernel<<<dim3((unsigned)ceil_div(N, 64), (unsigned)B), 256, 0,
-                               static_cast<hipStream_t>(stream)>>>(warped, target, best, loss_map, stats, (int)C,
-                                                                   (int)N, (float)eps_cos, (float)eps);
+  correctness_map_fwd_kernel<TT><<<dim3((unsigned)ceil_div(N, 64), (unsigned)B), 256, 0,
+                                   static_cast<hipStream_t>(stream)>>>(warped, target, best, loss_map, stats, (int)C,
+                                                                       (int)N, (float)eps_cos, (float)eps);
   return launch_status();
 }
 
-int gfla_correctness_map_bwd_f32(const float *warped, const float *target, const float *best, const float *stats,
-                                 const float *loss_map, const float *grad_map, float *grad_warped,
-                                 float *grad_target, float *grad_best, int64_t B, int64_t C, int64_t N,
-                                 double eps_cos, double eps, gfla_stream_t stream) {
-  using namespace gfla;
+template <typename TT>
+static int map_bwd(const float *warped, const TT *target, const float *best, const float *stats, const float *loss_map,
+                   const float *grad_map, float *grad_warped, TT *grad_target, float *grad_best, int64_t B, int64_t C,
+                   int64_t N, double eps_cos, double eps, gfla_stream_t stream) {
   if (!warped || !target || !best || !stats || !loss_map || !grad_map) return GFLA_ERR_NULL_POINTER;
   if (int rc = map_check(B, C, N)) return rc;
   if (B == 0 || N == 0 || (!grad_warped && !grad_target && !grad_best)) return GFLA_OK;
   const dim3 grid((unsigned)ceil_div(N, 64), (unsigned)B);
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define GFLA_MAP_BWD(GX_, GT_)                                                                                   \
-  correctness_map_bwd_kernel<GX_, GT_><<<grid, 256, 0, st>>>(warped, target, best, stats, loss_map, grad_map,    \
-                                                             grad_warped, grad_target, grad_best, (int)C, (int)N, \
-                                                             (float)eps_cos, (float)eps)
+#define GFLA_MAP_BWD(GX_, GT_)                                                                                      \
+  correctness_map_bwd_kernel<TT, GX_, GT_><<<grid, 256, 0, st>>>(warped, target, best, stats, loss_map, grad_map,   \
+                                                                 grad_warped, grad_target, grad_best, (int)C, (int)N, \
+                                                                 (float)eps_cos, (float)eps)
   if (grad_warped && grad_target) GFLA_MAP_BWD(true, true);
   else if (grad_warped) GFLA_MAP_BWD(true, false);
   else if (grad_target) GFLA_MAP_BWD(false, true);
@@ -135,4 +133,41 @@ int gfla_correctness_map_bwd_f32(const float *warped, const float *target, const
 #undef GFLA_MAP_BWD
   return launch_status();
 }
+
+}  // namespace gfla
+
+extern "C" {
+int gfla_correctness_map_fwd_f32(const float *warped, const float *target, const float *best, float *loss_map,
+                                 float *stats, int64_t B, int64_t C, int64_t N, double eps_cos, double eps,
+                                 gfla_stream_t stream) {
+  return gfla::map_fwd<float>(warped, target, best, loss_map, stats, B, C, N, eps_cos, eps, stream);
+}
+
+int gfla_correctness_map_bwd_f32(const float *warped, const float *target, const float *best, const float *stats,
+                                 const float *loss_map, const float *grad_map, float *grad_warped,
+                                 float *grad_target, float *grad_best, int64_t B, int64_t C, int64_t N,
+                                 double eps_cos, double eps, gfla_stream_t stream) {
+  return gfla::map_bwd<float>(warped, target, best, stats, loss_map, grad_map, grad_warped, grad_target, grad_best, B, C,
+                              N, eps_cos, eps, stream);
+}
+
+// 16-bit target (float16 / bfloat16 storage): warped and everything else float32, grad_target in the storage type
+#define GFLA_MAP_16(SFX, TT)                                                                                          \
+  int gfla_correctness_map_fwd_##SFX(const float *warped, const uint16_t *target, const float *best, float *loss_map, \
+                                     float *stats, int64_t B, int64_t C, int64_t N, double eps_cos, double eps,       \
+                                     gfla_stream_t stream) {                                                          \
+    return gfla::map_fwd<gfla::TT>(warped, reinterpret_cast<const gfla::TT *>(target), best, loss_map, stats, B, C,   \
+                                   N, eps_cos, eps, stream);                                                          \
+  }                                                                                                                   \
+  int gfla_correctness_map_bwd_##SFX(const float *warped, const uint16_t *target, const float *best,                  \
+                                     const float *stats, const float *loss_map, const float *grad_map,                \
+                                     float *grad_warped, uint16_t *grad_target, float *grad_best, int64_t B,          \
+                                     int64_t C, int64_t N, double eps_cos, double eps, gfla_stream_t stream) {        \
+    return gfla::map_bwd<gfla::TT>(warped, reinterpret_cast<const gfla::TT *>(target), best, stats, loss_map,         \
+                                   grad_map, grad_warped, reinterpret_cast<gfla::TT *>(grad_target), grad_best, B, C, \
+                                   N, eps_cos, eps, stream);                                                          \
+  }
+GFLA_MAP_16(f16, f16_t)
+GFLA_MAP_16(bf16, bf16_t)
+#undef GFLA_MAP_16
 }

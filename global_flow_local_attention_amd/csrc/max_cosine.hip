@@ -42,9 +42,11 @@ __device__ __forceinline__ float unpack_best(unsigned long long key, int *idx) {
   return __uint_as_float(u);
 }
 
-// out[b, n] = 1 / (sqrt(sum_c x[b, c, n]^2) + eps): lanes along n (coalesced), 4 channel slices.
+// out[b, n] = 1 / (sqrt(sum_c x[b, c, n]^2) + eps): lanes along n (coalesced), 4 channel slices; float32 sums whatever
+// the storage type T (float, f16_t, bf16_t).
 // keys != NULL: also reset the packed maxima of these positions.
-__global__ __launch_bounds__(256) void inv_norm_kernel(const float *__restrict__ x, float *__restrict__ out,
+template <typename T>
+__global__ __launch_bounds__(256) void inv_norm_kernel(const T *__restrict__ x, float *__restrict__ out,
                                                       unsigned long long *__restrict__ keys, int C, int N,
                                                       float eps) {
   __shared__ float part[4][64];
@@ -53,9 +55,9 @@ __global__ __launch_bounds__(256) void inv_norm_kernel(const float *__restrict__
   const int64_t b = blockIdx.y;
   float s = 0.f;
   if (n < N) {
-    const float *p = x + b * C * (int64_t)N + n;
+    const T *p = x + b * C * (int64_t)N + n;
     for (int c = slice; c < C; c += 4) {
-      const float v = p[(int64_t)c * N];
+      const float v = Num<T>::ld(p + (int64_t)c * N);
       s = fmaf(v, v, s);
     }
   }
@@ -293,9 +295,9 @@ static int max_cosine(const float *source, const float *target, void *workspace,
   float *inv_t = reinterpret_cast<float *>(ws + align16(8 * B * Nt));
   float *inv_s = reinterpret_cast<float *>(ws + align16(8 * B * Nt) + align16(4 * B * Nt));
 
-  inv_norm_kernel<<<dim3((unsigned)ceil_div(Ns, 64), (unsigned)B), 256, 0, stream>>>(source, inv_s, nullptr, (int)C,
+  inv_norm_kernel<float><<<dim3((unsigned)ceil_div(Ns, 64), (unsigned)B), 256, 0, stream>>>(source, inv_s, nullptr, (int)C,
                                                                                     (int)Ns, (float)eps);
-  inv_norm_kernel<<<dim3((unsigned)ceil_div(Nt, 64), (unsigned)B), 256, 0, stream>>>(target, inv_t, keys, (int)C,
+  inv_norm_kernel<float><<<dim3((unsigned)ceil_div(Nt, 64), (unsigned)B), 256, 0, stream>>>(target, inv_t, keys, (int)C,
                                                                                     (int)Nt, (float)eps);
   const int64_t per_xcd = ceil_div(total, kNumXCD);
   const dim3 grid((unsigned)(per_xcd * kNumXCD));
@@ -317,6 +319,313 @@ static int max_cosine(const float *source, const float *target, void *workspace,
   return launch_status();
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------
+// 16-bit storage (float16 / bfloat16) on v_mfma_f32_32x32x16_{f16,bf16}.  A product of two f16 or two bf16 values is
+// exact in the float32 accumulator, so this evaluates the same rounded features as the float32 kernel would after an
+// up-cast, at 16 x the matrix rate and without the float32 copies.
+//
+// A unit = (sample, TN target columns, a range of source tiles), as above, but the target tile stays RESIDENT in the LDS
+// for the unit's lifetime ([c][n] rows exactly as they lie in memory, 16-byte loads along n) and only 128-row source
+// tiles stream past it, double-buffered in chunks of 32 channels: at the 16-bit rate a unit that re-read both operands
+// per source tile would be bound by the L2.  TN = 256 while C <= 256 (128 KB), 128 while C <= 512; beyond that the
+// target is re-staged in passes of 512 channels per source tile (correct for any C, no longer resident).
+//
+// K = C is the strided axis of both maps, while a lane's MFMA fragment is 8 consecutive k of ONE position: the
+// fragments are read with ds_read_b64_tr_b16, which hands lane i of a 16-lane group column i of a 4-row x 16-column
+// block.  Within a 32-lane half the two groups read 4 rows x 64 contiguous bytes; the 64-byte segments of a row are
+// XOR-ed with (row & 3) so that the four rows fall into the four quarters of the 256-byte bank row (conflict-free; the
+// row pitches are multiples of 256 bytes).  The read needs EXEC all ones: nothing in the loop below is lane-dependent.
+constexpr int kTM16 = 128;     // source positions per streamed tile
+constexpr int kKC16 = 32;      // channels per streamed chunk (two k = 16 steps)
+constexpr int kCR16 = 512;     // most channels of a 128-column target tile kept in the LDS
+constexpr int kThreads16 = 512;
+
+typedef _Float16 mc_f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 mc_bf16x8 __attribute__((ext_vector_type(8)));
+typedef short mc_s16x4 __attribute__((ext_vector_type(4)));
+typedef short mc_s16x8 __attribute__((ext_vector_type(8)));
+
+// byte offset of 16-bit element (row, col) in an image with `pitch` bytes per row (pitch % 256 == 0)
+__device__ __forceinline__ int img_off(int row, int col, int pitch) { return row * pitch + ((col * 2) ^ ((row & 3) << 6)); }
+
+__device__ __forceinline__ mc_s16x8 tr_frag(const unsigned char *p, int pitch) {
+  typedef __attribute__((address_space(3))) mc_s16x4 lds_s16x4;
+  const mc_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p));
+  const mc_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p + 4 * pitch));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+template <typename T>
+__device__ __forceinline__ f32x16 mma16(mc_s16x8 a, mc_s16x8 b, f32x16 acc) {
+  if constexpr (sizeof(T) == 2 && __is_same(T, f16_t))
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(mc_f16x8, a), __builtin_bit_cast(mc_f16x8, b), acc, 0,
+                                                  0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mc_bf16x8, a), __builtin_bit_cast(mc_bf16x8, b), acc,
+                                                   0, 0, 0);
+}
+
+// Eight consecutive 16-bit elements of channel row c, columns col .. col + 7 (col % 8 == 0).  FAST (rows 16-byte
+// aligned, N % 8 == 0): one 16-byte load; an octet past the row end is redirected to the last octet of the row (those
+// source rows are masked to -inf after the MFMAs and those target columns are never merged).  Otherwise element-wise,
+// zero beyond the row end.  Channels >= C are zero either way.
+template <bool FAST>
+__device__ __forceinline__ uint4 load_octet(const uint16_t *__restrict__ plane, int c, int C, int N, int col) {
+  uint4 r = make_uint4(0u, 0u, 0u, 0u);
+  if (c >= C) return r;
+  const uint16_t *row = plane + (int64_t)c * N;
+  if constexpr (FAST) {
+    return *reinterpret_cast<const uint4 *>(row + min(col, N - 8));
+  }
+  uint32_t w[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const uint32_t lo = col + 2 * e < N ? row[col + 2 * e] : 0u;
+    const uint32_t hi = col + 2 * e + 1 < N ? row[col + 2 * e + 1] : 0u;
+    w[e] = lo | (hi << 16);
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// 8 waves = 2 (rows) x 4 (columns); a wave owns 64 x (TN / 4) outputs.
+template <typename T, bool FAST, int TN>
+__global__ __launch_bounds__(kThreads16) void max_cosine16_kernel(const uint16_t *__restrict__ S,
+                                                                  const uint16_t *__restrict__ Tg,
+                                                                  const float *__restrict__ rs,
+                                                                  unsigned long long *__restrict__ keys, int C, int Ns,
+                                                                  int Nt, int CR, int tilesN, int splitM, int total,
+                                                                  int per_xcd) {
+  constexpr int WN = TN / 4;       // columns per wave
+  constexpr int NJ = WN / 32;      // 32-column MFMA blocks per wave
+  constexpr int PA = kTM16 * 2;    // byte pitch of a source chunk row
+  constexpr int PB = TN * 2;       // byte pitch of a target row
+  constexpr int kOctB = TN / 8;    // 16-byte loads per target row
+  extern __shared__ __attribute__((aligned(16))) unsigned char mc_smem[];
+  unsigned char *Bs = mc_smem;                               // [CR][TN] 16-bit, swizzled
+  unsigned char *As = Bs + CR * PB;                          // [2][kKC16][kTM16] 16-bit, swizzled
+  float *rsl = reinterpret_cast<float *>(As + 2 * kKC16 * PA);   // [2][kTM16]
+  float *red_v = rsl + 2 * kTM16;                            // [TN]
+  int *red_i = reinterpret_cast<int *>(red_v + TN);          // [TN]
+
+  const int v = (blockIdx.x % kNumXCD) * per_xcd + blockIdx.x / kNumXCD;
+  if (v >= total) return;
+  const int per_sample = tilesN * splitM;
+  const int64_t b = v / per_sample;
+  const int rem = v - (int)b * per_sample;
+  const int n0 = (rem / splitM) * TN;
+  const int part = rem % splitM;
+  const int nM_all = (Ns + kTM16 - 1) / kTM16;
+  const int mt0 = (int)((int64_t)nM_all * part / splitM);
+  const int mt1 = (int)((int64_t)nM_all * (part + 1) / splitM);
+
+  const uint16_t *Sb = S + b * C * (int64_t)Ns;
+  const uint16_t *Tb = Tg + b * C * (int64_t)Nt;
+
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 2, wn = wave & 3;
+  const int l31 = lane & 31, kh = lane >> 5;
+  // transposed read: lane 4q + p of a 16-lane group supplies row q, columns 4p .. 4p + 3 of the group's block
+  const int tq = (lane & 15) >> 2, tcol = ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
+  // (one offset per 32-position block: the XOR does not commute with adding a block's 64 bytes)
+  int a_off[2], b_off[NJ];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) a_off[i] = img_off(8 * kh + tq, wm * 64 + i * 32 + tcol, PA);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) b_off[j] = img_off(8 * kh + tq, wn * WN + j * 32 + tcol, PB);
+  const int ld_row = t >> 4, ld_col = (t & 15) * 8;  // source staging: one octet per thread and chunk
+
+  const int nK = (C + kKC16 - 1) / kKC16;   // chunks per source tile
+  const int nKR = CR / kKC16;               // chunks per resident target pass
+  const bool resident = nK <= nKR;
+  const int iters = (mt1 - mt0) * nK;
+
+  auto stage_target = [&](int cb) {   // channels cb .. cb + CR - 1 of the unit's TN columns
+    for (int i = t; i < CR * kOctB; i += kThreads16) {
+      const int r = i / kOctB, col = (i % kOctB) * 8;
+      *reinterpret_cast<uint4 *>(Bs + img_off(r, col, PB)) = load_octet<FAST>(Tb, cb + r, C, Nt, n0 + col);
+    }
+  };
+
+  uint4 ra;
+  float rscale = 0.f;
+  auto fetch = [&](int it) {
+    const int mt = mt0 + it / nK, c0 = (it % nK) * kKC16;
+    ra = load_octet<FAST>(Sb, c0 + ld_row, C, Ns, mt * kTM16 + ld_col);
+    if (c0 == 0 && t < kTM16) {
+      const int m = mt * kTM16 + t;
+      rscale = m < Ns ? rs[b * Ns + m] : 0.f;
+    }
+  };
+  auto stage = [&](int it) {
+    *reinterpret_cast<uint4 *>(As + (it & 1) * kKC16 * PA + img_off(ld_row, ld_col, PA)) = ra;
+    if (it % nK == 0 && t < kTM16) rsl[((it / nK) & 1) * kTM16 + t] = rscale;
+  };
+
+  f32x16 acc[2][NJ];
+  float best[NJ];
+  int bidx[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    best[j] = -INFINITY;
+    bidx[j] = 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  }
+
+  if (iters > 0) {
+    fetch(0);
+    if (resident) stage_target(0);
+    stage(0);
+  }
+  __syncthreads();
+
+  for (int it = 0; it < iters; ++it) {
+    const int kc = it % nK;
+    if (!resident && kc % nKR == 0) {   // uniform: the next pass of target channels replaces the last one
+      __syncthreads();
+      stage_target(kc * kKC16);
+      __syncthreads();
+    }
+    if (it + 1 < iters) fetch(it + 1);
+
+    const unsigned char *Ab = As + (it & 1) * kKC16 * PA;
+    const unsigned char *Bb = Bs + (kc % nKR) * kKC16 * PB;
+#pragma unroll
+    for (int kk = 0; kk < kKC16; kk += 16) {   // rows kk + 16 n and + 4 keep (row & 3): the offsets carry over
+      const mc_s16x8 a0 = tr_frag(Ab + kk * PA + a_off[0], PA), a1 = tr_frag(Ab + kk * PA + a_off[1], PA);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const mc_s16x8 bj = tr_frag(Bb + kk * PB + b_off[j], PB);
+        acc[0][j] = mma16<T>(a0, bj, acc[0][j]);
+        acc[1][j] = mma16<T>(a1, bj, acc[1][j]);
+      }
+    }
+
+    if (kc == nK - 1) {
+      // rows of this tile are complete: scale by 1/(|s|+eps), fold into the running column maxima.
+      // C/D layout: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
+      const int lt = it / nK, mt = mt0 + lt;
+      const float *sc = rsl + (lt & 1) * kTM16;
+      const bool ragged = (mt + 1) * kTM16 > Ns;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int ml = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+          const int m = mt * kTM16 + ml;
+          const float s = sc[ml];
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            float val = acc[i][j][r] * s;
+            if (ragged && m >= Ns) val = -INFINITY;
+            if (val > best[j]) {
+              best[j] = val;
+              bidx[j] = m;
+            }
+            acc[i][j][r] = 0.f;
+          }
+        }
+    }
+
+    if (it + 1 < iters) stage(it + 1);
+    __syncthreads();
+  }
+
+  // merge the two row groups of a wave (lanes l, l ^ 32), then the two waves stacked along the rows,
+  // then this unit into the global keys
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const float ov = __shfl_xor(best[j], 32);
+    const int oi = __shfl_xor(bidx[j], 32);
+    if (ov > best[j] || (ov == best[j] && oi < bidx[j])) {
+      best[j] = ov;
+      bidx[j] = oi;
+    }
+  }
+  if (wm == 1 && kh == 0) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      red_v[wn * WN + j * 32 + l31] = best[j];
+      red_i[wn * WN + j * 32 + l31] = bidx[j];
+    }
+  }
+  __syncthreads();
+  if (wm == 0 && kh == 0) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int nl = wn * WN + j * 32 + l31;
+      const float ov = red_v[nl];
+      const int oi = red_i[nl];
+      if (ov > best[j] || (ov == best[j] && oi < bidx[j])) {
+        best[j] = ov;
+        bidx[j] = oi;
+      }
+      const int n = n0 + nl;
+      if (n < Nt && best[j] > -INFINITY) atomicMax(&keys[b * Nt + n], pack_best(best[j], bidx[j]));
+    }
+  }
+}
+
+template <typename T>
+static int max_cosine16(const uint16_t *source, const uint16_t *target, void *workspace, float *out_max, int32_t *out_idx,
+                        int64_t B, int64_t C, int64_t Ns, int64_t Nt, double eps, gfla_stream_t stream_) {
+  if (!source || !target || !workspace || !out_max) return GFLA_ERR_NULL_POINTER;
+  if (B < 0 || C <= 0 || Ns <= 0 || Nt < 0) return GFLA_ERR_BAD_SHAPE;
+  if (B == 0 || Nt == 0) return GFLA_OK;
+  if (Ns > 0x7fffff00LL || Nt > 0x7fffff00LL || C > 0x7fffff00LL || B > 65535) return GFLA_ERR_UNSUPPORTED;
+  const int64_t Cpad = ceil_div(C, kKC16) * kKC16;
+  const int TN = Cpad <= 256 ? 256 : 128;
+  const int64_t CR = Cpad < kCR16 ? Cpad : kCR16;
+  const int64_t tilesN = ceil_div(Nt, TN), nM = ceil_div(Ns, kTM16);
+  // one workgroup per CU while the target tile fills the LDS: several units per slot keep the tail of the launch short,
+  // few enough that the one-off load of the resident tile stays small beside the source tiles streamed past it
+  int64_t splitM = tuning(5) > 0 ? tuning(5) : ceil_div(4 * (int64_t)kNumCU, B * tilesN);
+  if (splitM > nM) splitM = nM;
+  if (splitM < 1) splitM = 1;
+  const int64_t total = B * tilesN * splitM;
+  if (total > 0x7ffffff0LL) return GFLA_ERR_UNSUPPORTED;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+
+  char *ws = static_cast<char *>(workspace);
+  unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws);
+  float *inv_t = reinterpret_cast<float *>(ws + align16(8 * B * Nt));
+  float *inv_s = reinterpret_cast<float *>(ws + align16(8 * B * Nt) + align16(4 * B * Nt));
+  const T *src_t = reinterpret_cast<const T *>(source), *tgt_t = reinterpret_cast<const T *>(target);
+  inv_norm_kernel<T><<<dim3((unsigned)ceil_div(Ns, 64), (unsigned)B), 256, 0, stream>>>(src_t, inv_s, nullptr, (int)C,
+                                                                                       (int)Ns, (float)eps);
+  inv_norm_kernel<T><<<dim3((unsigned)ceil_div(Nt, 64), (unsigned)B), 256, 0, stream>>>(tgt_t, inv_t, keys, (int)C,
+                                                                                       (int)Nt, (float)eps);
+  const int64_t per_xcd = ceil_div(total, kNumXCD);
+  const dim3 grid((unsigned)(per_xcd * kNumXCD));
+  const bool fast = Ns % 8 == 0 && Nt % 8 == 0 && Ns >= 8 && Nt >= 8 &&
+                    ((reinterpret_cast<uintptr_t>(source) | reinterpret_cast<uintptr_t>(target)) & 15) == 0;
+  // resident target + two source chunks + the source scales of two tiles + the cross-wave merge
+  const size_t lds = (size_t)CR * TN * 2 + 2 * kKC16 * kTM16 * 2 + 2 * kTM16 * 4 + (size_t)TN * 8;
+#define GFLA_MC16_LAUNCH(FAST_, TN_)                                                                                  \
+  do {                                                                                                                \
+    auto kern = max_cosine16_kernel<T, FAST_, TN_>;                                                                   \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,       \
+                              (int)lds);                                                                              \
+    kern<<<grid, kThreads16, lds, stream>>>(source, target, inv_s, keys, (int)C, (int)Ns, (int)Nt, (int)CR,           \
+                                            (int)tilesN, (int)splitM, (int)total, (int)per_xcd);                      \
+  } while (0)
+  if (TN == 256) {
+    if (fast) GFLA_MC16_LAUNCH(true, 256);
+    else GFLA_MC16_LAUNCH(false, 256);
+  } else {
+    if (fast) GFLA_MC16_LAUNCH(true, 128);
+    else GFLA_MC16_LAUNCH(false, 128);
+  }
+#undef GFLA_MC16_LAUNCH
+  max_cosine_finish_kernel<<<dim3((unsigned)ceil_div(B * Nt, 256)), 256, 0, stream>>>(keys, inv_t, out_max, out_idx,
+                                                                                     B * Nt);
+  return launch_status();
+}
+
 }  // namespace gfla
 
 extern "C" {
@@ -329,5 +638,17 @@ int gfla_max_cosine_fwd_f32(const float *source, const float *target, void *work
                             int32_t *out_idx, int64_t B, int64_t C, int64_t Ns, int64_t Nt, double eps,
                             gfla_stream_t stream) {
   return gfla::max_cosine(source, target, workspace, out_max, out_idx, B, C, Ns, Nt, eps, stream);
+}
+
+int gfla_max_cosine_fwd_f16(const uint16_t *source, const uint16_t *target, void *workspace, float *out_max,
+                            int32_t *out_idx, int64_t B, int64_t C, int64_t Ns, int64_t Nt, double eps,
+                            gfla_stream_t stream) {
+  return gfla::max_cosine16<gfla::f16_t>(source, target, workspace, out_max, out_idx, B, C, Ns, Nt, eps, stream);
+}
+
+int gfla_max_cosine_fwd_bf16(const uint16_t *source, const uint16_t *target, void *workspace, float *out_max,
+                             int32_t *out_idx, int64_t B, int64_t C, int64_t Ns, int64_t Nt, double eps,
+                             gfla_stream_t stream) {
+  return gfla::max_cosine16<gfla::bf16_t>(source, target, workspace, out_max, out_idx, B, C, Ns, Nt, eps, stream);
 }
 }

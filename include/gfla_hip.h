@@ -59,7 +59,8 @@ typedef void *gfla_stream_t; /* hipStream_t */
  *      gfla_xcd_swizzle)
  *   8: round 6 (arithmetic mode 5 of gfla_fc_*: Winograd domain with two-term f16 operands on the f16 matrix cores,
  *      csrc/fc_wino16.hip; path ids 18 / 19; tuning keys 43, 46, 49, 52); float16 storage (the _f16 entry points,
- *      gfla_fc_forward_f16, gfla_convert_multi flags 2 / 3, path id 21) only ADDS symbols and ids and keeps 8 */
+ *      gfla_fc_forward_f16, gfla_convert_multi flags 2 / 3, path id 21) only ADDS symbols and ids and keeps 8; so do
+ *      gfla_max_cosine_fwd_f16 / _bf16 and gfla_correctness_map_{fwd,bwd}_f16 / _bf16 */
 #define GFLA_ABI_VERSION 8
 int gfla_abi_version(void);
 const char *gfla_status_string(int status);
@@ -542,6 +543,17 @@ int64_t gfla_max_cosine_workspace_bytes(int64_t B, int64_t Ns, int64_t Nt);
 int gfla_max_cosine_fwd_f32(const float *source, const float *target, void *workspace, float *out_max,
                             int32_t *out_idx, int64_t B, int64_t C, int64_t Ns, int64_t Nt, double eps,
                             gfla_stream_t stream);
+/* The same on 16-bit storage (float16 / bfloat16 bit patterns), source and target of one type: v_mfma_f32_32x32x16_f16 /
+ * _bf16 with float32 accumulators.  A product of two 16-bit values is exact in float32, so the result is that of the
+ * float32 entry on the up-cast inputs up to the order of the float32 sums.  The target tile of a unit stays in the LDS
+ * and the source streams past it; no float32 or transposed copy of either map is made.  out_max float32, out_idx
+ * int32, eps, NaN handling and the workspace (gfla_max_cosine_workspace_bytes) as above. */
+int gfla_max_cosine_fwd_f16(const uint16_t *source, const uint16_t *target, void *workspace, float *out_max,
+                            int32_t *out_idx, int64_t B, int64_t C, int64_t Ns, int64_t Nt, double eps,
+                            gfla_stream_t stream);
+int gfla_max_cosine_fwd_bf16(const uint16_t *source, const uint16_t *target, void *workspace, float *out_max,
+                             int32_t *out_idx, int64_t B, int64_t C, int64_t Ns, int64_t Nt, double eps,
+                             gfla_stream_t stream);
 
 /* ---- per-position map of the sampling-correctness loss (external_function.py:275-276) -----------------
  *   loss_map[b,n] = exp(-cosine_similarity(warped[b,:,n], target[b,:,n]) / (best[b,n] + eps))
@@ -555,6 +567,23 @@ int gfla_correctness_map_fwd_f32(const float *warped, const float *target, const
 int gfla_correctness_map_bwd_f32(const float *warped, const float *target, const float *best,
                                  const float *stats, const float *loss_map, const float *grad_map,
                                  float *grad_warped, float *grad_target, float *grad_best, int64_t B,
+                                 int64_t C, int64_t N, double eps_cos, double eps, gfla_stream_t stream);
+/* 16-bit target map (float16 / bfloat16 storage), float32 warped map: the target is read as stored, never up-cast.
+ * best, loss_map, stats, grad_map, grad_best and grad_warped stay float32; grad_target is written in the storage type
+ * (float32 arithmetic, one rounding at the store). */
+int gfla_correctness_map_fwd_f16(const float *warped, const uint16_t *target, const float *best,
+                                 float *loss_map, float *stats, int64_t B, int64_t C, int64_t N,
+                                 double eps_cos, double eps, gfla_stream_t stream);
+int gfla_correctness_map_bwd_f16(const float *warped, const uint16_t *target, const float *best,
+                                 const float *stats, const float *loss_map, const float *grad_map,
+                                 float *grad_warped, uint16_t *grad_target, float *grad_best, int64_t B,
+                                 int64_t C, int64_t N, double eps_cos, double eps, gfla_stream_t stream);
+int gfla_correctness_map_fwd_bf16(const float *warped, const uint16_t *target, const float *best,
+                                 float *loss_map, float *stats, int64_t B, int64_t C, int64_t N,
+                                 double eps_cos, double eps, gfla_stream_t stream);
+int gfla_correctness_map_bwd_bf16(const float *warped, const uint16_t *target, const float *best,
+                                 const float *stats, const float *loss_map, const float *grad_map,
+                                 float *grad_warped, uint16_t *grad_target, float *grad_best, int64_t B,
                                  int64_t C, int64_t N, double eps_cos, double eps, gfla_stream_t stream);
 
 /* Storage-type conversion of up to four contiguous tensors in one launch (unused jobs: n = 0).  to_bf16 = 0: bfloat16 ->
