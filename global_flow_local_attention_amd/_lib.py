@@ -80,6 +80,15 @@ _SINGLE = {
     "gfla_fc_forward_f16": [_ptr] * 9 + [_i64] * 4 + [_int, ctypes.c_double, _ptr],
     "gfla_gemm_f64_workspace_bytes": [_i64] * 3 + [_int],
     "gfla_gemm_f64": [_ptr] * 6 + [_i64] * 3 + [_int, _int, _ptr, _ptr],
+    "gfla_affine_reg_workspace_bytes": [_i64] * 3 + [_int],
+    "gfla_affine_reg_fwd_f32": [_ptr] * 3 + [_i64] * 3 + [_int, _ptr],
+    "gfla_affine_reg_fwd_f64": [_ptr] * 3 + [_i64] * 3 + [_int, _ptr],
+    "gfla_affine_reg_fwd_f16": [_ptr] * 3 + [_i64] * 3 + [_int, _ptr],
+    "gfla_affine_reg_fwd_bf16": [_ptr] * 3 + [_i64] * 3 + [_int, _ptr],
+    "gfla_affine_reg_bwd_f32": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
+    "gfla_affine_reg_bwd_f64": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
+    "gfla_affine_reg_bwd_f16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
+    "gfla_affine_reg_bwd_bf16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
 }
 # bf16 and f16 storage exist for every entry point below; the backward ones return the reductions over channels (grad_flow,
 # grad_logits, grad_in2) in float32 (include/gfla_hip.h)

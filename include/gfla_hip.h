@@ -60,7 +60,7 @@ typedef void *gfla_stream_t; /* hipStream_t */
  *   8: round 6 (arithmetic mode 5 of gfla_fc_*: Winograd domain with two-term f16 operands on the f16 matrix cores,
  *      csrc/fc_wino16.hip; path ids 18 / 19; tuning keys 43, 46, 49, 52); float16 storage (the _f16 entry points,
  *      gfla_fc_forward_f16, gfla_convert_multi flags 2 / 3, path id 21) only ADDS symbols and ids and keeps 8; so do
- *      gfla_max_cosine_fwd_f16 / _bf16 and gfla_correctness_map_{fwd,bwd}_f16 / _bf16 */
+ *      gfla_max_cosine_fwd_f16 / _bf16, gfla_correctness_map_{fwd,bwd}_f16 / _bf16 and gfla_affine_reg_* */
 #define GFLA_ABI_VERSION 8
 int gfla_abi_version(void);
 const char *gfla_status_string(int status);
@@ -618,6 +618,39 @@ int gfla_mask_blend_bwd_f16(const uint16_t *out, const uint16_t *attn_p, const u
                             const uint16_t *mask_r, const uint16_t *grad_y, uint16_t *g_out, uint16_t *g_attn_p,
                             uint16_t *g_attn_r, float *g_mask_p, float *g_mask_r, int64_t B, int64_t C, int64_t HW,
                             gfla_stream_t stream);
+
+/* ---- affine regularisation loss of a flow field (external_function.py:31-77; csrc/affine_reg.hip) ----------------------
+ *   loss = 1/(B L) sum over b, the two axes and the L = (H-k+1)(W-k+1) valid k x k windows of |f - P f|^2
+ * f = the flow patch of one axis, P f = the least-squares plane through it.  This is the reference's u^T M u on the
+ * sampling grid u = flow + coordinates (M = I - P annihilates the coordinates), evaluated without the grid.
+ * flow (B,2,H,W) contiguous, read in its storage type (widened exactly at the load); the differences inside a window, the
+ * plane fit and every sum after it are float64 for every storage type (float32 loses the gradient of a nearly affine
+ * flow: csrc/affine_reg.hip), so a 16- or 32-bit result is rounded once, at its store.  `loss`: ONE device scalar, float32 (float64 for _f64), = loss_x + loss_y as the reference returns it.
+ * `grad_loss`: one DEVICE scalar of the loss's type (d/d loss from upstream, a GradScaler's scale included; no host
+ * sync); grad_flow (B,2,H,W) in the flow's storage type, fully overwritten, rounded once at the store.
+ * `workspace`: gfla_affine_reg_workspace_bytes(B, H, W, k) bytes, 8-byte aligned, uninitialised: forward keeps its
+ * per-workgroup partial sums there.  Backward re-fits the windows from `flow` and does not read it (it may be NULL).
+ * No atomics: partial sums are reduced in a fixed order, loss and gradient are bit-identical from call to call.
+ * NULL -> -1; non-positive sizes, H < k or W < k -> -2; k outside 2..7 -> GFLA_ERR_UNSUPPORTED (k = 1 has no projector:
+ * A^T A is singular), as are H or W > 16384 and B > 32767.  gfla_affine_reg_workspace_bytes returns the same codes.
+ * Additive: GFLA_ABI_VERSION stays 8. */
+int64_t gfla_affine_reg_workspace_bytes(int64_t B, int64_t H, int64_t W, int k);
+int gfla_affine_reg_fwd_f32(const float *flow, void *workspace, float *loss, int64_t B, int64_t H, int64_t W, int k,
+                            gfla_stream_t stream);
+int gfla_affine_reg_fwd_f64(const double *flow, void *workspace, double *loss, int64_t B, int64_t H, int64_t W, int k,
+                            gfla_stream_t stream);
+int gfla_affine_reg_fwd_f16(const uint16_t *flow, void *workspace, float *loss, int64_t B, int64_t H, int64_t W, int k,
+                            gfla_stream_t stream);
+int gfla_affine_reg_fwd_bf16(const uint16_t *flow, void *workspace, float *loss, int64_t B, int64_t H, int64_t W, int k,
+                             gfla_stream_t stream);
+int gfla_affine_reg_bwd_f32(const float *flow, const float *grad_loss, void *workspace, float *grad_flow, int64_t B,
+                            int64_t H, int64_t W, int k, gfla_stream_t stream);
+int gfla_affine_reg_bwd_f64(const double *flow, const double *grad_loss, void *workspace, double *grad_flow, int64_t B,
+                            int64_t H, int64_t W, int k, gfla_stream_t stream);
+int gfla_affine_reg_bwd_f16(const uint16_t *flow, const float *grad_loss, void *workspace, uint16_t *grad_flow, int64_t B,
+                            int64_t H, int64_t W, int k, gfla_stream_t stream);
+int gfla_affine_reg_bwd_bf16(const uint16_t *flow, const float *grad_loss, void *workspace, uint16_t *grad_flow, int64_t B,
+                             int64_t H, int64_t W, int k, gfla_stream_t stream);
 
 #ifdef __cplusplus
 }
