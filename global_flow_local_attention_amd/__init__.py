@@ -10,7 +10,8 @@ from .local_attn_reshape import LocalAttnReshape, LocalAttnReshapeFunction  # no
 from .resample2d import Resample2d, Resample2dFunction  # noqa: F401
 from .extractor_attn import (BlockExtractorUnfoldFunction, ExtractorAttn, FcTailFunction, GraphedCall,  # noqa: F401
                              LocalAttnAggregateFunction, graphed_inference, patch_reference_extractor_attn)
-from .losses import AffineRegFunction, AffineRegularizationLoss, MultiAffineRegularizationLoss  # noqa: F401
+from .losses import (AffineRegFunction, AffineRegularizationLoss, GramL1Function, MultiAffineRegularizationLoss,  # noqa: F401
+                     PerceptualLoss, StyleContentLoss, StyleLoss, VGGLoss, gram_l1)
 from .correctness import CorrectnessMapFunction, MaxCosineFunction, PerceptualCorrectness, max_cosine_similarity  # noqa: F401
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401

@@ -89,6 +89,13 @@ _SINGLE = {
     "gfla_affine_reg_bwd_f64": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
     "gfla_affine_reg_bwd_f16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
     "gfla_affine_reg_bwd_bf16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
+    "gfla_gram_l1_workspace_bytes": [_i64] * 3,
+    "gfla_gram_l1_fwd_f32": [_ptr] * 5 + [_i64] * 3 + [_ptr],
+    "gfla_gram_l1_fwd_f16": [_ptr] * 5 + [_i64] * 3 + [_ptr],
+    "gfla_gram_l1_fwd_bf16": [_ptr] * 5 + [_i64] * 3 + [_ptr],
+    "gfla_gram_l1_bwd_f32": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
+    "gfla_gram_l1_bwd_f16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
+    "gfla_gram_l1_bwd_bf16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
 }
 # bf16 and f16 storage exist for every entry point below; the backward ones return the reductions over channels (grad_flow,
 # grad_logits, grad_in2) in float32 (include/gfla_hip.h)

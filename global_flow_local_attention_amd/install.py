@@ -34,8 +34,16 @@ def _namespace(name, path=None):
     return mod
 
 
+def _bind_vgg(cls, vgg):
+    """`cls` with `vgg` as its default feature extractor: the reference constructs its losses without arguments."""
+    def __init__(self, *args, **kwargs):
+        kwargs.setdefault("vgg", vgg)
+        cls.__init__(self, *args, **kwargs)
+    return type(cls.__name__, (cls,), {"__init__": __init__, "__doc__": cls.__doc__})
+
+
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
-            dual_stream_face=False, strict_mfma=None):
+            dual_stream_face=False, strict_mfma=None, vgg=None):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -52,7 +60,12 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
 
     dual_stream_face: also patch the reference's FaceTargetNet.forward (generator.py:480-505) so that the two ExtractorAttn
     of an attention layer (previous frame / reference frame) run on two HIP streams (face_step.py).  Imports the
-    reference's generator module."""
+    reference's generator module.
+
+    vgg: a feature extractor (image -> {layer name: feature map}, e.g. the reference's VGG19 with its weights loaded).  When
+    given, the reference's external_function.VGGLoss / StyleLoss / PerceptualLoss are replaced by this package's (losses.py:
+    the Gram term on csrc/gram_l1.hip instead of bmm), constructed around it; imports the reference's external_function
+    module.  None (the default) leaves them alone."""
     from . import extractor_attn as _ea
     if strict_mfma is None and allow_vendor_fallback is not None:
         strict_mfma = not allow_vendor_fallback
@@ -96,4 +109,9 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
         from .face_step import patch_reference_face_target_net
         generator = importlib.import_module("model.networks.generator")
         patch_reference_face_target_net(generator.FaceTargetNet)
+    if vgg is not None:
+        from . import losses
+        external_function = importlib.import_module("model.networks.external_function")
+        for cls in (losses.VGGLoss, losses.StyleLoss, losses.PerceptualLoss):
+            setattr(external_function, cls.__name__, _bind_vgg(cls, vgg))
     return base_function

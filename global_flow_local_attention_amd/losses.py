@@ -21,6 +21,11 @@ the squared residual of the least-squares plane through the flow patch.  The ker
 (float16 / bfloat16 included) and never form flow + grid; under torch.autocast the composition rounds u (coordinates up
 to the map size) and M to 16 bits before a product whose result is the small difference of large numbers (DESIGN.md
 section 5).
+
+`VGGLoss` / `StyleLoss` / `PerceptualLoss` (external_function.py:121-220) keep the reference's surface around an injected
+feature extractor.  The style term, L1 of the difference of two Gram matrices, runs on csrc/gram_l1.hip for GPU features
+(`gram_l1`, `GramL1Function`): float32 sums on the matrix cores from the features as stored, where the composition's bmm
+is on autocast's 16-bit list and rounds -- or overflows -- each Gram entry before the subtraction.
 """
 import numpy as np
 import torch
@@ -146,3 +151,169 @@ class MultiAffineRegularizationLoss(nn.Module):
             method.impl = self.impl
             loss += method(flow_fields[i])
         return loss
+
+
+# ---- style and content loss (VGGLoss, external_function.py:121-220) --------------------------------------------------
+STYLE_LAYERS = ("relu2_2", "relu3_4", "relu4_4", "relu5_2")
+CONTENT_LAYERS = ("relu1_1", "relu2_1", "relu3_1", "relu4_1", "relu5_1")
+GRAM_IMPLS = ("auto", "torch")
+_GRAM_SUFFIX = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
+
+
+def compute_gram(x):
+    """external_function.py:134-139: G = F F^T / (h w ch), F = x viewed as (b, ch, h w)."""
+    b, ch, h, w = x.size()
+    f = x.reshape(b, ch, w * h)
+    f_T = f.transpose(1, 2)
+    return f.bmm(f_T) / (h * w * ch)
+
+
+class GramL1Function(Function):
+    """(x, y), both (B,C,H,W) or (B,C,N), one dtype of float32 / float16 / bfloat16, on the GPU -> mean |G(x) - G(y)| as a
+    0-dim float32 tensor (csrc/gram_l1.hip).  The features are read as stored; both Grams are summed in float32 on the
+    matrix cores whatever torch.autocast says, separately and in the same order (x == y gives exactly 0), and D = G(x) -
+    G(y) is saved for the backward: d/dx = +g 2/(B C^3 N) sign(D) F_x, d/dy = -g 2/(B C^3 N) sign(D) F_y, each stored once
+    in the features' dtype and only for an input that needs it.  Bit-identical from call to call (no atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        _lib.require_gpu(x, y)
+        if x.dtype != y.dtype:
+            raise TypeError("gram l1 loss: x and y must have one dtype (got %s and %s)" % (x.dtype, y.dtype))
+        if x.dtype not in _GRAM_SUFFIX:
+            raise TypeError("gram l1 loss: unsupported dtype %s (float32, float16, bfloat16)" % x.dtype)
+        if x.dim() not in (3, 4) or x.shape != y.shape:
+            raise ValueError("gram l1 loss: x and y must be (B,C,H,W) or (B,C,N) of one shape, got %s and %s"
+                             % (tuple(x.shape), tuple(y.shape)))
+        if x.numel() == 0:
+            raise ValueError("gram l1 loss: empty features %s" % (tuple(x.shape),))
+        sfx = _GRAM_SUFFIX[x.dtype]
+        x, y = x.contiguous(), y.contiguous()
+        B, C = x.shape[:2]
+        N = x.numel() // (B * C)
+        n = _lib.lib().gfla_gram_l1_workspace_bytes(B, C, N)
+        if n < 0:
+            err = _lib.Unsupported if n == -3 else RuntimeError
+            raise err("gfla_gram_l1_workspace_bytes%s: %s" % ((B, C, N), _lib.lib().gfla_status_string(n).decode()))
+        scratch = torch.empty(int(n), dtype=torch.uint8, device=x.device)
+        diff = torch.empty((B, C, C), dtype=torch.float32, device=x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        _lib.call("gfla_gram_l1_fwd_" + sfx, x, _lib.ptr(x), _lib.ptr(y), _lib.ptr(scratch), _lib.ptr(diff),
+                  _lib.ptr(loss), B, C, N)
+        ctx.save_for_backward(x, y, diff)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        x, y, diff = ctx.saved_tensors
+        B, C = x.shape[:2]
+        N = x.numel() // (B * C)
+        grad_loss = grad_loss.to(torch.float32).contiguous()
+        grads = [None, None]
+        for i, feat in enumerate((x, y)):
+            if ctx.needs_input_grad[i]:
+                grads[i] = torch.empty_like(feat)
+                _lib.call("gfla_gram_l1_bwd_" + _GRAM_SUFFIX[feat.dtype], feat, _lib.ptr(feat), _lib.ptr(diff),
+                          _lib.ptr(grad_loss), _lib.ptr(grads[i]), B, C, N, i)
+        return grads[0], grads[1]
+
+
+def gram_l1(x, y, impl="auto"):
+    """L1Loss(compute_gram(x), compute_gram(y)): one style layer of VGGLoss.  impl "auto": GPU features of one dtype among
+    float32 / float16 / bfloat16 take the library's kernels (GramL1Function); CPU tensors, float64, mixed dtypes and
+    shapes the kernels refuse (_lib.Unsupported) take the torch composition, the reference's arithmetic.  "torch": always
+    the composition."""
+    if impl not in GRAM_IMPLS:
+        raise ValueError("impl: one of %s (got %r)" % (GRAM_IMPLS, impl))
+    if impl == "auto" and x.is_cuda and y.is_cuda and x.dtype == y.dtype and x.dtype in _GRAM_SUFFIX:
+        try:
+            return GramL1Function.apply(x, y)
+        except _lib.Unsupported:
+            pass
+    return F.l1_loss(compute_gram(x), compute_gram(y))
+
+
+class _VggLossBase(nn.Module):
+    """The feature extractor is injected (`vgg`: callable image -> {layer name: feature map}), as in
+    PerceptualCorrectness: neither torchvision nor its weights are part of this package."""
+
+    def __init__(self, vgg, impl):
+        super(_VggLossBase, self).__init__()
+        if impl not in GRAM_IMPLS:
+            raise ValueError("impl: one of %s (got %r)" % (GRAM_IMPLS, impl))
+        if isinstance(vgg, nn.Module):
+            self.add_module('vgg', vgg)
+        else:
+            self.vgg = vgg
+        self.criterion = torch.nn.L1Loss()
+        self.impl = impl   # "auto" | "torch": how the Gram term is evaluated (gram_l1)
+
+    def compute_gram(self, x):
+        return compute_gram(x)
+
+    def _features(self, x, y):
+        if self.vgg is None:
+            raise RuntimeError("%s needs a feature extractor: pass vgg=... (image -> dict of feature maps)"
+                               % type(self).__name__)
+        return self.vgg(x), self.vgg(y)
+
+    def _content(self, x_vgg, y_vgg):
+        content_loss = 0.0
+        for weight, layer in zip(self.weights, CONTENT_LAYERS):
+            content_loss += weight * self.criterion(x_vgg[layer], y_vgg[layer])
+        return content_loss
+
+    def _style(self, x_vgg, y_vgg):
+        style_loss = 0.0
+        for layer in STYLE_LAYERS:
+            style_loss += gram_l1(x_vgg[layer], y_vgg[layer], self.impl)
+        return style_loss
+
+
+class VGGLoss(_VggLossBase):
+    """external_function.py:121-160: (x, y) -> (content_loss, style_loss).  Content: weighted L1 over relu1_1 .. relu5_1
+    (F.l1_loss: float32 under autocast, not a GEMM).  Style: gram_l1 over relu2_2, relu3_4, relu4_4, relu5_2."""
+
+    def __init__(self, weights=[1.0, 1.0, 1.0, 1.0, 1.0], vgg=None, impl="auto"):
+        super(VGGLoss, self).__init__(vgg, impl)
+        self.weights = weights
+
+    def __call__(self, x, y):
+        x_vgg, y_vgg = self._features(x, y)
+        return self._content(x_vgg, y_vgg), self._style(x_vgg, y_vgg)
+
+
+class StyleLoss(_VggLossBase):
+    """external_function.py:162-193: (x, y) -> style_loss."""
+
+    def __init__(self, vgg=None, impl="auto"):
+        super(StyleLoss, self).__init__(vgg, impl)
+
+    def __call__(self, x, y):
+        return self._style(*self._features(x, y))
+
+
+class PerceptualLoss(_VggLossBase):
+    """external_function.py:197-220: (x, y) -> content_loss."""
+
+    def __init__(self, weights=[1.0, 1.0, 1.0, 1.0, 1.0], vgg=None, impl="auto"):
+        super(PerceptualLoss, self).__init__(vgg, impl)
+        self.weights = weights
+
+    def __call__(self, x, y):
+        return self._content(*self._features(x, y))
+
+
+class StyleContentLoss(nn.Module):
+    """(generated, target) -> lambda_style * style + lambda_content * content of VGGLoss (pose_model.py:35-36, 174-176):
+    the callable TrainerShell(style_content_loss=...) expects."""
+
+    def __init__(self, vgg, lambda_style=500.0, lambda_content=0.5, impl="auto"):
+        super(StyleContentLoss, self).__init__()
+        self.vgg_loss = VGGLoss(vgg=vgg, impl=impl)
+        self.lambda_style, self.lambda_content = lambda_style, lambda_content
+
+    def forward(self, generated, target):
+        content, style = self.vgg_loss(generated, target)
+        return style * self.lambda_style + content * self.lambda_content

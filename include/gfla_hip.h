@@ -60,7 +60,8 @@ typedef void *gfla_stream_t; /* hipStream_t */
  *   8: round 6 (arithmetic mode 5 of gfla_fc_*: Winograd domain with two-term f16 operands on the f16 matrix cores,
  *      csrc/fc_wino16.hip; path ids 18 / 19; tuning keys 43, 46, 49, 52); float16 storage (the _f16 entry points,
  *      gfla_fc_forward_f16, gfla_convert_multi flags 2 / 3, path id 21) only ADDS symbols and ids and keeps 8; so do
- *      gfla_max_cosine_fwd_f16 / _bf16, gfla_correctness_map_{fwd,bwd}_f16 / _bf16 and gfla_affine_reg_* */
+ *      gfla_max_cosine_fwd_f16 / _bf16, gfla_correctness_map_{fwd,bwd}_f16 / _bf16, gfla_affine_reg_* and
+ *      gfla_gram_l1_* */
 #define GFLA_ABI_VERSION 8
 int gfla_abi_version(void);
 const char *gfla_status_string(int status);
@@ -651,6 +652,33 @@ int gfla_affine_reg_bwd_f16(const uint16_t *flow, const float *grad_loss, void *
                             int64_t H, int64_t W, int k, gfla_stream_t stream);
 int gfla_affine_reg_bwd_bf16(const uint16_t *flow, const float *grad_loss, void *workspace, uint16_t *grad_flow, int64_t B,
                              int64_t H, int64_t W, int k, gfla_stream_t stream);
+
+/* ---- style term of VGGLoss: L1 distance of two Gram matrices (external_function.py:121-160; csrc/gram_l1.hip) ---------
+ *   F = x viewed as (B,C,N), N = H W;   G(x) = F F^T / (N C);   D = G(x) - G(y);   loss = mean |D| over the B C^2 entries
+ * x, y (B,C,N) contiguous, one storage type, read as stored: float16 / bfloat16 products are exact in the float32
+ * accumulators of the matrix cores, G(x) and G(y) are summed separately and in the same order (x == y gives D = 0 and
+ * loss = 0 exactly), scaled and subtracted in float32.  `diff`: D (B,C,C) float32, fully overwritten, symmetric bit for
+ * bit.  `loss`: ONE device scalar, float32.  `workspace`: gfla_gram_l1_workspace_bytes(B, C, N) bytes, 16-byte aligned,
+ * uninitialised (partial tiles of the chunks N is split into, and the per-workgroup sums of |D|).
+ * Backward: grad_feat = (negate ? -1 : +1) grad_loss 2 / (B C^3 N) sign(D) feat, in feat's storage type, fully
+ * overwritten, rounded once at the store; negate = 0 for d/dx (feat = x), 1 for d/dy (feat = y).  `grad_loss`: one DEVICE
+ * float32 scalar (no host sync).  sign(D) is exact in every storage type.
+ * No atomics: loss, D and gradients are bit-identical from call to call.  Any B, C, N >= 1 (ragged C and N are
+ * zero-filled); NULL -> -1; non-positive sizes -> -2; B > 16384, C > 4096 or N > 2^24 -> GFLA_ERR_UNSUPPORTED, nothing is
+ * launched.  gfla_gram_l1_workspace_bytes returns the same codes.  Additive: GFLA_ABI_VERSION stays 8. */
+int64_t gfla_gram_l1_workspace_bytes(int64_t B, int64_t C, int64_t N);
+int gfla_gram_l1_fwd_f32(const float *x, const float *y, void *workspace, float *diff, float *loss, int64_t B, int64_t C,
+                         int64_t N, gfla_stream_t stream);
+int gfla_gram_l1_fwd_f16(const uint16_t *x, const uint16_t *y, void *workspace, float *diff, float *loss, int64_t B,
+                         int64_t C, int64_t N, gfla_stream_t stream);
+int gfla_gram_l1_fwd_bf16(const uint16_t *x, const uint16_t *y, void *workspace, float *diff, float *loss, int64_t B,
+                          int64_t C, int64_t N, gfla_stream_t stream);
+int gfla_gram_l1_bwd_f32(const float *feat, const float *diff, const float *grad_loss, float *grad_feat, int64_t B,
+                         int64_t C, int64_t N, int negate, gfla_stream_t stream);
+int gfla_gram_l1_bwd_f16(const uint16_t *feat, const float *diff, const float *grad_loss, uint16_t *grad_feat, int64_t B,
+                         int64_t C, int64_t N, int negate, gfla_stream_t stream);
+int gfla_gram_l1_bwd_bf16(const uint16_t *feat, const float *diff, const float *grad_loss, uint16_t *grad_feat, int64_t B,
+                          int64_t C, int64_t N, int negate, gfla_stream_t stream);
 
 #ifdef __cplusplus
 }
