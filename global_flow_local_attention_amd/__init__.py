@@ -13,6 +13,7 @@ from .extractor_attn import (BlockExtractorUnfoldFunction, ExtractorAttn, FcTail
 from .losses import (AffineRegFunction, AffineRegularizationLoss, GramL1Function, MultiAffineRegularizationLoss,  # noqa: F401
                      PerceptualLoss, StyleContentLoss, StyleLoss, VGGLoss, gram_l1)
 from .correctness import CorrectnessMapFunction, MaxCosineFunction, PerceptualCorrectness, max_cosine_similarity  # noqa: F401
+from .flow_warp import BilinearSamplingBlock, FlowWarp, FlowWarpFunction, flow_warp  # noqa: F401
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401
 from .face_step import (DualStreamAttn, MaskBlendFunction, face_target_forward, generate_frames,  # noqa: F401

@@ -30,6 +30,8 @@ _SIGNATURES = {
     "gfla_local_attn_aggregate_fwd": [_ptr] * 5 + [_i64] * 6 + [_int, _int, _ptr],
     "gfla_local_attn_aggregate_bwd": [_ptr] * 7 + [_i64] * 6 + [_int, _int, _ptr],
     "gfla_local_attn_source_bwd": [_ptr] * 7 + [_i64] * 6 + [_int, _int, _ptr],
+    "gfla_flow_warp_fwd": [_ptr] * 3 + [_i64] * 6 + [ctypes.c_double] * 4 + [_ptr],
+    "gfla_flow_warp_bwd": [_ptr] * 5 + [_i64] * 6 + [ctypes.c_double] * 4 + [_ptr],
 }
 # entry points that exist in one precision only: full symbol name -> argument types
 _SINGLE = {

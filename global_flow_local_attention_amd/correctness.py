@@ -10,7 +10,8 @@ Reference: `PerceptualCorrectness` (model/networks/external_function.py:223-319)
 
 Step 1 is `max_cosine_similarity` below: one MFMA kernel in libgfla_hip.so that keeps the
 similarity matrix in registers (gfla_max_cosine_fwd_f32; float16 / bfloat16 features run on the 16-bit
-matrix cores, gfla_max_cosine_fwd_f16 / _bf16).  Step 2 uses this package's Resample2d.
+matrix cores, gfla_max_cosine_fwd_f16 / _bf16).  Step 2 uses this package's Resample2d, or its bilinear
+flow warp (flow_warp.py) for `use_bilinear_sampling=True`.
 """
 import torch
 import torch.nn as nn
@@ -18,6 +19,7 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from . import _lib
+from .flow_warp import IMPLS as WARP_IMPLS, flow_warp
 from .resample2d import Resample2d
 
 
@@ -152,11 +154,16 @@ class PerceptualCorrectness(nn.Module):
 
     `half_features`: what `calculate_loss` does with float16 / bfloat16 features (torch.autocast).  "float32" (default):
     features, flow and mask are up-cast and the float32 kernels run.  "native": the best match runs on the 16-bit
-    features as they are (16-bit matrix cores) and the target map is never up-cast; only the source map is, once, for the
-    warp, which stays in float32 with the float32 flow (a 16-bit flow of 32-64 px has steps of 0.25-0.5 px in bfloat16).
-    The loss map, the mask arithmetic and the returned loss are float32 either way.  "native" covers the path the trainer
-    uses (Resample2d warp, fused loss map, source and target of one 16-bit dtype); `use_bilinear_sampling`, `fused = False`
-    and mixed feature dtypes are evaluated as under "float32".
+    features as they are (16-bit matrix cores) and the target map is never up-cast.  The flow stays float32 (a 16-bit
+    flow of 32-64 px has steps of 0.25-0.5 px in bfloat16).  With the Resample2d warp the source map is up-cast once,
+    for the warp; with `use_bilinear_sampling=True` the flow-warp kernel reads the 16-bit source as stored and returns
+    the float32 warped map, so nothing is up-cast.  The loss map, the mask arithmetic and the returned loss are float32
+    either way.  "native" needs the fused loss map and source and target of one 16-bit dtype; `fused = False` and mixed
+    feature dtypes are evaluated as under "float32".
+
+    `warp_impl` (instance attribute, "auto" | "torch"): how `bilinear_warp` is evaluated.  "auto": GPU features go
+    through the kernels of csrc/flow_warp.hip in the "correctness" convention, anything else through torch.  "torch":
+    the normalised grid and `F.grid_sample`, as the reference writes it.
     """
 
     HALF_FEATURES = ("float32", "native")
@@ -177,6 +184,7 @@ class PerceptualCorrectness(nn.Module):
         if half_features not in self.HALF_FEATURES:
             raise ValueError("half_features: one of %s (got %r)" % (self.HALF_FEATURES, half_features))
         self.half_features = half_features
+        self.warp_impl = "auto"
 
     def __call__(self, target, source, flow_list, used_layers, mask=None, use_bilinear_sampling=False):
         if self.vgg is None:
@@ -198,7 +206,7 @@ class PerceptualCorrectness(nn.Module):
             # resample2d, the fused correctness map) and returned in float32, as autocast returns losses
             with torch.autocast(device_type=target_feat.device.type, enabled=False):
                 if self.half_features == "native" and target_feat.dtype in half and \
-                        source_feat.dtype == target_feat.dtype and not use_bilinear_sampling and self.fused:
+                        source_feat.dtype == target_feat.dtype and self.fused:
                     return self._loss(flow.float(), target_feat, source_feat, None if mask is None else mask.float(),
                                       use_bilinear_sampling)
                 return self._loss(flow.float(), target_feat.float(), source_feat.float(),
@@ -230,8 +238,14 @@ class PerceptualCorrectness(nn.Module):
         return torch.sum(mask * (loss_map - floor)) / (torch.sum(mask) + self.eps)
 
     def bilinear_warp(self, source, flow):
-        """grid_sample alternative of the reference (:308-318), same normalisation of the flow."""
+        """grid_sample alternative of the reference (:308-318), same normalisation of the flow; (b, c, h*w)."""
         b, c, h, w = source.shape
+        if self.warp_impl not in WARP_IMPLS:
+            raise ValueError("warp_impl: one of %s (got %r)" % (WARP_IMPLS, self.warp_impl))
+        if self.warp_impl != "torch" and self.align_corners:
+            return flow_warp(source, flow, "correctness", self.warp_impl).view(b, c, -1)
+        if source.dtype != flow.dtype:
+            source = source.type_as(flow)
         xs = torch.arange(w, device=source.device).view(1, -1).expand(h, -1).type_as(source) / (w - 1)
         ys = torch.arange(h, device=source.device).view(-1, 1).expand(-1, w).type_as(source) / (h - 1)
         grid = 2 * torch.stack([xs, ys], dim=0).unsqueeze(0).expand(b, -1, -1, -1) - 1

@@ -43,7 +43,7 @@ def _bind_vgg(cls, vgg):
 
 
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
-            dual_stream_face=False, strict_mfma=None, vgg=None):
+            dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -65,7 +65,11 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     vgg: a feature extractor (image -> {layer name: feature map}, e.g. the reference's VGG19 with its weights loaded).  When
     given, the reference's external_function.VGGLoss / StyleLoss / PerceptualLoss are replaced by this package's (losses.py:
     the Gram term on csrc/gram_l1.hip instead of bmm), constructed around it; imports the reference's external_function
-    module.  None (the default) leaves them alone."""
+    module.  None (the default) leaves them alone.
+
+    bilinear_sampling_block: True replaces the reference's base_function.BilinearSamplingBlock by this package's
+    (flow_warp.py: the warp on csrc/flow_warp.hip instead of a normalised grid and grid_sample; it also drops the
+    reference's unconditional `.cuda()`).  False (the default) leaves the reference's class alone."""
     from . import extractor_attn as _ea
     if strict_mfma is None and allow_vendor_fallback is not None:
         strict_mfma = not allow_vendor_fallback
@@ -109,6 +113,9 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
         from .face_step import patch_reference_face_target_net
         generator = importlib.import_module("model.networks.generator")
         patch_reference_face_target_net(generator.FaceTargetNet)
+    if base_function is not None and bilinear_sampling_block:
+        from .flow_warp import BilinearSamplingBlock
+        base_function.BilinearSamplingBlock = BilinearSamplingBlock
     if vgg is not None:
         from . import losses
         external_function = importlib.import_module("model.networks.external_function")

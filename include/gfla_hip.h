@@ -60,8 +60,8 @@ typedef void *gfla_stream_t; /* hipStream_t */
  *   8: round 6 (arithmetic mode 5 of gfla_fc_*: Winograd domain with two-term f16 operands on the f16 matrix cores,
  *      csrc/fc_wino16.hip; path ids 18 / 19; tuning keys 43, 46, 49, 52); float16 storage (the _f16 entry points,
  *      gfla_fc_forward_f16, gfla_convert_multi flags 2 / 3, path id 21) only ADDS symbols and ids and keeps 8; so do
- *      gfla_max_cosine_fwd_f16 / _bf16, gfla_correctness_map_{fwd,bwd}_f16 / _bf16, gfla_affine_reg_* and
- *      gfla_gram_l1_* */
+ *      gfla_max_cosine_fwd_f16 / _bf16, gfla_correctness_map_{fwd,bwd}_f16 / _bf16, gfla_affine_reg_*,
+ *      gfla_gram_l1_* and gfla_flow_warp_* */
 #define GFLA_ABI_VERSION 8
 int gfla_abi_version(void);
 const char *gfla_status_string(int status);
@@ -679,6 +679,43 @@ int gfla_gram_l1_bwd_f16(const uint16_t *feat, const float *diff, const float *g
                          int64_t C, int64_t N, int negate, gfla_stream_t stream);
 int gfla_gram_l1_bwd_bf16(const uint16_t *feat, const float *diff, const float *grad_loss, uint16_t *grad_feat, int64_t B,
                           int64_t C, int64_t N, int negate, gfla_stream_t stream);
+
+/* ---- bilinear flow warp (external_function.py:309-319, base_function.py:490-506, poseflownet_model.py:86-103;
+ * csrc/flow_warp.hip) --------------------------------------------------------------------------------------------------
+ *   out[b,c,y,x] = bilinear(source[b,c], ix, iy),   ix = (x + gx flow_x) mx,   iy = (y + gy flow_y) my   (source pixels)
+ * with zero padding: a corner outside the map contributes 0 -- grid_sample(bilinear, zeros, align_corners=True) without
+ * the normalised grid.  The four scalars select the reference's convention (csrc/flow_warp.hip lists the three).
+ * source (B,C,Hs,Ws) contiguous, read in its storage type; flow (B,2,H,W), out (B,C,H,W) and grad_out float32 (float64
+ * for _f64).  Position, weights and interpolation run in the flow's precision; out is rounded once, at the store.
+ * Backward: either output may be NULL.  grad_flow (B,2,H,W), fully overwritten: one writer per element, the sum over
+ * channels in a fixed order inside the workgroup (float64), no atomics, bit-identical from call to call.  grad_source
+ * (B,C,Hs,Ws) in the FLOW's precision (float32 for 16-bit sources: the caller rounds it to the storage type once): the
+ * entry point zero-fills it itself and accumulates with float atomics -- the one output that is not bit-reproducible.
+ * NULL -> -1; non-positive sizes -> -2; Hs Ws, H W or the number of workgroups (B ceil(H W / 64) ceil(C / 32)) beyond
+ * 2^31 - 1 -> GFLA_ERR_UNSUPPORTED, nothing is launched.  Additive: GFLA_ABI_VERSION stays 8. */
+int gfla_flow_warp_fwd_f32(const float *source, const float *flow, float *out, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
+                           int64_t H, int64_t W, double gx, double gy, double mx, double my, gfla_stream_t stream);
+int gfla_flow_warp_fwd_f64(const double *source, const double *flow, double *out, int64_t B, int64_t C, int64_t Hs,
+                           int64_t Ws, int64_t H, int64_t W, double gx, double gy, double mx, double my,
+                           gfla_stream_t stream);
+int gfla_flow_warp_fwd_f16(const uint16_t *source, const float *flow, float *out, int64_t B, int64_t C, int64_t Hs,
+                           int64_t Ws, int64_t H, int64_t W, double gx, double gy, double mx, double my,
+                           gfla_stream_t stream);
+int gfla_flow_warp_fwd_bf16(const uint16_t *source, const float *flow, float *out, int64_t B, int64_t C, int64_t Hs,
+                            int64_t Ws, int64_t H, int64_t W, double gx, double gy, double mx, double my,
+                            gfla_stream_t stream);
+int gfla_flow_warp_bwd_f32(const float *source, const float *flow, const float *grad_out, float *grad_source,
+                           float *grad_flow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, double gx,
+                           double gy, double mx, double my, gfla_stream_t stream);
+int gfla_flow_warp_bwd_f64(const double *source, const double *flow, const double *grad_out, double *grad_source,
+                           double *grad_flow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, double gx,
+                           double gy, double mx, double my, gfla_stream_t stream);
+int gfla_flow_warp_bwd_f16(const uint16_t *source, const float *flow, const float *grad_out, float *grad_source,
+                           float *grad_flow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, double gx,
+                           double gy, double mx, double my, gfla_stream_t stream);
+int gfla_flow_warp_bwd_bf16(const uint16_t *source, const float *flow, const float *grad_out, float *grad_source,
+                            float *grad_flow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, double gx,
+                            double gy, double mx, double my, gfla_stream_t stream);
 
 #ifdef __cplusplus
 }
