@@ -57,6 +57,7 @@ __device__ __forceinline__ Corner corners(float fx, float fy, int x, int y, int 
 }
 
 __device__ __forceinline__ float lrelu_f(float v, float slope) { return v > 0.f ? v : v * slope; }
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 
 __device__ __forceinline__ float wave_sum_f(float v) {
 #pragma unroll
@@ -92,37 +93,74 @@ __global__ __launch_bounds__(256) void fc_tail_fwd_kernel(const float *__restric
   float *tile = reinterpret_cast<float *>(gfla_smem);  // [64][129] hidden pre-activations
   float *w_s = tile + kSmpPix * kSmpPitch;             // [128][KK]
   float *red = tile;                                   // [4][KK][64] partial logits, once the tile is dead
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int HW = H * W;
   const int64_t b = blockIdx.y;
   const int p0 = blockIdx.x * kSmpPix;
-  for (int i = t; i < kFcHidden * KK; i += 256) {
-    const int o = i / KK, q = i - o * KK;
-    w_s[i] = w1[q * kFcHidden + o];
+  // Phase A used to be sixteen branches per wave, each a chain of two dependent global round trips (flow -> corner rows):
+  // 32 round trips in a row, and nothing of the next position in flight.  Now a wave requests the flows of its 16 CONSECUTIVE
+  // positions at once (lane i holds position i's), the W1 values it will stage, and then the ten rows (4 corners + the target
+  // map, two channel halves) of EIGHT positions before it uses the first: four round trips per wave.  Indices are clamped
+  // for the request and the position mask is applied at the use.
+  constexpr int kWalk = kSmpPix / 4, kBatch = 8;
+  constexpr int NW = (kFcHidden * KK + 255) / 256;
+  const int pw0 = p0 + wave * kWalk;
+  const int nwalk = max(0, min(kWalk, HW - pw0));
+  float fx_l = 0.f, fy_l = 0.f;
+  if ((lane & (kWalk - 1)) < nwalk) {
+    fx_l = flow[(b * 2 + 0) * HW + pw0 + (lane & (kWalk - 1))];
+    fy_l = flow[(b * 2 + 1) * HW + pw0 + (lane & (kWalk - 1))];
   }
-  // phase A: lanes = hidden channels (lane, lane + 64); a wave walks 16 positions
+  float wq[NW];
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
+    const int i = min(t + 256 * j, kFcHidden * KK - 1);
+    const int o = i / KK, q = i - o * KK;
+    wq[j] = w1[q * kFcHidden + o];
+  }
+  // lanes = hidden channels (lane, lane + 64)
   const float *gsb = gs + b * gs_bs, *gtb = gt + b * gt_bs;
   const float bias0 = b0 ? b0[lane] : 0.f, bias1 = b0 ? b0[lane + 64] : 0.f;
-#pragma unroll 4
-  for (int it = 0; it < kSmpPix / 4; ++it) {
-    const int pp = wave + 4 * it, p = p0 + pp;
-    float h0 = 0.f, h1 = 0.f;
-    if (p < HW) {
+#pragma unroll
+  for (int it0 = 0; it0 < kWalk; it0 += kBatch) {
+    float g[kBatch][10], wt[kBatch][4];
+#pragma unroll
+    for (int j = 0; j < kBatch; ++j) {
+      const int it = it0 + j;
+      const int p = min(pw0 + it, HW - 1);
       const int y = p / W, x = p - y * W;
-      const float fx = flow[(b * 2 + 0) * HW + p], fy = flow[(b * 2 + 1) * HW + p];
+      const float fx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fx_l), it));
+      const float fy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fy_l), it));
       const Corner c = corners<KS>(fx, fy, x, y, H, W, wps);
       const float *g00 = gsb + (int64_t)c.i00 * kFcHidden + lane, *g01 = gsb + (int64_t)c.i01 * kFcHidden + lane;
       const float *g10 = gsb + (int64_t)c.i10 * kFcHidden + lane, *g11 = gsb + (int64_t)c.i11 * kFcHidden + lane;
       const float *tp = gtb + (int64_t)(y * wpt + x) * kFcHidden + lane;
-      const float wa = c.xl * c.yt, wb = c.xr * c.yt, wc = c.xl * c.yb, wd = c.xr * c.yb;
-      h0 = bias0 + tp[0] + (wa * g00[0] + wb * g01[0] + wc * g10[0] + wd * g11[0]);
-      h1 = bias1 + tp[64] + (wa * g00[64] + wb * g01[64] + wc * g10[64] + wd * g11[64]);
-      float *hp = hid + (b * HW + p) * kFcHidden + lane;
-      hp[0] = h0;
-      hp[64] = h1;
+      wt[j][0] = c.xl * c.yt, wt[j][1] = c.xr * c.yt, wt[j][2] = c.xl * c.yb, wt[j][3] = c.xr * c.yb;
+      g[j][0] = g00[0], g[j][1] = g01[0], g[j][2] = g10[0], g[j][3] = g11[0];
+      g[j][4] = g00[64], g[j][5] = g01[64], g[j][6] = g10[64], g[j][7] = g11[64];
+      g[j][8] = tp[0], g[j][9] = tp[64];
     }
-    tile[pp * kSmpPitch + lane] = h0;
-    tile[pp * kSmpPitch + lane + 64] = h1;
+#pragma unroll
+    for (int j = 0; j < kBatch; ++j) {
+      const int it = it0 + j, pp = wave * kWalk + it;
+      const float wa = wt[j][0], wb = wt[j][1], wc = wt[j][2], wd = wt[j][3];
+      float h0 = bias0 + g[j][8] + (wa * g[j][0] + wb * g[j][1] + wc * g[j][2] + wd * g[j][3]);
+      float h1 = bias1 + g[j][9] + (wa * g[j][4] + wb * g[j][5] + wc * g[j][6] + wd * g[j][7]);
+      if (it < nwalk) {
+        float *hp = hid + (b * HW + pw0 + it) * kFcHidden + lane;
+        hp[0] = h0;
+        hp[64] = h1;
+      } else {
+        h0 = h1 = 0.f;
+      }
+      tile[pp * kSmpPitch + lane] = h0;
+      tile[pp * kSmpPitch + lane + 64] = h1;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
+    const int i = t + 256 * j;
+    if (i < kFcHidden * KK) w_s[i] = wq[j];
   }
   __syncthreads();
   // phase B: lanes = positions, wave s takes hidden channels s, s+4, ...
@@ -169,22 +207,46 @@ __global__ __launch_bounds__(256) void fc_tail_bwd_kernel(
   const int HW = H * W;
   const int64_t b = blockIdx.y;
   const int p0 = blockIdx.x * kSmpPix;
-  for (int i = t; i < kFcHidden * KK; i += 256) {
+  // W1, the tile of hidden pre-activations and this lane's d logits are requested together: one round trip (the W1 loop
+  // used to wait for each of its 13 loads before it issued the next, and d logits were requested behind the barrier)
+  constexpr int NW = (kFcHidden * KK + 255) / 256;
+  float wq[NW];
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
+    const int i = min(t + 256 * j, kFcHidden * KK - 1);
     const int o = i / KK, q = i - o * KK;
-    w_s[i] = w1[q * kFcHidden + o];
+    wq[j] = w1[q * kFcHidden + o];
   }
-  for (int i = t; i < kSmpPix * kFcHidden; i += 256) {
-    const int pp = i >> 7, n = i & 127;
-    tile[pp * kSmpPitch + n] = p0 + pp < HW ? hid[(b * HW + p0 + pp) * kFcHidden + n] : 0.f;
+  float gl[KK];
+  {
+    const float *glp = g_logits + b * (int64_t)KK * HW + min(p0 + lane, HW - 1);
+#pragma unroll
+    for (int q = 0; q < KK; ++q) gl[q] = glp[(int64_t)q * HW];
+  }
+  float4 hq[kSmpPix * kFcHidden / 4 / 256];   // 16-byte pieces of the (64 x 128) tile; rows past the map are masked at the use
+#pragma unroll
+  for (int j = 0; j < kSmpPix * kFcHidden / 4 / 256; ++j) {
+    const int i = t + 256 * j, pp = i >> 5, n4 = i & 31;
+    hq[j] = ld4(hid + (b * HW + min(p0 + pp, HW - 1)) * kFcHidden + 4 * n4);
+  }
+#pragma unroll
+  for (int j = 0; j < kSmpPix * kFcHidden / 4 / 256; ++j) {
+    const int i = t + 256 * j, pp = i >> 5, n4 = i & 31;
+    const bool in = p0 + pp < HW;
+    float *tp = tile + pp * kSmpPitch + 4 * n4;
+    tp[0] = in ? hq[j].x : 0.f, tp[1] = in ? hq[j].y : 0.f, tp[2] = in ? hq[j].z : 0.f, tp[3] = in ? hq[j].w : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
+    const int i = t + 256 * j;
+    if (i < kFcHidden * KK) w_s[i] = wq[j];
   }
   __syncthreads();
   {  // phase 1: lanes = positions: d hidden = (W1^T d logits) * lrelu'(hidden)
     const int p = p0 + lane;
     const bool live = p < HW;
-    float gl[KK];
-    const float *glp = g_logits + b * (int64_t)KK * HW + (live ? p : 0);
 #pragma unroll
-    for (int q = 0; q < KK; ++q) gl[q] = live ? glp[(int64_t)q * HW] : 0.f;
+    for (int q = 0; q < KK; ++q) gl[q] = live ? gl[q] : 0.f;
     uint32_t mx = 0;   // max |d hidden| of this lane (bit pattern: a NaN compares above every finite value)
 #pragma unroll 4
     for (int o = wave; o < kFcHidden; o += 4) {
@@ -243,7 +305,7 @@ __global__ __launch_bounds__(256) void fc_tail_bwd_kernel(
   };
   if (!zsb) {
     // The gradient map of Gs is somebody else's (fc_scatter_own_kernel): nothing is carried from position to position, so the
-    // corner values of FOUR positions are in flight at a time, and the flow gradients of the wave's 16 positions are
+    // corner values of EIGHT positions are in flight at a time, and the flow gradients of the wave's 16 positions are
     // collected in lanes 0-15 and leave through one store each (the read-modify-write of an accumulated gradient used to sit
     // in lane 63 of every iteration: a dependent global round trip per position, 16 in a row)
     float old_x = 0.f, old_y = 0.f, res_x = 0.f, res_y = 0.f;
@@ -251,23 +313,34 @@ __global__ __launch_bounds__(256) void fc_tail_bwd_kernel(
       old_x = gflow[(b * 2 + 0) * HW + pw0 + lane];
       old_y = gflow[(b * 2 + 1) * HW + pw0 + lane];
     }
-    for (int it0 = 0; it0 < nwalk; it0 += 4) {
-      Corner c4[4];
-      float g4[4][8];
+    // (the batch is requested branch-free, indices clamped, before its first use: with the requests inside issue()'s branch
+    // hipcc waited for each position's eight rows before it asked for the next one's -- 16 round trips in a row per wave;
+    // a call without a flow gradient requests them too: they are rows of the workspace, and that call is the rare one)
+    constexpr int kBatch = 8;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        issue(min(it0 + j, nwalk - 1));
-        c4[j] = cn;
+    for (int it0 = 0; it0 < kWalk; it0 += kBatch) {
+      if (it0 >= nwalk) break;
+      float cw[kBatch][4], g8[kBatch][8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) g4[j][i] = gn[i];
+      for (int j = 0; j < kBatch; ++j) {
+        const int it = it0 + j, p = min(pw0 + it, HW - 1);
+        const int y = p / W, x = p - y * W;
+        const float fx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fx_l), it));
+        const float fy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fy_l), it));
+        const Corner c = corners<KS>(fx, fy, x, y, H, W, wps, wpz);
+        cw[j][0] = c.xl, cw[j][1] = c.xr, cw[j][2] = c.yt, cw[j][3] = c.yb;
+        const float *g00 = gsb + (int64_t)c.i00 * kFcHidden + lane, *g01 = gsb + (int64_t)c.i01 * kFcHidden + lane;
+        const float *g10 = gsb + (int64_t)c.i10 * kFcHidden + lane, *g11 = gsb + (int64_t)c.i11 * kFcHidden + lane;
+        g8[j][0] = g00[0], g8[j][1] = g01[0], g8[j][2] = g10[0], g8[j][3] = g11[0];
+        g8[j][4] = g00[64], g8[j][5] = g01[64], g8[j][6] = g10[64], g8[j][7] = g11[64];
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < kBatch; ++j) {
         const int it = it0 + j;
         if (it >= nwalk) break;
         const int pp = wave * kWalk + it, p = p0 + pp;
-        const Corner &c = c4[j];
-        const float *g = g4[j];
+        const float xl = cw[j][0], xr = cw[j][1], yt = cw[j][2], yb = cw[j][3];
+        const float *g = g8[j];
         const float d0 = tile[pp * kSmpPitch + lane], d1 = tile[pp * kSmpPitch + lane + 64];
         s0 += d0;
         s1 += d1;
@@ -278,8 +351,8 @@ __global__ __launch_bounds__(256) void fc_tail_bwd_kernel(
           zp[64] = d1;
         }
         if (gflow) {
-          float gx = d0 * (c.yt * (g[1] - g[0]) + c.yb * (g[3] - g[2])) + d1 * (c.yt * (g[5] - g[4]) + c.yb * (g[7] - g[6]));
-          float gy = d0 * (c.xl * (g[2] - g[0]) + c.xr * (g[3] - g[1])) + d1 * (c.xl * (g[6] - g[4]) + c.xr * (g[7] - g[5]));
+          float gx = d0 * (yt * (g[1] - g[0]) + yb * (g[3] - g[2])) + d1 * (yt * (g[5] - g[4]) + yb * (g[7] - g[6]));
+          float gy = d0 * (xl * (g[2] - g[0]) + xr * (g[3] - g[1])) + d1 * (xl * (g[6] - g[4]) + xr * (g[7] - g[5]));
           gx = wave_sum_lane63(gx);
           gy = wave_sum_lane63(gy);
           const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gx), 63));
@@ -454,6 +527,7 @@ __global__ __launch_bounds__(kOwnThreads) void fc_scatter_own_kernel(
     for (int i = t; i < rows * Wo * (kFcHidden / 2); i += kOwnThreads) t2[i] = longlong2{0, 0};
   }
   if (t == 0) s_max = 0, s_total = 0, s_count = 0;
+  __syncthreads();   // (another wave's atomicAdd on s_total below must not precede the initialisation)
   const FixScale fs = fix_scale(*amax_d);
   const int npos = (HW + kOwnThreads - 1) / kOwnThreads;   // positions per thread: p = i * 512 + t
   // corner geometry of position i * 512 + t: block_extractor_kernel.cu:58-70 for the centre tap on the convolved map's
@@ -891,9 +965,162 @@ __global__ __launch_bounds__(256) void fc_fold_kernel(FoldJobs jobs, int nb0, in
   }
 }
 
+// The streaming form (C a multiple of 4, 16-byte aligned maps).  A workgroup owns R whole rows x 32 channels of one sample:
+//   * a (position, 32 channels) piece is ONE 128-byte line, read as eight 16-byte loads; a thread keeps kFoldU pieces in
+//     flight, and the channel groups of a row range are neighbouring workgroups (blockIdx.x), so the four quarters of a
+//     512-byte (position, C = 128) row are wanted at about the same time;
+//   * R is chosen so that R W floats are whole 128-byte lines (W = 44: R = 8, 1408 bytes = 11 lines; W = 22: R = 16): the R
+//     rows of a channel plane are contiguous in NCHW, so a plane piece leaves as full, line-aligned 16-byte stores.  The
+//     one-row kernel above ends every 176-byte (88-byte) row inside a line that ANOTHER workgroup completes later -- the
+//     pattern the store micro-benchmark prices at 3.2-3.8 TB/s against 5.5 for flat stores; round 6's
+//     multi-row form used R = 4 (704 bytes = 5.5 lines) and gave up the early request of the old values, which is kept here;
+//   * the sums are formed in the one-row kernel's order (centre + (ring in row-major order)): the results are bit-equal.
+constexpr int kFoldCG = 32;     // channels per workgroup
+constexpr int kFoldPos = 352;   // positions (R x W) per workgroup at most: 32 x 356 floats of LDS, three workgroups per CU
+constexpr int kFoldU = 4;       // 16-byte pieces a thread has in flight
+constexpr int kFoldOld4 = 12;   // 16-byte old values a thread requests up front (covers every tile of <= 352 positions)
+
+__global__ __launch_bounds__(256) void fc_fold_rows_kernel(FoldJobs jobs, int nb0, int C, int H, int W, int R, int pitch,
+                                                          int vec_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char gfla_smem[];
+  float *tile = reinterpret_cast<float *>(gfla_smem);  // [32][pitch]: channel-major, position r * W + x
+  const bool second = (int)blockIdx.z >= nb0;
+  const FoldJob &J = jobs.j[second ? 1 : 0];
+  const int Hp = J.Hp, Wp = J.Wp, pad_t = J.pad_t, pad_l = J.pad_l, accumulate = J.accumulate;
+  const int t = threadIdx.x;
+  const int r0 = blockIdx.y * R, npos = min(R, H - r0) * W;
+  const int c0 = blockIdx.x * kFoldCG, ncl = min(kFoldCG, C - c0), nc4 = ncl >> 2;
+  const int64_t b = (int)blockIdx.z - (second ? nb0 : 0);
+  const int64_t plane = (int64_t)H * W;
+  float *__restrict__ gbase = J.grad + ((b * C + c0) * H + r0) * (int64_t)W;   // channel cl of the tile: + cl * plane
+  const float *__restrict__ src = J.dxpad + b * J.dx_bs + c0;
+  const int n4row = npos >> 2, n4 = ncl * n4row;   // (vec_out: npos is a multiple of 4)
+  // the values this workgroup will add to are requested right behind the first centre pieces (ahead of them, the loop
+  // head's wait for the previous round's registers would wait for these too before the first piece is asked for)
+  const bool early = accumulate && vec_out && n4 <= kFoldOld4 * 256;
+  float4 old4[kFoldOld4];
+  // item i = (position i / 8, channel quad i % 8): the eight lanes of a position read its 128-byte line
+  const int nitems = npos * 8;
+  for (int base = 0; base < nitems; base += 256 * kFoldU) {
+    float4 acc[kFoldU];
+    int ys[kFoldU], xs[kFoldU];
+#pragma unroll
+    for (int u = 0; u < kFoldU; ++u) {   // the centre pieces: one round trip for all of them
+      const int i = min(base + t + 256 * u, nitems - 1);
+      const int pos = i >> 3, c4 = min(i & 7, nc4 - 1);
+      const int r = pos / W;
+      ys[u] = r0 + r, xs[u] = pos - r * W;
+      acc[u] = ld4(src + (int64_t)((ys[u] + pad_t) * Wp + xs[u] + pad_l) * C + 4 * c4);
+    }
+    if (early && base == 0) {
+#pragma unroll
+      for (int u = 0; u < kFoldOld4; ++u) {
+        const int j = min(t + 256 * u, n4 - 1);
+        const int cl = j / n4row, q = j - cl * n4row;
+        old4[u] = ld4(gbase + cl * plane + 4 * q);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kFoldU; ++u) {
+      const int i = base + t + 256 * u;
+      if (i >= nitems) break;
+      const int pos = i >> 3, c4 = i & 7;
+      if (c4 >= nc4) continue;
+      const int y = ys[u], x = xs[u];
+      if (y == 0 || y == H - 1 || x == 0 || x == W - 1) {  // border: the padded positions that clamp onto (y, x)
+        const int x0 = x == 0 ? 0 : x + pad_l, x1 = x == W - 1 ? Wp - 1 : x + pad_l;
+        const int y0 = y == 0 ? 0 : y + pad_t, y1 = y == H - 1 ? Hp - 1 : y + pad_t;
+        const int n = (y1 - y0 + 1) * (x1 - x0 + 1);
+        float4 extra = make_float4(0.f, 0.f, 0.f, 0.f);
+        int yy = y0, xx = x0;
+#pragma unroll 5
+        for (int e = 0; e < n; ++e) {   // (the centre is read again and left out of the sum: five requests fly together)
+          const float4 v = ld4(src + (int64_t)(yy * Wp + xx) * C + 4 * c4);
+          const bool ring = yy != y + pad_t || xx != x + pad_l;
+          extra.x += ring ? v.x : 0.f, extra.y += ring ? v.y : 0.f, extra.z += ring ? v.z : 0.f, extra.w += ring ? v.w : 0.f;
+          if (++xx > x1) xx = x0, ++yy;
+        }
+        acc[u].x += extra.x, acc[u].y += extra.y, acc[u].z += extra.z, acc[u].w += extra.w;
+      }
+      float *tp = tile + (4 * c4) * pitch + pos;
+      tp[0] = acc[u].x, tp[pitch] = acc[u].y, tp[2 * pitch] = acc[u].z, tp[3 * pitch] = acc[u].w;
+    }
+  }
+  __syncthreads();
+  if (vec_out) {   // channel cl: npos contiguous floats, 16-byte aligned
+    if (early || !accumulate) {
+#pragma unroll
+      for (int u = 0; u < kFoldOld4; ++u) {
+        const int j = t + 256 * u;
+        if (j >= n4) break;
+        const int cl = j / n4row, q = j - cl * n4row;
+        float4 v = ld4(tile + cl * pitch + 4 * q);
+        if (early) v.x = old4[u].x + v.x, v.y = old4[u].y + v.y, v.z = old4[u].z + v.z, v.w = old4[u].w + v.w;
+        *reinterpret_cast<float4 *>(gbase + cl * plane + 4 * q) = v;
+      }
+      for (int j = t + 256 * kFoldOld4; j < n4; j += 256) {   // (not accumulating, one very wide row)
+        const int cl = j / n4row, q = j - cl * n4row;
+        *reinterpret_cast<float4 *>(gbase + cl * plane + 4 * q) = ld4(tile + cl * pitch + 4 * q);
+      }
+      return;
+    }
+    for (int j = t; j < n4; j += 256) {   // accumulating into one very wide row
+      const int cl = j / n4row, q = j - cl * n4row;
+      float4 *g = reinterpret_cast<float4 *>(gbase + cl * plane + 4 * q);
+      const float4 o = *g, v = ld4(tile + cl * pitch + 4 * q);
+      *g = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
+    }
+    return;
+  }
+  // planes whose pieces are not 16-byte aligned: four elements per thread and pass, their old values one round trip
+  const int n1 = ncl * npos;
+  for (int base = 0; base < n1; base += 4 * 256) {
+    float *g[4];
+    float v[4], o[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = min(base + t + 256 * u, n1 - 1);
+      const int cl = j / npos, e = j - cl * npos;
+      g[u] = gbase + cl * plane + e;
+      v[u] = tile[cl * pitch + e];
+      o[u] = accumulate ? *g[u] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (base + t + 256 * u < n1) *g[u] = accumulate ? o[u] + v[u] : v[u];
+  }
+}
+
+// rows per workgroup of the streaming form: R W floats are whole 128-byte lines where that fits, else whole 16-byte pieces
+static int fc_fold_rows(int H, int W) {
+  const int maxr = std::max(1, std::min(H, kFoldPos / W));
+  for (int m = 32; m >= 4; m /= 8) {
+    int g = W, r = m;   // gcd(W, m)
+    while (r) { const int q = g % r; g = r, r = q; }
+    const int step = m / g;
+    if (step <= maxr) return maxr / step * step;
+  }
+  return maxr;
+}
+
 static int fc_fold_launch(const FoldJobs &jobs, int njobs, int64_t B, int C, int H, int W, hipStream_t stream) {
   if (B <= 0 || njobs <= 0) return GFLA_OK;
   if (njobs * B > 65535 || ceil_div(C, 64) > 65535 || (int64_t)64 * (W + 1) * 4 > 64 * 1024) return GFLA_ERR_UNSUPPORTED;
+  bool stream16 = C % 4 == 0, vec_out = ((int64_t)H * W) % 4 == 0;
+  for (int j = 0; j < njobs; ++j) {
+    stream16 = stream16 && reinterpret_cast<uintptr_t>(jobs.j[j].dxpad) % 16 == 0 && jobs.j[j].dx_bs % 4 == 0;
+    vec_out = vec_out && reinterpret_cast<uintptr_t>(jobs.j[j].grad) % 16 == 0;
+  }
+  if (stream16) {
+    const int R = fc_fold_rows(H, W);
+    const int pitch = (int)round_up((int64_t)std::min(R, H) * W, 16) + 4;   // a multiple of 4: 16-byte LDS reads
+    vec_out = vec_out && (R * W) % 4 == 0;
+    if (ceil_div(H, R) > 65535) return GFLA_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)ceil_div(C, kFoldCG), (unsigned)ceil_div(H, R), (unsigned)(njobs * B));
+    fc_fold_rows_kernel<<<grid, 256, (unsigned)(kFoldCG * pitch * sizeof(float)), stream>>>(jobs, (int)B, C, H, W, R, pitch,
+                                                                                            vec_out ? 1 : 0);
+    return launch_status();
+  }
   const dim3 grid((unsigned)H, (unsigned)ceil_div(C, 64), (unsigned)(njobs * B));
   fc_fold_kernel<<<grid, 256, (unsigned)(64 * (W + 1) * sizeof(float)), stream>>>(jobs, (int)B, C, H, W);
   return launch_status();
