@@ -98,6 +98,22 @@ _SINGLE = {
     "gfla_gram_l1_bwd_f32": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
     "gfla_gram_l1_bwd_f16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
     "gfla_gram_l1_bwd_bf16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
+    "gfla_conv3x3_packed_bytes": [_i64, _i64, _int, _int],
+    "gfla_conv3x3_relu_fwd_f32": [_ptr] * 4 + [_i64] * 5 + [_ptr],
+    "gfla_conv3x3_relu_bwd_data_f32": [_ptr] * 4 + [_i64] * 5 + [_ptr],
+    "gfla_conv3x3_pack_weights_f32": [_ptr, _int, _ptr, _i64, _i64, _int, _ptr],
+    "gfla_maxpool2x2_fwd_f32": [_ptr] * 2 + [_i64] * 4 + [_ptr],
+    "gfla_maxpool2x2_bwd_f32": [_ptr] * 3 + [_i64] * 4 + [_ptr],
+    "gfla_conv3x3_relu_fwd_f16": [_ptr] * 4 + [_i64] * 5 + [_ptr],
+    "gfla_conv3x3_relu_bwd_data_f16": [_ptr] * 4 + [_i64] * 5 + [_ptr],
+    "gfla_conv3x3_pack_weights_f16": [_ptr, _int, _ptr, _i64, _i64, _int, _ptr],
+    "gfla_maxpool2x2_fwd_f16": [_ptr] * 2 + [_i64] * 4 + [_ptr],
+    "gfla_maxpool2x2_bwd_f16": [_ptr] * 3 + [_i64] * 4 + [_ptr],
+    "gfla_conv3x3_relu_fwd_bf16": [_ptr] * 4 + [_i64] * 5 + [_ptr],
+    "gfla_conv3x3_relu_bwd_data_bf16": [_ptr] * 4 + [_i64] * 5 + [_ptr],
+    "gfla_conv3x3_pack_weights_bf16": [_ptr, _int, _ptr, _i64, _i64, _int, _ptr],
+    "gfla_maxpool2x2_fwd_bf16": [_ptr] * 2 + [_i64] * 4 + [_ptr],
+    "gfla_maxpool2x2_bwd_bf16": [_ptr] * 3 + [_i64] * 4 + [_ptr],
 }
 # bf16 and f16 storage exist for every entry point below; the backward ones return the reductions over channels (grad_flow,
 # grad_logits, grad_in2) in float32 (include/gfla_hip.h)

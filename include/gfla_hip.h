@@ -717,6 +717,46 @@ int gfla_flow_warp_bwd_bf16(const uint16_t *source, const float *flow, const flo
                             float *grad_flow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, double gx,
                             double gy, double mx, double my, gfla_stream_t stream);
 
+/* ---- VGG19 feature extractor (external_function.py:323-444): 3x3 convolution + bias + ReLU and 2x2 max pooling --------
+ * (csrc/conv3x3.hip, csrc/maxpool2x2.hip).  T: the storage type of the activations, float32 / float16 / bfloat16; sums are
+ * float32 on the matrix cores (v_mfma_f32_32x32x2_f32 / 32x32x16_f16 / 32x32x16_bf16), 16-bit results are rounded to
+ * nearest even once.  Stride 1, zero padding 1, NCHW contiguous, any B, Cin, Cout, H, W >= 1.
+ *   fwd:       y (B,Cout,H,W) = max(0, conv3x3(x (B,Cin,H,W), w) + bias); bias: Cout float32 values.
+ *   bwd_data:  grad_x (B,Cin,H,W) = conv3x3(grad_y [y > 0], w mirrored and transposed); y is the saved forward output.
+ *              The weights are frozen in the reference: there is no weight gradient.
+ *   `packed`:  gfla_conv3x3_packed_bytes(Cout, Cin, layout, sizeof(T)) bytes, 16-byte aligned, written by
+ *              gfla_conv3x3_pack_weights_<T> from w (Cout,Cin,3,3) stored as src_type 0 float32 / 1 float16 / 2 bfloat16
+ *              and rounded once to T: [tap][chunk of 32 / sizeof(T) reduction channels][channels padded to 32][chunk],
+ *              zero-padded.  layout 0 is what fwd reads, layout 1 (taps mirrored, Cin and Cout swapped) what bwd_data
+ *              reads.
+ * maxpool2x2: stride 2, floor mode, y (B,C,H/2,W/2); an odd last row / column is dropped and gets a zero gradient.  The
+ * backward finds the winner again from the saved input x (first maximum in scan order, as F.max_pool2d) and writes every
+ * element of grad_x exactly once.  H or W of 1 (empty output) is valid: fwd launches nothing, bwd writes zeros.
+ * No atomics: everything here is bit-identical from call to call.  NULL -> -1; non-positive sizes, layout or src_type out
+ * of range -> -2; H W > 2^31 - 1, B > 65535 or more than 65536 channels -> GFLA_ERR_UNSUPPORTED, nothing is launched.
+ * Additive: GFLA_ABI_VERSION stays 8. */
+int64_t gfla_conv3x3_packed_bytes(int64_t Cout, int64_t Cin, int layout, int elem_size);
+#define GFLA_DECL_CONV3X3(SFX, T)                                                                                        \
+  int gfla_conv3x3_relu_fwd_##SFX(const T *x, const void *packed, const float *bias, T *y, int64_t B, int64_t Cin,       \
+                                  int64_t Cout, int64_t H, int64_t W, gfla_stream_t stream);                             \
+  int gfla_conv3x3_relu_bwd_data_##SFX(const T *grad_y, const T *y, const void *packed_grad, T *grad_x, int64_t B,       \
+                                       int64_t Cin, int64_t Cout, int64_t H, int64_t W, gfla_stream_t stream);           \
+  int gfla_conv3x3_pack_weights_##SFX(const void *w, int src_type, void *packed, int64_t Cout, int64_t Cin, int layout,  \
+                                      gfla_stream_t stream);
+GFLA_DECL_CONV3X3(f32, float)
+GFLA_DECL_CONV3X3(f16, uint16_t)
+GFLA_DECL_CONV3X3(bf16, uint16_t)
+#undef GFLA_DECL_CONV3X3
+
+#define GFLA_DECL_MAXPOOL2X2(SFX, T)                                                                                     \
+  int gfla_maxpool2x2_fwd_##SFX(const T *x, T *y, int64_t B, int64_t C, int64_t H, int64_t W, gfla_stream_t stream);     \
+  int gfla_maxpool2x2_bwd_##SFX(const T *x, const T *grad_y, T *grad_x, int64_t B, int64_t C, int64_t H, int64_t W,      \
+                                gfla_stream_t stream);
+GFLA_DECL_MAXPOOL2X2(f32, float)
+GFLA_DECL_MAXPOOL2X2(f16, uint16_t)
+GFLA_DECL_MAXPOOL2X2(bf16, uint16_t)
+#undef GFLA_DECL_MAXPOOL2X2
+
 #ifdef __cplusplus
 }
 #endif
