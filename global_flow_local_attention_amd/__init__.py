@@ -15,6 +15,8 @@ from .losses import (AffineRegFunction, AffineRegularizationLoss, GramL1Function
 from .correctness import CorrectnessMapFunction, MaxCosineFunction, PerceptualCorrectness, max_cosine_similarity  # noqa: F401
 from .flow_warp import BilinearSamplingBlock, FlowWarp, FlowWarpFunction, flow_warp  # noqa: F401
 from .vgg import Conv3x3ReluFunction, MaxPool2x2Function, VGG19Features, conv3x3_relu, maxpool2x2  # noqa: F401
+from .instance_norm import (InstanceNormAct, InstanceNormActFunction, fuse_instance_norm_act,  # noqa: F401
+                            instance_norm_act)
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401
 from .face_step import (DualStreamAttn, MaskBlendFunction, face_target_forward, generate_frames,  # noqa: F401

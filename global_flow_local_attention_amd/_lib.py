@@ -32,6 +32,8 @@ _SIGNATURES = {
     "gfla_local_attn_source_bwd": [_ptr] * 7 + [_i64] * 6 + [_int, _int, _ptr],
     "gfla_flow_warp_fwd": [_ptr] * 3 + [_i64] * 6 + [ctypes.c_double] * 4 + [_ptr],
     "gfla_flow_warp_bwd": [_ptr] * 5 + [_i64] * 6 + [ctypes.c_double] * 4 + [_ptr],
+    "gfla_instance_norm_fwd": [_ptr] * 7 + [_i64] * 4 + [ctypes.c_double] * 2 + [_int, _ptr],
+    "gfla_instance_norm_bwd": [_ptr] * 10 + [_i64] * 4 + [ctypes.c_double, _int, _ptr],
 }
 # entry points that exist in one precision only: full symbol name -> argument types
 _SINGLE = {
@@ -114,6 +116,8 @@ _SINGLE = {
     "gfla_conv3x3_pack_weights_bf16": [_ptr, _int, _ptr, _i64, _i64, _int, _ptr],
     "gfla_maxpool2x2_fwd_bf16": [_ptr] * 2 + [_i64] * 4 + [_ptr],
     "gfla_maxpool2x2_bwd_bf16": [_ptr] * 3 + [_i64] * 4 + [_ptr],
+    "gfla_instance_norm_geometry": [_i64] * 4 + [_int, _int, _ptr],
+    "gfla_instance_norm_workspace_bytes": [_i64] * 4 + [_int],
 }
 # bf16 and f16 storage exist for every entry point below; the backward ones return the reductions over channels (grad_flow,
 # grad_logits, grad_in2) in float32 (include/gfla_hip.h)

@@ -43,7 +43,7 @@ def _bind_vgg(cls, vgg):
 
 
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
-            dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False):
+            dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False, fuse_instance_norm=False):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -69,7 +69,14 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
 
     bilinear_sampling_block: True replaces the reference's base_function.BilinearSamplingBlock by this package's
     (flow_warp.py: the warp on csrc/flow_warp.hip instead of a normalised grid and grid_sample; it also drops the
-    reference's unconditional `.cuda()`).  False (the default) leaves the reference's class alone."""
+    reference's unconditional `.cuda()`).  False (the default) leaves the reference's class alone.
+
+    fuse_instance_norm: True wraps the constructors of the reference's base_function block classes that build a
+    `norm_layer(C) -> nonlinearity` sequence (EncoderBlock, ResBlock, ResBlockDecoder, ResBlockEncoder and every other
+    class there that takes `norm_layer`), so that a network built AFTER install() has each nn.InstanceNorm2d + LeakyReLU /
+    ReLU pair as one InstanceNormAct (instance_norm.py: csrc/instance_norm.hip instead of batch_norm on a reshaped view
+    plus an activation launch).  Module indices, state-dict keys and the Parameter objects are unchanged, so reference
+    checkpoints load as before.  False (the default) leaves the classes alone."""
     from . import extractor_attn as _ea
     if strict_mfma is None and allow_vendor_fallback is not None:
         strict_mfma = not allow_vendor_fallback
@@ -116,6 +123,9 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     if base_function is not None and bilinear_sampling_block:
         from .flow_warp import BilinearSamplingBlock
         base_function.BilinearSamplingBlock = BilinearSamplingBlock
+    if base_function is not None and fuse_instance_norm:
+        from .instance_norm import patch_reference_blocks
+        patch_reference_blocks(base_function)
     if vgg is not None:
         from . import losses
         external_function = importlib.import_module("model.networks.external_function")

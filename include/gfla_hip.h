@@ -757,6 +757,50 @@ GFLA_DECL_MAXPOOL2X2(f16, uint16_t)
 GFLA_DECL_MAXPOOL2X2(bf16, uint16_t)
 #undef GFLA_DECL_MAXPOOL2X2
 
+/* ---- fused InstanceNorm2d (+ affine) + LeakyReLU / ReLU (base_function.py:334-556: the `norm_layer(C) -> nonlinearity`
+ * pair in front of every convolution of the generators' blocks; csrc/instance_norm.hip) ---------------------------------
+ * Per plane (b, c) of N = H W values, x (B,C,H,W) contiguous in its storage type, arithmetic in float32 (float64 for _f64):
+ *   mean, rstd = 1 / sqrt(biased variance + eps),  z = (x - mean) rstd gamma[c] + beta[c],  y = z > 0 ? z : slope z
+ * gamma / beta: C values in the ARITHMETIC type, or NULL (1 / 0).  act = 0: y = z (plain instance norm); slope = 0: ReLU.
+ * mean, rstd: B C values in the arithmetic type, written by fwd and read by bwd.  The variance is a centred sum of squares
+ * over values held in registers (Chan's update across the workgroups of a split plane), never E[x^2] - mean^2.
+ * bwd: z is recomputed from x (z == 0 takes the slope side); dx (B,C,H,W), dgamma (C), dbeta (C) may each be NULL and are
+ * fully overwritten otherwise.  Per-plane sums go to the workspace and are added over b in ascending order: no atomics,
+ * every result is bit-identical from call to call.
+ * `workspace`: gfla_instance_norm_workspace_bytes(B, C, H, W, sizeof(T)) bytes, 8-byte aligned, uninitialised, for fwd and
+ * for bwd.  x, y (x, dy, dx) must agree in their address modulo 16 (-3 otherwise; fresh allocations do).
+ * gfla_instance_norm_geometry: the launch plan, host only: out[0..6] = regime (0 wave per plane, 1 workgroup per plane, 2
+ * split plane), threads per workgroup, planes per workgroup, workgroups per plane, values per thread, LDS bytes, workgroups
+ * per launch.  It depends on (B C, H W, elem_size) only.
+ * NULL -> -1; non-positive sizes, H W == 1, elem_size not 2 / 4 / 8 -> -2; H W or B C beyond 2^31 - 1, more than 4096
+ * workgroups per plane -> GFLA_ERR_UNSUPPORTED, nothing is launched.  Additive: GFLA_ABI_VERSION stays 8. */
+int gfla_instance_norm_geometry(int64_t B, int64_t C, int64_t H, int64_t W, int elem_size, int is_backward, int64_t *out);
+int64_t gfla_instance_norm_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int elem_size);
+int gfla_instance_norm_fwd_f32(const float *x, const float *gamma, const float *beta, float *y, float *mean, float *rstd, void *workspace,
+                               int64_t B, int64_t C, int64_t H, int64_t W, double eps, double slope, int act,
+                               gfla_stream_t stream);
+int gfla_instance_norm_bwd_f32(const float *x, const float *dy, const float *gamma, const float *beta, const float *mean, const float *rstd,
+                               float *dx, float *dgamma, float *dbeta, void *workspace, int64_t B, int64_t C, int64_t H, int64_t W,
+                               double slope, int act, gfla_stream_t stream);
+int gfla_instance_norm_fwd_f64(const double *x, const double *gamma, const double *beta, double *y, double *mean, double *rstd, void *workspace,
+                               int64_t B, int64_t C, int64_t H, int64_t W, double eps, double slope, int act,
+                               gfla_stream_t stream);
+int gfla_instance_norm_bwd_f64(const double *x, const double *dy, const double *gamma, const double *beta, const double *mean, const double *rstd,
+                               double *dx, double *dgamma, double *dbeta, void *workspace, int64_t B, int64_t C, int64_t H, int64_t W,
+                               double slope, int act, gfla_stream_t stream);
+int gfla_instance_norm_fwd_f16(const uint16_t *x, const float *gamma, const float *beta, uint16_t *y, float *mean, float *rstd, void *workspace,
+                               int64_t B, int64_t C, int64_t H, int64_t W, double eps, double slope, int act,
+                               gfla_stream_t stream);
+int gfla_instance_norm_bwd_f16(const uint16_t *x, const uint16_t *dy, const float *gamma, const float *beta, const float *mean, const float *rstd,
+                               uint16_t *dx, float *dgamma, float *dbeta, void *workspace, int64_t B, int64_t C, int64_t H, int64_t W,
+                               double slope, int act, gfla_stream_t stream);
+int gfla_instance_norm_fwd_bf16(const uint16_t *x, const float *gamma, const float *beta, uint16_t *y, float *mean, float *rstd, void *workspace,
+                               int64_t B, int64_t C, int64_t H, int64_t W, double eps, double slope, int act,
+                               gfla_stream_t stream);
+int gfla_instance_norm_bwd_bf16(const uint16_t *x, const uint16_t *dy, const float *gamma, const float *beta, const float *mean, const float *rstd,
+                               uint16_t *dx, float *dgamma, float *dbeta, void *workspace, int64_t B, int64_t C, int64_t H, int64_t W,
+                               double slope, int act, gfla_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
