@@ -17,6 +17,8 @@ from .flow_warp import BilinearSamplingBlock, FlowWarp, FlowWarpFunction, flow_w
 from .vgg import Conv3x3ReluFunction, MaxPool2x2Function, VGG19Features, conv3x3_relu, maxpool2x2  # noqa: F401
 from .instance_norm import (InstanceNormAct, InstanceNormActFunction, fuse_instance_norm_act,  # noqa: F401
                             instance_norm_act)
+from .head_conv import (HeadConv3x3, HeadConv3x3Function, flow_mask_heads, fuse_output_heads, head_conv3x3,  # noqa: F401
+                        patch_reference_flow_heads, torch_head_conv3x3)
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401
 from .face_step import (DualStreamAttn, MaskBlendFunction, face_target_forward, generate_frames,  # noqa: F401

@@ -118,6 +118,14 @@ _SINGLE = {
     "gfla_maxpool2x2_bwd_bf16": [_ptr] * 3 + [_i64] * 4 + [_ptr],
     "gfla_instance_norm_geometry": [_i64] * 4 + [_int, _int, _ptr],
     "gfla_instance_norm_workspace_bytes": [_i64] * 4 + [_int],
+    "gfla_head_conv3x3_workspace_bytes": [_i64] * 5 + [_int],
+    "gfla_head_conv3x3_geometry": [_i64] * 5 + [_int, _ptr],
+    "gfla_head_conv3x3_fwd_f32": [_ptr] * 5 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
+    "gfla_head_conv3x3_fwd_f16": [_ptr] * 5 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
+    "gfla_head_conv3x3_fwd_bf16": [_ptr] * 5 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
+    "gfla_head_conv3x3_bwd_f32": [_ptr] * 10 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
+    "gfla_head_conv3x3_bwd_f16": [_ptr] * 10 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
+    "gfla_head_conv3x3_bwd_bf16": [_ptr] * 10 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
 }
 # bf16 and f16 storage exist for every entry point below; the backward ones return the reductions over channels (grad_flow,
 # grad_logits, grad_in2) in float32 (include/gfla_hip.h)

@@ -43,7 +43,8 @@ def _bind_vgg(cls, vgg):
 
 
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
-            dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False, fuse_instance_norm=False):
+            dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False, fuse_instance_norm=False,
+            fuse_heads=False):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -76,7 +77,14 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     class there that takes `norm_layer`), so that a network built AFTER install() has each nn.InstanceNorm2d + LeakyReLU /
     ReLU pair as one InstanceNormAct (instance_norm.py: csrc/instance_norm.hip instead of batch_norm on a reshaped view
     plus an activation launch).  Module indices, state-dict keys and the Parameter objects are unchanged, so reference
-    checkpoints load as before.  False (the default) leaves the classes alone."""
+    checkpoints load as before.  False (the default) leaves the classes alone.
+
+    fuse_heads: True (or "auto" / "torch", the `impl` of head_conv.py) closes the generators' tails on csrc/head_conv3x3.hip:
+    the constructor of base_function.Output is wrapped so that an image head built AFTER install() is one HeadConv3x3
+    (LeakyReLU -> ReflectionPad2d(1) -> Conv2d(ngf, 3, 3) -> Tanh; state-dict keys `conv1.*` and `model.2.*` and the
+    Parameter objects unchanged), and `attn_output` of PoseFlowNet / FaceFlowNet / ShapeNetFlowNet computes the flow field
+    and its sigmoid mask in one launch (head_conv.flow_mask_heads).  Imports the reference's generator module.  Heads built
+    with spectral norm or coordinate convolutions keep the reference's modules.  False (the default) changes nothing."""
     from . import extractor_attn as _ea
     if strict_mfma is None and allow_vendor_fallback is not None:
         strict_mfma = not allow_vendor_fallback
@@ -126,6 +134,11 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     if base_function is not None and fuse_instance_norm:
         from .instance_norm import patch_reference_blocks
         patch_reference_blocks(base_function)
+    if base_function is not None and fuse_heads:
+        from .head_conv import patch_reference_flow_heads, patch_reference_outputs
+        impl = fuse_heads if isinstance(fuse_heads, str) else "auto"
+        patch_reference_outputs(base_function, impl)
+        patch_reference_flow_heads(importlib.import_module("model.networks.generator"), impl)
     if vgg is not None:
         from . import losses
         external_function = importlib.import_module("model.networks.external_function")

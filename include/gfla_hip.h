@@ -801,6 +801,49 @@ int gfla_instance_norm_bwd_bf16(const uint16_t *x, const uint16_t *dy, const flo
                                uint16_t *dx, float *dgamma, float *dbeta, void *workspace, int64_t B, int64_t C, int64_t H, int64_t W,
                                double slope, int act, gfla_stream_t stream);
 
+/* ---- narrow 3x3 convolution heads with fused surroundings (base_function.py:650-670 `Output`; generator.py:203-209,
+ * 237-242 the flow and mask heads; csrc/head_conv3x3.hip) -----------------------------------------------------------------
+ *   a = pre_act ? leaky_relu(x, pre_slope) : x;  s = conv3x3(pad(a), w) + bias;  y_c = post_c(s_c)
+ * x (B,Cin,H,W) contiguous in its storage type T (float32 / float16 / bfloat16), read as stored; w (Cout,Cin,3,3) and bias
+ * (Cout, or NULL) are float32; sums are float32, a 16-bit result is rounded once.  Stride 1, one pixel of padding,
+ * pad_mode 0 zeros / 1 reflect (-1 -> 1, H -> H-2), output H x W.  1 <= Cout <= 8, any Cin, B.  post_c: bit c of tanh_mask
+ * -> tanh, bit c of sigmoid_mask -> sigmoid, neither -> identity.  Output channels [0, C0) go to y0 (B,C0,H,W), [C0, Cout)
+ * to y1 (B,Cout-C0,H,W); y1 may be NULL when C0 == Cout.  Neither the activated nor the padded map exists in memory.
+ * bwd: grad_y0 / grad_y1 may each be NULL (= zero); the post-activation's derivative is taken from the saved outputs y0 /
+ * y1 (1 - y^2, y (1 - y)).  grad_x (B,Cin,H,W) in T, grad_w (Cout,Cin,3,3) and grad_b (Cout) in float32 may each be NULL
+ * and are fully overwritten otherwise; x == 0 takes the slope side.  grad_x is owner-computes (reflect: the pad ring is
+ * folded onto rows / columns 1 and H-2 / W-2); grad_w / grad_b recompute a from x, leave per-slab partials in `workspace`
+ * (gfla_head_conv3x3_workspace_bytes bytes, 4-byte aligned, uninitialised; needed only with grad_w or grad_b) and a second
+ * launch adds them in slab order: no atomics, no memset, every result is bit-identical from call to call.
+ * gfla_head_conv3x3_geometry (host only): out[0..6] = tile width, tile height, threads per workgroup, tiles per plane of
+ * the forward (is_backward = 0) or the grad_x kernel (1); rows per slab, slabs, channel groups of the grad_w kernel.
+ * NULL -> -1; non-positive sizes, Cout > 8, C0 outside [1, Cout], mask bits beyond Cout or in both masks, pad_mode not
+ * 0 / 1, reflect with H or W < 2, elem_size not 2 / 4 -> -2; H W beyond 2^31 - 1 or more workgroups than a launch takes
+ * -> GFLA_ERR_UNSUPPORTED, nothing is launched.  Additive: GFLA_ABI_VERSION stays 8. */
+int64_t gfla_head_conv3x3_workspace_bytes(int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int elem_size);
+int gfla_head_conv3x3_geometry(int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int is_backward, int64_t *out);
+int gfla_head_conv3x3_fwd_f32(const float *x, const float *w, const float *bias, float *y0, float *y1, int64_t B, int64_t Cin,
+                               int64_t Cout, int64_t C0, int64_t H, int64_t W, int pad_mode, int pre_act, double pre_slope,
+                               int tanh_mask, int sigmoid_mask, gfla_stream_t stream);
+int gfla_head_conv3x3_bwd_f32(const float *x, const float *w, const float *y0, const float *y1, const float *grad_y0,
+                               const float *grad_y1, float *grad_x, float *grad_w, float *grad_b, void *workspace, int64_t B,
+                               int64_t Cin, int64_t Cout, int64_t C0, int64_t H, int64_t W, int pad_mode, int pre_act,
+                               double pre_slope, int tanh_mask, int sigmoid_mask, gfla_stream_t stream);
+int gfla_head_conv3x3_fwd_f16(const uint16_t *x, const float *w, const float *bias, uint16_t *y0, uint16_t *y1, int64_t B, int64_t Cin,
+                               int64_t Cout, int64_t C0, int64_t H, int64_t W, int pad_mode, int pre_act, double pre_slope,
+                               int tanh_mask, int sigmoid_mask, gfla_stream_t stream);
+int gfla_head_conv3x3_bwd_f16(const uint16_t *x, const float *w, const uint16_t *y0, const uint16_t *y1, const uint16_t *grad_y0,
+                               const uint16_t *grad_y1, uint16_t *grad_x, float *grad_w, float *grad_b, void *workspace, int64_t B,
+                               int64_t Cin, int64_t Cout, int64_t C0, int64_t H, int64_t W, int pad_mode, int pre_act,
+                               double pre_slope, int tanh_mask, int sigmoid_mask, gfla_stream_t stream);
+int gfla_head_conv3x3_fwd_bf16(const uint16_t *x, const float *w, const float *bias, uint16_t *y0, uint16_t *y1, int64_t B, int64_t Cin,
+                               int64_t Cout, int64_t C0, int64_t H, int64_t W, int pad_mode, int pre_act, double pre_slope,
+                               int tanh_mask, int sigmoid_mask, gfla_stream_t stream);
+int gfla_head_conv3x3_bwd_bf16(const uint16_t *x, const float *w, const uint16_t *y0, const uint16_t *y1, const uint16_t *grad_y0,
+                               const uint16_t *grad_y1, uint16_t *grad_x, float *grad_w, float *grad_b, void *workspace, int64_t B,
+                               int64_t Cin, int64_t Cout, int64_t C0, int64_t H, int64_t W, int pad_mode, int pre_act,
+                               double pre_slope, int tanh_mask, int sigmoid_mask, gfla_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
