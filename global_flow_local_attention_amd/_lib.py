@@ -1,4 +1,7 @@
-"""ctypes binding of libgfla_hip.so (the C ABI declared in include/gfla_hip.h).
+"""ctypes binding of libgfla_hip.so.
+
+include/gfla_hip.h is the single description of the C ABI: the argument and return types of every entry point, the
+dispatch-trace ids (enum gfla_path -> PATH_*), the status codes and ABI_VERSION are read from it, never restated here.
 
 The library is the only implementation of the ops: there is no Python/torch fallback.  If it
 is missing or fails to load, importing an op raises; if a call returns a non-zero status, a
@@ -6,6 +9,7 @@ RuntimeError is raised (the reference swallows native errors, block_extractor_cu
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -13,134 +17,83 @@ import torch
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # GFLA_HIP_LIBRARY: a differently built library (tools/ubench/build_agg_abl.sh timing variants); default = the in-tree build
 LIB_PATH = os.environ.get("GFLA_HIP_LIBRARY") or os.path.join(_PKG, "libgfla_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfla_hip.h")   # csrc/Makefile: ../../include/gfla_hip.h
 _lib = None
 
-_i64, _int, _ptr = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
+# the types the ABI is written in; a pointer of any pointee crosses as c_void_p
+_ARG_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "gfla_stream_t": ctypes.c_void_p}
+_RETURN_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
 
-# entry point -> argument types (pointers first, then sizes), mirroring include/gfla_hip.h
-_SIGNATURES = {
-    "gfla_block_extractor_fwd": [_ptr] * 3 + [_i64] * 6 + [_int, _ptr],
-    "gfla_block_extractor_bwd": [_ptr] * 5 + [_i64] * 6 + [_int, _ptr],
-    "gfla_block_extractor_unfold_fwd": [_ptr] * 3 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_block_extractor_unfold_bwd": [_ptr] * 5 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_local_attn_reshape_fwd": [_ptr] * 2 + [_i64] * 3 + [_int, _ptr],
-    "gfla_local_attn_reshape_bwd": [_ptr] * 2 + [_i64] * 3 + [_int, _ptr],
-    "gfla_resample2d_fwd": [_ptr] * 3 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_resample2d_bwd": [_ptr] * 5 + [_i64] * 6 + [_int, _int, _int, _ptr],
-    "gfla_local_attn_aggregate_fwd": [_ptr] * 5 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_local_attn_aggregate_bwd": [_ptr] * 7 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_local_attn_source_bwd": [_ptr] * 7 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_flow_warp_fwd": [_ptr] * 3 + [_i64] * 6 + [ctypes.c_double] * 4 + [_ptr],
-    "gfla_flow_warp_bwd": [_ptr] * 5 + [_i64] * 6 + [ctypes.c_double] * 4 + [_ptr],
-    "gfla_instance_norm_fwd": [_ptr] * 7 + [_i64] * 4 + [ctypes.c_double] * 2 + [_int, _ptr],
-    "gfla_instance_norm_bwd": [_ptr] * 10 + [_i64] * 4 + [ctypes.c_double, _int, _ptr],
-}
-# entry points that exist in one precision only: full symbol name -> argument types
-_SINGLE = {
-    "gfla_max_cosine_fwd_f32": [_ptr] * 5 + [_i64] * 4 + [ctypes.c_double, _ptr],
-    "gfla_max_cosine_fwd_f16": [_ptr] * 5 + [_i64] * 4 + [ctypes.c_double, _ptr],
-    "gfla_max_cosine_fwd_bf16": [_ptr] * 5 + [_i64] * 4 + [ctypes.c_double, _ptr],
-    "gfla_max_cosine_workspace_bytes": [_i64] * 3,
-    "gfla_fc_tail_fwd_f32": [_ptr, _i64, _i64] + [_ptr] * 5 + [_i64] * 3 + [_int, ctypes.c_double, _ptr],
-    "gfla_fc_tail_fwd_f64": [_ptr, _i64, _i64] + [_ptr] * 5 + [_i64] * 3 + [_int, ctypes.c_double, _ptr],
-    "gfla_fc_tail_bwd_f32": [_ptr, _i64, _i64] + [_ptr] * 8 + [_i64] * 3 + [_int, ctypes.c_double, _ptr],
-    "gfla_fc_tail_bwd_f64": [_ptr, _i64, _i64] + [_ptr] * 8 + [_i64] * 3 + [_int, ctypes.c_double, _ptr],
-    "gfla_replicate_pad_bwd_f32": [_ptr] * 2 + [_i64] * 3 + [_int] * 4 + [_ptr],
-    "gfla_replicate_pad_bwd_f64": [_ptr] * 2 + [_i64] * 3 + [_int] * 4 + [_ptr],
-    "gfla_correctness_map_fwd_f32": [_ptr] * 5 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
-    "gfla_correctness_map_bwd_f32": [_ptr] * 9 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
-    "gfla_correctness_map_fwd_f16": [_ptr] * 5 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
-    "gfla_correctness_map_bwd_f16": [_ptr] * 9 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
-    "gfla_correctness_map_fwd_bf16": [_ptr] * 5 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
-    "gfla_correctness_map_bwd_bf16": [_ptr] * 9 + [_i64] * 3 + [ctypes.c_double] * 2 + [_ptr],
-    "gfla_fc_supported": [_i64] * 3 + [_int, _int],
-    "gfla_fc_workspace_bytes": [_i64] * 4 + [_int] * 3,
-    "gfla_fc_forward_f32": [_ptr] * 9 + [_i64] * 4 + [_int, ctypes.c_double, _int, _ptr],
-    "gfla_fc_backward_f32": [_ptr] * 12 + [_i64] * 4 + [_int, ctypes.c_double, _int, _int, _ptr],
-    "gfla_fc_geometry": [_i64, _i64, _int, _int, _ptr],
-    "gfla_fc_conv_fwd_f32": [_ptr, _ptr, _int, _ptr, _ptr] + [_i64] * 4 + [_int, _int, _ptr],
-    "gfla_fc_conv_bwd_f32": [_ptr, _int, _ptr, _ptr, _ptr, _ptr] + [_i64] * 4 + [_int, _int, _ptr],
-    "gfla_fc_tr_probe": [_ptr, _int, _ptr, _ptr, _ptr],
-    "gfla_fc_wino_debug_buffer": [_ptr],
-    "gfla_fc_kernel_f32": [_int, _ptr, _ptr] + [_i64] * 4 + [_int, _int, _ptr],
-    "gfla_scatter_workspace_bytes": [_i64] * 3 + [_int],
-    "gfla_aggregate_fwd_workspace_bytes": [_i64] * 3 + [_int],
-    "gfla_aggregate_fwd_geometry": [_i64] * 6 + [_int, _ptr],
-    "gfla_aggregate_bwd_supported": [_i64, _i64, _int],
-    "gfla_big_plane_geometry": [_int] + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_xcd_swizzle": [_i64, _i64],
-    "gfla_local_attn_aggregate_fwd_ws_f32": [_ptr] * 6 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_local_attn_aggregate_fwd_ws_bf16": [_ptr] * 6 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_local_attn_aggregate_fwd_ws_f16": [_ptr] * 6 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_local_attn_aggregate_bwd_ws_f32": [_ptr] * 8 + [_i64] * 6 + [_int, _int, _ptr],
-    "gfla_resample2d_bwd_ws_f32": [_ptr] * 6 + [_i64] * 6 + [_int, _int, _int, _ptr],
-    "gfla_convert_multi": [_ptr, _ptr, _i64] * 4 + [_int, _ptr],
-    "gfla_mask_blend_fwd_f32": [_ptr] * 6 + [_i64] * 3 + [_ptr],
-    "gfla_mask_blend_fwd_bf16": [_ptr] * 6 + [_i64] * 3 + [_ptr],
-    "gfla_mask_blend_bwd_f32": [_ptr] * 11 + [_i64] * 3 + [_ptr],
-    "gfla_mask_blend_bwd_bf16": [_ptr] * 11 + [_i64] * 3 + [_ptr],
-    "gfla_mask_blend_fwd_f16": [_ptr] * 6 + [_i64] * 3 + [_ptr],
-    "gfla_mask_blend_bwd_f16": [_ptr] * 11 + [_i64] * 3 + [_ptr],
-    "gfla_fc_forward_f16": [_ptr] * 9 + [_i64] * 4 + [_int, ctypes.c_double, _ptr],
-    "gfla_gemm_f64_workspace_bytes": [_i64] * 3 + [_int],
-    "gfla_gemm_f64": [_ptr] * 6 + [_i64] * 3 + [_int, _int, _ptr, _ptr],
-    "gfla_affine_reg_workspace_bytes": [_i64] * 3 + [_int],
-    "gfla_affine_reg_fwd_f32": [_ptr] * 3 + [_i64] * 3 + [_int, _ptr],
-    "gfla_affine_reg_fwd_f64": [_ptr] * 3 + [_i64] * 3 + [_int, _ptr],
-    "gfla_affine_reg_fwd_f16": [_ptr] * 3 + [_i64] * 3 + [_int, _ptr],
-    "gfla_affine_reg_fwd_bf16": [_ptr] * 3 + [_i64] * 3 + [_int, _ptr],
-    "gfla_affine_reg_bwd_f32": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
-    "gfla_affine_reg_bwd_f64": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
-    "gfla_affine_reg_bwd_f16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
-    "gfla_affine_reg_bwd_bf16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
-    "gfla_gram_l1_workspace_bytes": [_i64] * 3,
-    "gfla_gram_l1_fwd_f32": [_ptr] * 5 + [_i64] * 3 + [_ptr],
-    "gfla_gram_l1_fwd_f16": [_ptr] * 5 + [_i64] * 3 + [_ptr],
-    "gfla_gram_l1_fwd_bf16": [_ptr] * 5 + [_i64] * 3 + [_ptr],
-    "gfla_gram_l1_bwd_f32": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
-    "gfla_gram_l1_bwd_f16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
-    "gfla_gram_l1_bwd_bf16": [_ptr] * 4 + [_i64] * 3 + [_int, _ptr],
-    "gfla_conv3x3_packed_bytes": [_i64, _i64, _int, _int],
-    "gfla_conv3x3_relu_fwd_f32": [_ptr] * 4 + [_i64] * 5 + [_ptr],
-    "gfla_conv3x3_relu_bwd_data_f32": [_ptr] * 4 + [_i64] * 5 + [_ptr],
-    "gfla_conv3x3_pack_weights_f32": [_ptr, _int, _ptr, _i64, _i64, _int, _ptr],
-    "gfla_maxpool2x2_fwd_f32": [_ptr] * 2 + [_i64] * 4 + [_ptr],
-    "gfla_maxpool2x2_bwd_f32": [_ptr] * 3 + [_i64] * 4 + [_ptr],
-    "gfla_conv3x3_relu_fwd_f16": [_ptr] * 4 + [_i64] * 5 + [_ptr],
-    "gfla_conv3x3_relu_bwd_data_f16": [_ptr] * 4 + [_i64] * 5 + [_ptr],
-    "gfla_conv3x3_pack_weights_f16": [_ptr, _int, _ptr, _i64, _i64, _int, _ptr],
-    "gfla_maxpool2x2_fwd_f16": [_ptr] * 2 + [_i64] * 4 + [_ptr],
-    "gfla_maxpool2x2_bwd_f16": [_ptr] * 3 + [_i64] * 4 + [_ptr],
-    "gfla_conv3x3_relu_fwd_bf16": [_ptr] * 4 + [_i64] * 5 + [_ptr],
-    "gfla_conv3x3_relu_bwd_data_bf16": [_ptr] * 4 + [_i64] * 5 + [_ptr],
-    "gfla_conv3x3_pack_weights_bf16": [_ptr, _int, _ptr, _i64, _i64, _int, _ptr],
-    "gfla_maxpool2x2_fwd_bf16": [_ptr] * 2 + [_i64] * 4 + [_ptr],
-    "gfla_maxpool2x2_bwd_bf16": [_ptr] * 3 + [_i64] * 4 + [_ptr],
-    "gfla_instance_norm_geometry": [_i64] * 4 + [_int, _int, _ptr],
-    "gfla_instance_norm_workspace_bytes": [_i64] * 4 + [_int],
-    "gfla_head_conv3x3_workspace_bytes": [_i64] * 5 + [_int],
-    "gfla_head_conv3x3_geometry": [_i64] * 5 + [_int, _ptr],
-    "gfla_head_conv3x3_fwd_f32": [_ptr] * 5 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
-    "gfla_head_conv3x3_fwd_f16": [_ptr] * 5 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
-    "gfla_head_conv3x3_fwd_bf16": [_ptr] * 5 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
-    "gfla_head_conv3x3_bwd_f32": [_ptr] * 10 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
-    "gfla_head_conv3x3_bwd_f16": [_ptr] * 10 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
-    "gfla_head_conv3x3_bwd_bf16": [_ptr] * 10 + [_i64] * 6 + [_int, _int, ctypes.c_double, _int, _int, _ptr],
-}
-# bf16 and f16 storage exist for every entry point below; the backward ones return the reductions over channels (grad_flow,
-# grad_logits, grad_in2) in float32 (include/gfla_hip.h)
-_FWD_ONLY_BF16 = set()
+
+def _enum_items(body, decl):
+    for item in filter(None, (i.strip() for i in body.split(","))):
+        m = re.fullmatch(r"(\w+) = (-?\d+)", item)
+        if m is None:
+            raise ValueError("gfla_hip.h: enumerator without an explicit integer value: %r in %r" % (item, decl))
+        yield m.group(1), int(m.group(2))
+
+
+def parse_header(text):
+    """(functions, constants) of a header in gfla_hip.h's dialect.  functions: entry point -> (restype, [argtypes]), with
+    every GFLA_DECL_*(SFX, T) instantiation expanded; constants: enumerators and integer #defines -> int.  Strict: a type
+    outside _ARG_TYPES / _RETURN_TYPES, or a statement that is no declaration, typedef or enum, raises ValueError with the
+    declaration in its message."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S).replace("\\\n", " ")
+    functions, constants, macros, code = {}, {}, {}, []
+    for line in text.splitlines():
+        line = line.strip()
+        m = re.match(r"#\s*define\s+(\w+)(\(SFX, T\))?\s*(.*)", line)
+        if m and m.group(2):
+            macros[m.group(1)] = m.group(3)
+        elif m and re.fullmatch(r"-?\d+", m.group(3)):
+            constants[m.group(1)] = int(m.group(3))
+        elif not line.startswith("#") and line not in ('extern "C" {', "}"):   # include guard, #undef, the C++ wrapper
+            code.append(line)
+    code = re.sub(r"\b(GFLA_DECL_\w+)\((\w+), (\w+)\)",
+                  lambda m: re.sub(r"\bT\b", m.group(3), macros[m.group(1)].replace("##SFX", m.group(2))), " ".join(code))
+    for decl in filter(None, (" ".join(d.split()) for d in code.split(";"))):
+        enum = re.fullmatch(r"(?:typedef )?enum \w+ \{(.*)\}(?: \w+)?", decl)
+        if enum:
+            constants.update(_enum_items(enum.group(1), decl))
+            continue
+        if re.fullmatch(r"typedef void \*gfla_stream_t", decl):
+            continue
+        m = re.fullmatch(r"(.*?)(gfla_\w+)\((.*)\)", decl)
+        if m is None:
+            raise ValueError("gfla_hip.h: not a declaration this binding understands: %r" % decl)
+        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if ret not in _RETURN_TYPES:
+            raise ValueError("gfla_hip.h: unknown return type %r in %r" % (ret, decl))
+        argtypes = []
+        for arg in ([] if args == "void" else args.split(",")):
+            ctype = re.sub(r"\w+$", "", arg.strip()).strip()     # drop the parameter's name
+            if "*" in ctype:
+                argtypes.append(ctypes.c_void_p)
+            elif ctype in _ARG_TYPES:
+                argtypes.append(_ARG_TYPES[ctype])
+            else:
+                raise ValueError("gfla_hip.h: unknown argument type %r (%r) in %r" % (ctype, arg.strip(), decl))
+        functions[name] = (_RETURN_TYPES[ret], argtypes)
+    return functions, constants
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError("include/gfla_hip.h, the description of the C ABI, is missing (%s)" % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+_FUNCTIONS, _CONSTANTS = _read_header()   # once per process
+ABI_VERSION = _CONSTANTS["GFLA_ABI_VERSION"]
+_ERR_UNSUPPORTED = _CONSTANTS["GFLA_ERR_UNSUPPORTED"]
+# dispatch-trace ids: GFLA_PATH_X of enum gfla_path is PATH_X here (PATH_BE_BWD_LDS ... PATH_COUNT)
+globals().update((name[len("GFLA_"):], value) for name, value in _CONSTANTS.items() if name.startswith("GFLA_PATH_"))
 
 
 def exported_symbols():
     """Every symbol include/gfla_hip.h declares."""
-    names = ["gfla_abi_version", "gfla_status_string", "gfla_set_tuning", "gfla_path_count", "gfla_unfold_supported"]
-    for base in _SIGNATURES:
-        for sfx in ("f32", "f64", "bf16", "f16"):
-            if sfx == "bf16" and base in _FWD_ONLY_BF16:
-                continue
-            names.append("%s_%s" % (base, sfx))
-    return names + list(_SINGLE)
+    return list(_FUNCTIONS)
 
 
 def build(force=False):
@@ -160,42 +113,32 @@ def lib():
                 "libgfla_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C global_flow_local_attention_amd/csrc`. There is no fallback path." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        handle.gfla_status_string.restype = ctypes.c_char_p
-        handle.gfla_status_string.argtypes = [_int]
-        handle.gfla_set_tuning.argtypes = [_int, _int]
-        handle.gfla_path_count.argtypes = [_int]
-        handle.gfla_path_count.restype = _i64
-        handle.gfla_unfold_supported.argtypes = [_i64, _i64, _int, _int]
-        for base, args in _SIGNATURES.items():
-            for sfx in ("f32", "f64", "bf16", "f16"):
-                if sfx == "bf16" and base in _FWD_ONLY_BF16:
-                    continue
-                fn = getattr(handle, "%s_%s" % (base, sfx))
-                fn.argtypes = args
-                fn.restype = _int
-        for name, args in _SINGLE.items():
+        for name, (restype, argtypes) in _FUNCTIONS.items():
             fn = getattr(handle, name)
-            fn.argtypes = args
-            fn.restype = _i64 if (name.endswith("_bytes") or name == "gfla_xcd_swizzle") else _int
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = handle
     return _lib
 
 
-_SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
+SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
 # 16-bit storage types: fp32 arithmetic inside, reductions over channels in float32
 HALF_TYPES = (torch.bfloat16, torch.float16)
 
 
-def suffix(t, what, allow_bf16=True):
-    """Entry-point suffix for t's dtype.  allow_bf16=False: entry points without bfloat16 storage raise a clear
-    TypeError instead of a missing-symbol AttributeError."""
+def suffix(t, what):
+    """Entry-point suffix for t's dtype."""
     try:
-        sfx = _SUFFIX[t.dtype]
+        return SUFFIX[t.dtype]
     except KeyError:
         raise TypeError("%s: unsupported dtype %s (float32, float64, bfloat16, float16)" % (what, t.dtype))
-    if sfx == "bf16" and not allow_bf16:
-        raise TypeError("%s: bfloat16 is forward-only in this library (use float32 for training)" % what)
-    return sfx
+
+
+IMPLS = ("auto", "torch")
+
+
+def check_impl(impl):
+    if impl not in IMPLS:
+        raise ValueError("impl: one of %s (got %r)" % (IMPLS, impl))
 
 
 def reduction_like(t):
@@ -204,10 +147,24 @@ def reduction_like(t):
     return torch.zeros(t.shape, dtype=torch.float32 if t.dtype in HALF_TYPES else t.dtype, device=t.device)
 
 
+def workspace_bytes(query_name, *sizes, what):
+    """Answer of the `*_bytes` size query `query_name` for `sizes`.  A negative answer is a gfla_status: Unsupported for
+    GFLA_ERR_UNSUPPORTED (callers with another way to the result catch it), ValueError for anything else."""
+    n = int(getattr(lib(), query_name)(*(int(s) for s in sizes)))
+    if n < 0:
+        err = Unsupported if n == _ERR_UNSUPPORTED else ValueError
+        raise err("%s%s: %s" % (what, tuple(int(s) for s in sizes), lib().gfla_status_string(n).decode()))
+    return n
+
+
+def workspace(query_name, ref_tensor, *sizes, what):
+    """Scratch of the size `query_name` asks for, on ref_tensor's device: at least 16 bytes, so never a NULL pointer."""
+    return torch.empty(max(workspace_bytes(query_name, *sizes, what=what), 16), dtype=torch.uint8, device=ref_tensor.device)
+
+
 def scatter_workspace(ref_tensor, B, H, W, entries):
     """Scratch for the matrix-core scatter paths (csrc/patch_mfma.hip): the patch table of one op invocation."""
-    n = lib().gfla_scatter_workspace_bytes(int(B), int(H), int(W), int(entries))
-    return torch.empty(max(int(n), 16), dtype=torch.uint8, device=ref_tensor.device)
+    return workspace("gfla_scatter_workspace_bytes", ref_tensor, B, H, W, entries, what="scatter workspace")
 
 
 def aggregate_fwd(source, flow, logits, out, attn, k, apply_softmax):
@@ -218,8 +175,7 @@ def aggregate_fwd(source, flow, logits, out, attn, k, apply_softmax):
     sfx = suffix(source, "local_attn_aggregate")
     tail = (b, c, hs, ws, h, w, int(k), 1 if apply_softmax else 0)
     if sfx in ("f32", "bf16", "f16"):
-        n = lib().gfla_aggregate_fwd_workspace_bytes(int(b), int(h), int(w), int(k))
-        scratch = torch.empty(max(int(n), 16), dtype=torch.uint8, device=source.device)
+        scratch = workspace("gfla_aggregate_fwd_workspace_bytes", source, b, h, w, k, what="local_attn_aggregate")
         call("gfla_local_attn_aggregate_fwd_ws_" + sfx, source, ptr(source), ptr(flow), ptr(logits), ptr(out), ptr(attn),
              ptr(scratch), *tail)
     else:
@@ -250,7 +206,7 @@ def call(name, ref_tensor, *args):
         stream = ctypes.c_void_p(torch.cuda.current_stream(ref_tensor.device).cuda_stream)
         status = fn(*args, stream)
     if status != 0:
-        err = Unsupported if status == -3 else RuntimeError
+        err = Unsupported if status == _ERR_UNSUPPORTED else RuntimeError
         raise err("%s failed: %s (status %d)" % (name, lib().gfla_status_string(status).decode(), status))
 
 
@@ -289,16 +245,6 @@ def unfold_supported(Hs, Ws, k, elem_size):
 def set_tuning(key, value):
     """Process-global tuning knob (include/gfla_hip.h); returns the old value."""
     return lib().gfla_set_tuning(int(key), int(value))
-
-
-ABI_VERSION = 8
-# dispatch-trace ids (enum gfla_path in include/gfla_hip.h)
-PATH_BE_BWD_LDS, PATH_BE_BWD_GLOBAL, PATH_FC_FWD_MODE0, PATH_FC_BWD_MODE0, PATH_BE_FWD_PIX = 0, 1, 2, 7, 12
-# round 5: the big-plane kernels (few planes, each beyond the LDS budget; csrc/tile_map.h)
-PATH_BE_FWD_GPIX, PATH_BE_BWD_TILE, PATH_RS_FWD_BIG, PATH_RS_BWD1_TILE, PATH_RS_BWD2_BIG = 13, 14, 15, 16, 17
-PATH_FC_FWD_MODE5, PATH_FC_BWD_MODE5 = 18, 19
-PATH_GEMM_F64 = 20   # float64 FC layers of ExtractorAttn (csrc/gemm_f64.hip)
-PATH_FC_PACK_F16, PATH_COUNT = 21, 22   # gfla_fc_forward_f16: activation records packed straight from the float16 maps
 
 
 def fc_path(mode, backward=False):

@@ -48,8 +48,7 @@ class MaxCosineFunction(Function):
         Nt = target.size(2)
         best = torch.empty(B, Nt, dtype=torch.float32, device=source.device)
         index = torch.empty(B, Nt, dtype=torch.int32, device=source.device)
-        scratch = torch.empty(_lib.lib().gfla_max_cosine_workspace_bytes(B, Ns, Nt), dtype=torch.uint8,
-                              device=source.device)
+        scratch = _lib.workspace("gfla_max_cosine_workspace_bytes", source, B, Ns, Nt, what="max_cosine_similarity")
         _lib.call("gfla_max_cosine_fwd_" + _lib.suffix(source, "max_cosine_similarity"), source, _lib.ptr(source), _lib.ptr(target), _lib.ptr(scratch),
                   _lib.ptr(best), _lib.ptr(index), B, C, Ns, Nt, float(eps))
         ctx.eps = eps

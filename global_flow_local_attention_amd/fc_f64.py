@@ -41,10 +41,8 @@ def gemm(c, c_view, a, a_view, b, b_view, M, N, K, beta=0, split_k=0, offsets=(0
         if t.dtype != torch.float64:
             raise TypeError("gemm_f64: float64 operands only (got %s)" % t.dtype)
     _lib.require_gpu(c, a, b)
-    n = int(_lib.lib().gfla_gemm_f64_workspace_bytes(int(M), int(N), int(K), int(split_k)))
-    if n < 0:
-        raise ValueError("gemm_f64: bad extents M=%s N=%s K=%s split_k=%s" % (M, N, K, split_k))
-    ws = torch.empty(n, dtype=torch.uint8, device=c.device) if n > 0 else None
+    n = _lib.workspace_bytes("gfla_gemm_f64_workspace_bytes", M, N, K, split_k, what="gemm_f64 (M, N, K, split_k)")
+    ws = torch.empty(n, dtype=torch.uint8, device=c.device) if n > 0 else None   # no split: NULL, as the header allows
     p = [ctypes.c_void_p(t.data_ptr() + 8 * int(o)) for t, o in zip((c, a, b), offsets)]
     _lib.call("gfla_gemm_f64", c, p[0], c_view, p[1], a_view, p[2], b_view, int(M), int(N), int(K), int(beta),
               int(split_k), _lib.ptr(ws))

@@ -58,10 +58,8 @@ def resolve_mode(C, H, W, k, mode=None):
 
 
 def workspace_bytes(B, C, H, W, k, mode, which):
-    n = _lib.lib().gfla_fc_workspace_bytes(int(B), int(C), int(H), int(W), int(k), int(mode), int(which))
-    if n < 0:
-        raise ValueError("fc_mfma: unsupported shape B=%d C=%d %dx%d k=%d mode=%d" % (B, C, H, W, k, mode))
-    return n
+    return _lib.workspace_bytes("gfla_fc_workspace_bytes", B, C, H, W, k, mode, which,
+                                what="fc_mfma: unsupported shape (B, C, H, W, k, mode, which)")
 
 
 def geometry(H, W, k, is_source):

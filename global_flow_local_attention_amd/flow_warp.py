@@ -21,7 +21,7 @@ from torch.autograd import Function
 from . import _lib
 
 CONVENTIONS = ("correctness", "block", "pixel")
-IMPLS = ("auto", "torch")
+IMPLS = _lib.IMPLS
 
 
 def convention_scalars(convention, hs, ws):
@@ -111,7 +111,7 @@ def torch_flow_warp(source, flow, gx, gy, mx, my):
 
 
 def _kernel_dtypes(source, flow):
-    if not (source.is_cuda and flow.is_cuda) or source.dtype not in _lib._SUFFIX:
+    if not (source.is_cuda and flow.is_cuda) or source.dtype not in _lib.SUFFIX:
         return False
     return flow.dtype == (torch.float64 if source.dtype == torch.float64 else torch.float32)
 
@@ -123,8 +123,7 @@ def flow_warp(source, flow, convention="pixel", impl="auto"):
     kernels of csrc/flow_warp.hip.  CPU tensors and any other dtype pairing take the torch composition (torch_flow_warp).
     impl "torch": always the composition.  On either route a 16-bit flow is up-cast to float32 first (a 16-bit flow of
     32-64 px has steps of 0.25-0.5 px in bfloat16; its gradient is cast back), and 16-bit sources give a float32 map."""
-    if impl not in IMPLS:
-        raise ValueError("impl: one of %s (got %r)" % (IMPLS, impl))
+    _lib.check_impl(impl)
     scalars = convention_scalars(convention, source.size(2), source.size(3))
     if flow.dtype in _lib.HALF_TYPES:
         flow = flow.float()     # (autograd casts the flow's gradient back)
@@ -140,8 +139,7 @@ class FlowWarp(nn.Module):
         super(FlowWarp, self).__init__()
         if convention not in CONVENTIONS:
             raise ValueError("convention: one of %s (got %r)" % (CONVENTIONS, convention))
-        if impl not in IMPLS:
-            raise ValueError("impl: one of %s (got %r)" % (IMPLS, impl))
+        _lib.check_impl(impl)
         self.convention = convention
         self.impl = impl
 

@@ -27,16 +27,11 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 
-IMPLS = ("auto", "torch")
+IMPLS = _lib.IMPLS
 PADDINGS = ("zeros", "reflect")
 POSTS = (None, "tanh", "sigmoid")
 MAX_COUT = 8
 _KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
-
-
-def _check_impl(impl):
-    if impl not in IMPLS:
-        raise ValueError("impl: one of %s (got %r)" % (IMPLS, impl))
 
 
 def _posts(post, cout):
@@ -83,11 +78,7 @@ def _masks(posts):
 
 def _workspace(x, cout):
     B, C, H, W = x.shape
-    n = _lib.lib().gfla_head_conv3x3_workspace_bytes(B, C, cout, H, W, x.element_size())
-    if n < 0:
-        err = _lib.Unsupported if n == -3 else ValueError
-        raise err("head_conv3x3%s: %s" % (tuple(x.shape), _lib.lib().gfla_status_string(int(n)).decode()))
-    return torch.empty(max(int(n), 16), dtype=torch.uint8, device=x.device)
+    return _lib.workspace("gfla_head_conv3x3_workspace_bytes", x, B, C, cout, H, W, x.element_size(), what="head_conv3x3")
 
 
 class HeadConv3x3Function(Function):
@@ -212,7 +203,7 @@ def head_conv3x3(x, weight, bias=None, padding="zeros", pre_slope=None, post=Non
     impl "auto": a GPU map of float32 / float16 / bfloat16 with Cout <= 8 runs on the kernels (HeadConv3x3Function).
     Float64 tensors, CPU tensors, Cout > 8 and shapes the library refuses (_lib.Unsupported) take the torch composition
     (torch_head_conv3x3).  "torch": always the composition."""
-    _check_impl(impl)
+    _lib.check_impl(impl)
     posts, split = _validate(x, weight, bias, padding, pre_slope, post, split)
     if impl == "auto" and _kernel_inputs(x, weight, bias):
         try:
@@ -230,7 +221,7 @@ class HeadConv3x3(nn.Module):
     def __init__(self, in_channels, out_channels, bias=True, padding="zeros", pre_slope=None, post=None, split=None,
                  impl="auto"):
         super(HeadConv3x3, self).__init__()
-        _check_impl(impl)
+        _lib.check_impl(impl)
         if int(in_channels) < 1 or int(out_channels) < 1:
             raise ValueError("HeadConv3x3: positive channel counts (got %r, %r)" % (in_channels, out_channels))
         if padding not in PADDINGS:
@@ -305,7 +296,7 @@ def fuse_output_heads(module, impl="auto"):
     that carry any forward or backward hook (spectral norm recomputes the weight in one) are left alone.  An activation
     built with inplace=True no longer overwrites the caller's input once it is fused: the op reads x and leaves it as it
     is.  Returns the number of heads fused."""
-    _check_impl(impl)
+    _lib.check_impl(impl)
     heads = 0
     for seq in [m for m in module.modules() if isinstance(m, nn.Sequential)]:
         names = list(seq._modules.keys())

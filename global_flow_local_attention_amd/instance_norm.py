@@ -19,7 +19,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 
-IMPLS = ("auto", "torch")
+IMPLS = _lib.IMPLS
 
 
 def _acc_dtype(dtype):
@@ -35,11 +35,7 @@ def _aligned(t):
 
 def _workspace(x):
     B, C, H, W = x.shape
-    n = _lib.lib().gfla_instance_norm_workspace_bytes(B, C, H, W, x.element_size())
-    if n < 0:
-        err = _lib.Unsupported if n == -3 else ValueError
-        raise err("instance_norm_act%s: %s" % (tuple(x.shape), _lib.lib().gfla_status_string(int(n)).decode()))
-    return torch.empty(max(int(n), 16), dtype=torch.uint8, device=x.device)
+    return _lib.workspace("gfla_instance_norm_workspace_bytes", x, B, C, H, W, x.element_size(), what="instance_norm_act")
 
 
 class InstanceNormActFunction(Function):
@@ -121,11 +117,6 @@ class InstanceNormActFunction(Function):
         return dx, dw, db, None, None
 
 
-def _check_impl(impl):
-    if impl not in IMPLS:
-        raise ValueError("impl: one of %s (got %r)" % (IMPLS, impl))
-
-
 def torch_instance_norm_act(x, weight=None, bias=None, eps=1e-5, negative_slope=None):
     """The same map as the torch composition: F.instance_norm (no running statistics), then F.leaky_relu, or F.relu for a
     slope of 0, or nothing for None."""
@@ -136,7 +127,7 @@ def torch_instance_norm_act(x, weight=None, bias=None, eps=1e-5, negative_slope=
 
 
 def _kernel_inputs(x, weight, bias):
-    if not x.is_cuda or x.dtype not in _lib._SUFFIX or x.dim() != 4 or x.numel() == 0:
+    if not x.is_cuda or x.dtype not in _lib.SUFFIX or x.dim() != 4 or x.numel() == 0:
         return False
     return all(p is None or (p.is_cuda and p.is_floating_point()) for p in (weight, bias))
 
@@ -148,7 +139,7 @@ def instance_norm_act(x, weight=None, bias=None, eps=1e-5, negative_slope=None, 
     torch.autocast a float32 map stays float32, as F.instance_norm keeps it).  CPU tensors, other dtypes and shapes the
     library refuses (_lib.Unsupported) take the torch composition (torch_instance_norm_act).  "torch": always the
     composition."""
-    _check_impl(impl)
+    _lib.check_impl(impl)
     if x.dim() != 4:
         raise ValueError("instance_norm_act: x (B,C,H,W) (got %s)" % (tuple(x.shape),))
     for name, p in (("weight", weight), ("bias", bias)):
@@ -171,7 +162,7 @@ class InstanceNormAct(nn.Module):
         super(InstanceNormAct, self).__init__()
         if track_running_stats:
             raise ValueError("InstanceNormAct: track_running_stats is not supported")
-        _check_impl(impl)
+        _lib.check_impl(impl)
         if int(num_features) < 1:
             raise ValueError("num_features: a positive channel count (got %r)" % (num_features,))
         if negative_slope is not None and not float(negative_slope) >= 0:
@@ -227,7 +218,7 @@ def fuse_instance_norm_act(module, impl="auto"):
     activation instance shared with other places of the network (the reference passes one object around) is left as it
     is: only slots are replaced.  An nn.InstanceNorm2d of a Sequential with no activation after it becomes
     InstanceNormAct(negative_slope=None).  Anything else is left alone.  Returns the number of pairs fused."""
-    _check_impl(impl)
+    _lib.check_impl(impl)
     pairs = 0
     for seq in [m for m in module.modules() if isinstance(m, nn.Sequential)]:
         names = list(seq._modules.keys())

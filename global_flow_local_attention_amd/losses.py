@@ -67,11 +67,7 @@ class AffineRegFunction(Function):
         if H < kz or W < kz:
             raise ValueError("affine regularisation loss: a %dx%d map has no %dx%d window" % (H, W, kz, kz))
         flow = flow.contiguous()
-        n = _lib.lib().gfla_affine_reg_workspace_bytes(B, H, W, kz)
-        if n < 0:
-            err = _lib.Unsupported if n == -3 else RuntimeError
-            raise err("gfla_affine_reg_workspace_bytes%s: %s" % ((B, H, W, kz), _lib.lib().gfla_status_string(n).decode()))
-        scratch = torch.empty(int(n), dtype=torch.uint8, device=flow.device)
+        scratch = _lib.workspace("gfla_affine_reg_workspace_bytes", flow, B, H, W, kz, what="affine regularisation loss")
         loss = torch.empty((), dtype=torch.float64 if flow.dtype == torch.float64 else torch.float32, device=flow.device)
         _lib.call("gfla_affine_reg_fwd_" + sfx, flow, _lib.ptr(flow), _lib.ptr(scratch), _lib.ptr(loss), B, H, W, kz)
         ctx.kz = kz
@@ -99,18 +95,17 @@ class AffineRegularizationLoss(nn.Module):
     library's kernels (AffineRegFunction), everything else the torch composition below; "torch" -- always the composition
     (cross-checks, tools/bench_affine_reg.py)."""
 
-    IMPLS = ("auto", "torch")
+    IMPLS = _lib.IMPLS
 
     def __init__(self, kz, impl="auto"):
         super(AffineRegularizationLoss, self).__init__()
-        if impl not in self.IMPLS:
-            raise ValueError("impl: one of %s (got %r)" % (self.IMPLS, impl))
+        _lib.check_impl(impl)
         self.kz = kz
         self.kernel = affine_projector(kz).view(kz ** 2, kz ** 2)
         self.impl = impl
 
     def __call__(self, flow_fields):
-        if self.impl == "auto" and flow_fields.is_cuda and flow_fields.dtype in _lib._SUFFIX and \
+        if self.impl == "auto" and flow_fields.is_cuda and flow_fields.dtype in _lib.SUFFIX and \
                 KZ_MIN <= self.kz <= KZ_MAX:
             return AffineRegFunction.apply(flow_fields, self.kz)
         grid = self.flow2grid(flow_fields)
@@ -156,7 +151,7 @@ class MultiAffineRegularizationLoss(nn.Module):
 # ---- style and content loss (VGGLoss, external_function.py:121-220) --------------------------------------------------
 STYLE_LAYERS = ("relu2_2", "relu3_4", "relu4_4", "relu5_2")
 CONTENT_LAYERS = ("relu1_1", "relu2_1", "relu3_1", "relu4_1", "relu5_1")
-GRAM_IMPLS = ("auto", "torch")
+GRAM_IMPLS = _lib.IMPLS
 _GRAM_SUFFIX = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
 
 
@@ -191,11 +186,7 @@ class GramL1Function(Function):
         x, y = x.contiguous(), y.contiguous()
         B, C = x.shape[:2]
         N = x.numel() // (B * C)
-        n = _lib.lib().gfla_gram_l1_workspace_bytes(B, C, N)
-        if n < 0:
-            err = _lib.Unsupported if n == -3 else RuntimeError
-            raise err("gfla_gram_l1_workspace_bytes%s: %s" % ((B, C, N), _lib.lib().gfla_status_string(n).decode()))
-        scratch = torch.empty(int(n), dtype=torch.uint8, device=x.device)
+        scratch = _lib.workspace("gfla_gram_l1_workspace_bytes", x, B, C, N, what="gram l1 loss")
         diff = torch.empty((B, C, C), dtype=torch.float32, device=x.device)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         _lib.call("gfla_gram_l1_fwd_" + sfx, x, _lib.ptr(x), _lib.ptr(y), _lib.ptr(scratch), _lib.ptr(diff),
@@ -224,8 +215,7 @@ def gram_l1(x, y, impl="auto"):
     float32 / float16 / bfloat16 take the library's kernels (GramL1Function); CPU tensors, float64, mixed dtypes and
     shapes the kernels refuse (_lib.Unsupported) take the torch composition, the reference's arithmetic.  "torch": always
     the composition."""
-    if impl not in GRAM_IMPLS:
-        raise ValueError("impl: one of %s (got %r)" % (GRAM_IMPLS, impl))
+    _lib.check_impl(impl)
     if impl == "auto" and x.is_cuda and y.is_cuda and x.dtype == y.dtype and x.dtype in _GRAM_SUFFIX:
         try:
             return GramL1Function.apply(x, y)
@@ -240,8 +230,7 @@ class _VggLossBase(nn.Module):
 
     def __init__(self, vgg, impl):
         super(_VggLossBase, self).__init__()
-        if impl not in GRAM_IMPLS:
-            raise ValueError("impl: one of %s (got %r)" % (GRAM_IMPLS, impl))
+        _lib.check_impl(impl)
         if isinstance(vgg, nn.Module):
             self.add_module('vgg', vgg)
         else:

@@ -17,7 +17,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 
-IMPLS = ("auto", "torch")
+IMPLS = _lib.IMPLS
 _SFX = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
 _SRC_TYPE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
@@ -57,11 +57,7 @@ def packed_weights(weight, dtype, layout):
         w = weight.detach().contiguous()
         cout, cin = w.shape[:2]
         esize = torch.empty((), dtype=dtype).element_size()
-        n = _lib.lib().gfla_conv3x3_packed_bytes(cout, cin, layout, esize)
-        if n < 0:
-            err = _lib.Unsupported if n == -3 else RuntimeError
-            raise err("gfla_conv3x3_packed_bytes%s: %s" % ((cout, cin), _lib.lib().gfla_status_string(n).decode()))
-        packed = torch.empty(int(n), dtype=torch.uint8, device=w.device)
+        packed = _lib.workspace("gfla_conv3x3_packed_bytes", w, cout, cin, layout, esize, what="conv3x3 packed weights")
         _lib.call("gfla_conv3x3_pack_weights_" + _SFX[dtype], w, _lib.ptr(w), _SRC_TYPE[w.dtype], _lib.ptr(packed), cout, cin,
                   layout)
         return packed
@@ -151,17 +147,12 @@ class MaxPool2x2Function(Function):
         return grad_x
 
 
-def _check_impl(impl):
-    if impl not in IMPLS:
-        raise ValueError("impl: one of %s (got %r)" % (IMPLS, impl))
-
-
 def conv3x3_relu(x, weight, bias, impl="auto"):
     """relu(conv2d(x, weight, bias, stride=1, padding=1)).  impl "auto": a GPU map of float32 / float16 / bfloat16 with
     frozen float parameters runs on the kernels (Conv3x3ReluFunction).  CPU tensors, float64, a weight or bias that
     requires a gradient, and shapes the library refuses (_lib.Unsupported) take the torch composition.  "torch": always
     the composition."""
-    _check_impl(impl)
+    _lib.check_impl(impl)
     if impl == "auto" and x.is_cuda and weight.is_cuda and bias.is_cuda and x.dtype in _SFX and x.numel() > 0 and \
             weight.dtype in _SRC_TYPE and bias.dtype in _SRC_TYPE and not (weight.requires_grad or bias.requires_grad):
         try:
@@ -176,7 +167,7 @@ def conv3x3_relu(x, weight, bias, impl="auto"):
 def maxpool2x2(x, impl="auto"):
     """max_pool2d(x, kernel_size=2, stride=2).  impl "auto": GPU maps of float32 / float16 / bfloat16 run on the kernels
     (MaxPool2x2Function); anything else, and "torch", take F.max_pool2d."""
-    _check_impl(impl)
+    _lib.check_impl(impl)
     if impl == "auto" and x.is_cuda and x.dtype in _SFX and x.dim() == 4 and x.numel() > 0:
         try:
             return MaxPool2x2Function.apply(x)
@@ -225,7 +216,7 @@ class VGG19Features(nn.Module):
 
     def __init__(self, widths=(64, 128, 256, 512, 512), impl="auto"):
         super(VGG19Features, self).__init__()
-        _check_impl(impl)
+        _lib.check_impl(impl)
         if len(widths) != 5 or any(int(w) < 1 for w in widths):
             raise ValueError("widths: five positive channel counts (got %r)" % (widths,))
         self._impl = impl
@@ -252,7 +243,7 @@ class VGG19Features(nn.Module):
 
     @impl.setter
     def impl(self, value):
-        _check_impl(value)
+        _lib.check_impl(value)
         self._impl = value
         for m in self.modules():
             if isinstance(m, (_Conv, _Pool)):

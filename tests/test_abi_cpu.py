@@ -35,6 +35,110 @@ def test_header_and_library_agree(gfla):
     assert _lib.lib().gfla_abi_version() == _lib.ABI_VERSION == 8
 
 
+def test_argument_types_match_header(gfla):
+    """The binding's types are derived from the header (_lib.parse_header).  The expectations below are written by hand from
+    reading include/gfla_hip.h; the properties after them hold for every exported symbol."""
+    from global_flow_local_attention_amd import _lib
+    P, L, I, D = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
+    expected = {
+        "gfla_fc_tail_fwd_f32": [P, L, L, P, P, P, P, P, L, L, L, I, D, P],
+        "gfla_fc_tail_bwd_f64": [P, L, L, P, P, P, P, P, P, P, P, L, L, L, I, D, P],
+        "gfla_convert_multi": [P, P, L, P, P, L, P, P, L, P, P, L, I, P],
+        "gfla_gemm_f64": [P, P, P, P, P, P, L, L, L, I, I, P, P],
+        "gfla_flow_warp_fwd_f16": [P, P, P, L, L, L, L, L, L, D, D, D, D, P],
+        "gfla_instance_norm_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, L, L, L, L, D, I, P],
+        "gfla_head_conv3x3_bwd_f16": [P, P, P, P, P, P, P, P, P, P, L, L, L, L, L, L, I, I, D, I, I, P],
+        "gfla_fc_backward_f32": [P, P, P, P, P, P, P, P, P, P, P, P, L, L, L, L, I, D, I, I, P],
+        "gfla_big_plane_geometry": [I, L, L, L, L, L, L, I, I, P],
+        "gfla_resample2d_bwd_ws_f32": [P, P, P, P, P, P, L, L, L, L, L, L, I, I, I, P],
+        "gfla_block_extractor_unfold_bwd_f16": [P, P, P, P, P, L, L, L, L, L, L, I, I, P],   # GFLA_DECL_BWD16
+        "gfla_maxpool2x2_bwd_bf16": [P, P, P, L, L, L, L, P],                                # GFLA_DECL_MAXPOOL2X2
+        "gfla_abi_version": [],
+        "gfla_status_string": [I],
+        "gfla_xcd_swizzle": [L, L],
+    }
+    handle = _lib.lib()
+    for name, args in expected.items():
+        assert list(getattr(handle, name).argtypes) == args, name
+    # which declarations end in a stream, and which return int64_t: read straight from the header's text (each macro body
+    # with the suffixes it is instantiated with), not from the parser under test
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "gfla_hip.h")).read(), flags=re.S).replace("\\\n", " ")
+    with_stream, pointer_last, returns_i64 = set(), set(), set()
+    scopes = [(("",), "\n".join(line for line in text.splitlines() if not line.startswith("#")))]      # plain declarations
+    for macro, body in re.findall(r"^#define (GFLA_DECL_\w+)\(SFX, T\)(.*)$", text, flags=re.M):        # and each macro's
+        scopes.append(([sfx for sfx in re.findall(macro + r"\((\w+), \w+\)", text) if sfx != "SFX"], body))
+    for suffixes, scope in scopes:
+        for ret, name, args in re.findall(r"\b(int64_t|int|const char \*)\s*(gfla_[\w#]+)\(([^)]*)\)\s*;", scope):
+            names = [name.replace("##SFX", sfx) for sfx in suffixes]
+            if re.search(r"gfla_stream_t stream\s*$", args):
+                with_stream.update(names)
+            elif "*" in args.split(",")[-1]:   # gfla_*_geometry's `int64_t *out`, gfla_fc_wino_debug_buffer's `void *buffer`
+                pointer_last.update(names)
+            if ret == "int64_t":
+                returns_i64.update(names)
+    symbols = gfla.exported_symbols()
+    assert len(symbols) == len(set(symbols)) == 154 and (with_stream | pointer_last | returns_i64) <= set(symbols)
+    assert len(with_stream) == 130 and len(returns_i64) == 12          # counted by hand in the header
+    assert pointer_last == {"gfla_big_plane_geometry", "gfla_aggregate_fwd_geometry", "gfla_fc_geometry", "gfla_fc_wino_debug_buffer",
+                            "gfla_instance_norm_geometry", "gfla_head_conv3x3_geometry"}
+    for name in symbols:
+        fn = getattr(handle, name)
+        assert fn.argtypes is not None, name
+        last_is_pointer = len(fn.argtypes) > 0 and fn.argtypes[-1] is P
+        assert last_is_pointer == (name in with_stream or name in pointer_last), name
+        assert (fn.restype is L) == (name in returns_i64), name
+        assert fn.restype in (I, L) or name == "gfla_status_string", name
+    assert handle.gfla_status_string.restype is ctypes.c_char_p
+    # constants come from the header as well
+    assert (_lib.PATH_BE_BWD_LDS, _lib.PATH_FC_BWD_MODE0, _lib.PATH_GEMM_F64, _lib.PATH_COUNT) == (0, 7, 20, 22)
+    assert _lib.fc_path(3) == 5 and _lib.fc_path(2, backward=True) == 9 and _lib.fc_path(5) == 18
+
+
+def test_header_parser_is_strict():
+    from global_flow_local_attention_amd import _lib
+    fns, consts = _lib.parse_header("enum e { A = 1, B = -2 };\n#define N 7\nint64_t gfla_f(const float *x, int n, gfla_stream_t stream);")
+    assert fns == {"gfla_f": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])}
+    assert consts == {"A": 1, "B": -2, "N": 7}
+    for decl in ("int gfla_f(float x, int n)",           # float by value: no such argument in this ABI
+                 "int gfla_f(int64_t n, size_t m)",
+                 "int gfla_f(n)",
+                 "float gfla_f(int n)",                  # unknown return types
+                 "void *gfla_f(int n)",
+                 "struct gfla_s { int a; }"):            # neither a declaration, a typedef nor an enum
+        with pytest.raises(ValueError) as info:
+            _lib.parse_header("int gfla_ok(int n);\n%s;\n" % decl)
+        assert decl.split(";")[0] in str(info.value), (decl, str(info.value))
+
+
+def test_workspace_helper(gfla, monkeypatch):
+    """_lib.workspace on a stub library: a refusal of the size query is an exception that names the op, never a size handed
+    to torch.empty, and the buffer is never empty (an empty tensor's pointer is NULL)."""
+    import types
+    from global_flow_local_attention_amd import _lib
+    asked = []
+
+    def query(answer):
+        def fn(*sizes):
+            asked.append(sizes)
+            return answer
+        return fn
+    stub = types.SimpleNamespace(gfla_status_string=_lib.lib().gfla_status_string, q_unsupported=query(-3), q_shape=query(-2),
+                                 q_null=query(-1), q_zero=query(0), q_some=query(1000))
+    monkeypatch.setattr(_lib, "_lib", stub)
+    ref = torch.zeros(1)
+    with pytest.raises(_lib.Unsupported, match="some op"):
+        _lib.workspace("q_unsupported", ref, 1, 2, what="some op")
+    for name in ("q_shape", "q_null"):
+        with pytest.raises(ValueError, match="some op") as info:
+            _lib.workspace(name, ref, 1, 2, what="some op")
+        assert not isinstance(info.value, _lib.Unsupported)
+        assert _lib.lib().gfla_status_string(-2 if name == "q_shape" else -1).decode() in str(info.value)
+    buf = _lib.workspace("q_zero", ref, 3, what="some op")
+    assert buf.dtype == torch.uint8 and buf.numel() == 16 and buf.device == ref.device
+    assert _lib.workspace("q_some", ref, 4.0, True, what="x").numel() == 1000
+    assert asked[-1] == (4, 1) and all(type(v) is int for v in asked[-1])             # sizes cross as ints
+
+
 def test_argument_validation_without_gpu(gfla):
     from global_flow_local_attention_amd import _lib
     L = _lib.lib()

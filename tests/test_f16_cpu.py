@@ -9,7 +9,12 @@ import torch
 def test_every_f16_symbol_resolves(gfla):
     from global_flow_local_attention_amd import _lib
     handle = ctypes.CDLL(_lib.LIB_PATH)
-    names = ["%s_f16" % base for base in _lib._SIGNATURES]
+    bases = ("gfla_block_extractor_fwd", "gfla_block_extractor_bwd", "gfla_block_extractor_unfold_fwd",
+             "gfla_block_extractor_unfold_bwd", "gfla_local_attn_reshape_fwd", "gfla_local_attn_reshape_bwd",
+             "gfla_resample2d_fwd", "gfla_resample2d_bwd", "gfla_local_attn_aggregate_fwd", "gfla_local_attn_aggregate_bwd",
+             "gfla_local_attn_source_bwd", "gfla_flow_warp_fwd", "gfla_flow_warp_bwd", "gfla_instance_norm_fwd",
+             "gfla_instance_norm_bwd")
+    names = ["%s_f16" % base for base in bases]
     names += ["gfla_fc_forward_f16", "gfla_mask_blend_fwd_f16", "gfla_mask_blend_bwd_f16",
               "gfla_local_attn_aggregate_fwd_ws_f16"]
     for name in names:
