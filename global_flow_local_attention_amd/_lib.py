@@ -2,6 +2,7 @@
 
 include/gfla_hip.h is the single description of the C ABI: the argument and return types of every entry point, the
 dispatch-trace ids (enum gfla_path -> PATH_*), the status codes and ABI_VERSION are read from it, never restated here.
+Headers it includes (include/gfla_gen_conv.h) are read in the same way.
 
 The library is the only implementation of the ops: there is no Python/torch fallback.  If it
 is missing or fails to load, importing an op raises; if a call returns a non-zero status, a
@@ -18,6 +19,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # GFLA_HIP_LIBRARY: a differently built library (tools/ubench/build_agg_abl.sh timing variants); default = the in-tree build
 LIB_PATH = os.environ.get("GFLA_HIP_LIBRARY") or os.path.join(_PKG, "libgfla_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfla_hip.h")   # csrc/Makefile: ../../include/gfla_hip.h
+# headers gfla_hip.h includes, in the same dialect: their entry points are bound as well (extension_symbols)
+EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "gfla_gen_conv.h"),)
 _lib = None
 
 # the types the ABI is written in; a pointer of any pointee crosses as c_void_p
@@ -77,14 +80,17 @@ def parse_header(text):
     return functions, constants
 
 
-def _read_header():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError("include/gfla_hip.h, the description of the C ABI, is missing (%s)" % HEADER_PATH)
-    with open(HEADER_PATH) as f:
+def _read_header(path=HEADER_PATH):
+    if not os.path.exists(path):
+        raise RuntimeError("include/%s, the description of the C ABI, is missing (%s)" % (os.path.basename(path), path))
+    with open(path) as f:
         return parse_header(f.read())
 
 
 _FUNCTIONS, _CONSTANTS = _read_header()   # once per process
+_EXTENSION_FUNCTIONS = {}
+for _path in EXTENSION_HEADER_PATHS:
+    _EXTENSION_FUNCTIONS.update(_read_header(_path)[0])
 ABI_VERSION = _CONSTANTS["GFLA_ABI_VERSION"]
 _ERR_UNSUPPORTED = _CONSTANTS["GFLA_ERR_UNSUPPORTED"]
 # dispatch-trace ids: GFLA_PATH_X of enum gfla_path is PATH_X here (PATH_BE_BWD_LDS ... PATH_COUNT)
@@ -94,6 +100,11 @@ globals().update((name[len("GFLA_"):], value) for name, value in _CONSTANTS.item
 def exported_symbols():
     """Every symbol include/gfla_hip.h declares."""
     return list(_FUNCTIONS)
+
+
+def extension_symbols():
+    """Every symbol the headers included by gfla_hip.h declare (EXTENSION_HEADER_PATHS)."""
+    return list(_EXTENSION_FUNCTIONS)
 
 
 def build(force=False):
@@ -113,7 +124,7 @@ def lib():
                 "libgfla_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C global_flow_local_attention_amd/csrc`. There is no fallback path." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _FUNCTIONS.items():
+        for name, (restype, argtypes) in list(_FUNCTIONS.items()) + list(_EXTENSION_FUNCTIONS.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = handle

@@ -21,46 +21,15 @@
 // Data gradient (the weights are frozen: no weight gradient): dX = conv3x3(g [y > 0], w mirrored, Cin <-> Cout), the same
 // kernel with the ReLU mask of the saved output applied to g while it is staged; no bias, no ReLU in the epilogue.
 // 16-bit outputs are rounded to nearest even once, from the float32 accumulator.  No atomics anywhere.
-#include "gfla_common.h"
+#include "conv_mma.h"
 
 namespace gfla {
 
-typedef float cv_f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 cv_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cv_bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kCvRec = 32;        // bytes of one pixel (or one output channel) of one chunk
 constexpr int kCvMB = 2;          // 32-channel MFMA tiles per wave
 constexpr int kCvNB = 2;          // 32-pixel MFMA tiles per wave
 constexpr int kCvItems = 11;      // 4-byte words of the halo tile a thread stages per chunk: 8 * 340 / 256 rounded up
 constexpr int kCvMaxHalo = kCvItems * kBlock / 8;
 constexpr int64_t kCvMaxC = 1 << 16;
-
-template <typename T>
-constexpr int cv_ck() { return kCvRec / (int)sizeof(T); }
-
-template <typename T>
-__device__ __forceinline__ cv_f32x16 cv_mma(uint4 a, uint4 b, cv_f32x16 acc) {
-  if constexpr (__is_same(T, float)) {
-    const float4 fa = __builtin_bit_cast(float4, a), fb = __builtin_bit_cast(float4, b);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.x, fb.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.y, fb.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.z, fb.z, acc, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(fa.w, fb.w, acc, 0, 0, 0);
-  } else if constexpr (__is_same(T, f16_t)) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cv_f16x8, a), __builtin_bit_cast(cv_f16x8, b), acc, 0,
-                                                  0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cv_bf16x8, a), __builtin_bit_cast(cv_bf16x8, b), acc,
-                                                   0, 0, 0);
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ uint32_t cv_bits(const T *p) {
-  if constexpr (__is_same(T, float)) return __float_as_uint(*p);
-  else return p->bits;
-}
 
 // the tile a launch uses: TW = 1 << tw_log2 columns, WM waves along the output channels
 struct CvTile {

@@ -44,7 +44,7 @@ def _bind_vgg(cls, vgg):
 
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
             dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False, fuse_instance_norm=False,
-            fuse_heads=False):
+            fuse_heads=False, inference_convs=False):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -84,7 +84,14 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     (LeakyReLU -> ReflectionPad2d(1) -> Conv2d(ngf, 3, 3) -> Tanh; state-dict keys `conv1.*` and `model.2.*` and the
     Parameter objects unchanged), and `attn_output` of PoseFlowNet / FaceFlowNet / ShapeNetFlowNet computes the flow field
     and its sigmoid mask in one launch (head_conv.flow_mask_heads).  Imports the reference's generator module.  Heads built
-    with spectral norm or coordinate convolutions keep the reference's modules.  False (the default) changes nothing."""
+    with spectral norm or coordinate convolutions keep the reference's modules.  False (the default) changes nothing.
+
+    inference_convs: True (or "auto" / "torch", the `impl` of gen_conv.py) wraps the constructors of the reference's
+    EncoderBlock, ResBlock, ResBlockDecoder and Jump so that a generator built AFTER install() has its 3x3, 4x4 stride-2 and
+    transposed 3x3 convolutions as InferenceConv (gen_conv.py: csrc/gen_conv.hip under eval() / torch.no_grad(), the torch
+    composition whenever a gradient could be asked for), and replaces ResBlock.forward / ResBlockDecoder.forward by versions
+    that add the residual in the last convolution's epilogue.  Indices, state-dict keys and the Parameter objects are
+    unchanged.  Composes with fuse_instance_norm and fuse_heads.  False (the default) changes nothing."""
     from . import extractor_attn as _ea
     if strict_mfma is None and allow_vendor_fallback is not None:
         strict_mfma = not allow_vendor_fallback
@@ -139,6 +146,9 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
         impl = fuse_heads if isinstance(fuse_heads, str) else "auto"
         patch_reference_outputs(base_function, impl)
         patch_reference_flow_heads(importlib.import_module("model.networks.generator"), impl)
+    if base_function is not None and inference_convs:
+        from .gen_conv import patch_reference_convs
+        patch_reference_convs(base_function, inference_convs if isinstance(inference_convs, str) else "auto")
     if vgg is not None:
         from . import losses
         external_function = importlib.import_module("model.networks.external_function")

@@ -844,6 +844,9 @@ int gfla_head_conv3x3_bwd_bf16(const uint16_t *x, const float *w, const uint16_t
                                int64_t Cin, int64_t Cout, int64_t C0, int64_t H, int64_t W, int pad_mode, int pre_act,
                                double pre_slope, int tanh_mask, int sigmoid_mask, gfla_stream_t stream);
 
+/* ---- generator inference convolutions (csrc/gen_conv.hip): gfla_gen_conv_*, declared and documented in gfla_gen_conv.h ---- */
+#include "gfla_gen_conv.h"
+
 #ifdef __cplusplus
 }
 #endif
