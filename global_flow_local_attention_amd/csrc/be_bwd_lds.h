@@ -294,6 +294,17 @@ __global__ __launch_bounds__(kLdsThreads) void be_bwd_lds_kernel(
   }
 }
 
+// Launch geometry of be_bwd_lds_kernel (the launcher below and gfla_lds_plane_geometry use it).  The factored / unfold forms
+// are only produced for planes that fit; the tensor form may window.  16-bit storage (elem_size 2): whole planes, one owner per
+// plane (no atomics on the planes).
+inline PlaneGeo be_bwd_lds_geometry(int mode, int elem_size, int acc_size, bool need_src, bool need_flow, int64_t B, int64_t C,
+                                    int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int K) {
+  const int bytes = (need_src ? (int)sizeof(lds_acc_t) : 0) + (need_flow ? acc_size : 0);
+  const bool half = elem_size == 2;
+  return (mode == kGoutTensor && !half) ? lds_geometry(Hs, Ws, bytes, B, C, Hf, Wf, K + 3, 1)
+                                        : plane_geometry(Hs * Ws, bytes, B, C, Hf * Wf, !half, 1);
+}
+
 // Launch helper.  mode = kGoutTensor / kGoutAttn / kGoutUnfold (see GoutRow).  *done = false when the
 // planes do not fit in LDS.
 template <typename T, int K>
@@ -303,11 +314,7 @@ static int launch_be_bwd_lds(int mode, const T *src, const T *flow, const T *gou
                              const T *gout2 = nullptr, const unsigned *skip_stat = nullptr, unsigned skip_limit = 0) {
   using A = typename Num<T>::acc;
   *done = false;
-  const int bytes = (gsrc ? (int)sizeof(lds_acc_t) : 0) + (gflow ? (int)sizeof(A) : 0);
-  // the factored / unfold forms are only produced for planes that fit; the tensor form may window
-  constexpr bool kBf16 = sizeof(T) == 2;  // bf16 storage: whole planes, one owner per plane (no atomics on the planes)
-  PlaneGeo g = (mode == kGoutTensor && !kBf16) ? lds_geometry(Hs, Ws, bytes, B, C, Hf, Wf, K + 3, 1)
-                                               : plane_geometry(Hs * Ws, bytes, B, C, Hf * Wf, !kBf16, 1);
+  PlaneGeo g = be_bwd_lds_geometry(mode, (int)sizeof(T), (int)sizeof(A), gsrc != nullptr, gflow != nullptr, B, C, Hs, Ws, Hf, Wf, K);
   if (g.G == 0) return GFLA_OK;
   const int64_t blocks = B * g.ngroups * g.split;
   if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;

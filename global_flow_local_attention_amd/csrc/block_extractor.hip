@@ -636,7 +636,7 @@ static int block_extractor_unfold_fwd(const T *src, const T *flow, T *out, int64
   int st = unfold_check(B, C, Hs, Ws, Hf, Wf, k, sizeof(A));
   if (st != GFLA_OK) return st;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  PlaneGeo g = plane_geometry(Hs * Ws, sizeof(A), B, C, Hf * Wf, true);
+  PlaneGeo g = unfold_fwd_geometry(sizeof(A), B, C, Hs, Ws, Hf, Wf);
   const int64_t blocks = B * g.ngroups * g.split;
   if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
   int64_t cs, bs;
@@ -706,6 +706,37 @@ int gfla_block_extractor_bwd_f64(const double *s, const double *f, const double 
                                  double *gf, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
                                  int64_t Hf, int64_t Wf, int k, gfla_stream_t st) {
   return gfla::block_extractor_bwd<double>(s, f, go, gs, gf, B, C, Hs, Ws, Hf, Wf, k, st);
+}
+/* Host-side launch geometry of the planes-in-LDS kernels (include/gfla_lds_plane.h; no GPU needed).  The geometry itself comes
+ * from the functions the launchers call; what is written out here is only whether the dispatch in front of a launcher hands it
+ * the call at all (big-plane regime, keys 2 / 6, whole-plane requirements). */
+int gfla_lds_plane_geometry(int op, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k, int dilation,
+                            int elem_size, int needs, int64_t *out) {
+  if (!out) return GFLA_ERR_NULL_POINTER;
+  if (op < 0 || op > 7 || B <= 0 || C <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || k < 1 || dilation < 1 ||
+      (elem_size != 2 && elem_size != 4 && elem_size != 8) || (op <= 3 && (needs & 3) == 0) || (op >= 5 && k < 2))
+    return GFLA_ERR_BAD_SHAPE;
+  const int acc = elem_size == 8 ? 8 : 4;
+  gfla::PlaneGeo g{0, 0, 1, 0, 0, -1};
+  if (op <= 3) {
+    const bool tile = op == 0 && elem_size != 2 && gfla::tuning(2) != 1 &&
+                      gfla::big_plane_regime(B, C, Hs * Ws * (int64_t)(8 + acc), gfla::lds_budget());
+    if (k <= 5 && !tile && (gfla::tuning(2) != 1 || elem_size == 2 || op != 0))
+      g = gfla::be_bwd_lds_geometry(op, elem_size, acc, (needs & 1) != 0, (needs & 2) != 0, B, C, Hs, Ws, H, W, k);
+  } else if (op == 4) {
+    if (k <= 5 && Hs * Ws * (int64_t)acc <= gfla::lds_budget()) g = gfla::unfold_fwd_geometry(acc, B, C, Hs, Ws, H, W);
+  } else if (op == 5) {
+    if (gfla::tuning(6) != 1 && !gfla::big_plane_regime(B, C, Hs * Ws * (int64_t)acc, gfla::lds_budget()))
+      g = gfla::rs_gather_geometry(acc, B, C, Hs, Ws, H, W, k, dilation, 1);
+  } else {
+    const bool big = elem_size != 2 && gfla::tuning(6) != 1 && gfla::big_plane_regime(B, C, Hs * Ws * (int64_t)8, gfla::lds_budget());
+    const gfla::PlaneGeo pg1 = gfla::rs_scatter_geometry(elem_size, B, C, Hs, Ws, H, W, k, dilation);
+    const gfla::PlaneGeo pg2 = gfla::rs_gather_geometry(acc, B, C, Hs, Ws, H, W, k, dilation, 0);
+    if (!big && (gfla::tuning(6) != 1 || elem_size == 2) && pg1.G > 0 && pg2.G > 0) g = op == 6 ? pg1 : pg2;
+  }
+  const int64_t v[6] = {g.G, g.ngroups, g.split, g.per, g.margin, g.lds_bytes};
+  for (int i = 0; i < 6; ++i) out[i] = g.G > 0 ? v[i] : 0;
+  return GFLA_OK;
 }
 int gfla_unfold_supported(int64_t Hs, int64_t Ws, int k, int elem_size) {
   const int acc = elem_size == 8 ? 8 : 4;

@@ -105,7 +105,9 @@ inline PlaneGeo plane_geometry(int64_t plane_elems, int bytes_per_elem, int64_t 
     const int64_t wgs = B * g.ngroups;
     while (wgs * split < 4 * kNumCU && work_items / (split * 2) >= 2 * kLdsThreads && split < 64) split *= 2;
   }
-  if (tuning(5) > 0) split = tuning(5);
+  // key 5 forces a split only where the kernel can flush a shared plane (atomics); a caller that cannot split (16-bit
+  // storage: one owner per plane, plain read-modify-write) keeps split = 1 whatever the key says
+  if (allow_split && tuning(5) > 0) split = tuning(5);
   g.split = split;
   g.per = (int)ceil_div(work_items, split);
   g.lds_bytes = (unsigned)(G * per_channel);
@@ -147,6 +149,24 @@ inline PlaneGeo lds_geometry(int64_t H, int64_t W, int bytes_per_elem, int64_t B
   if (g.G > 0) return g;
   if (tuning(7) == 1) return g;  // windows disabled
   return band_geometry(H, W, bytes_per_elem, B, C, Hf, items_per_row, k_span);
+}
+
+// The geometry of each launcher of the family, in one place: the launchers call these and gfla_lds_plane_geometry
+// (include/gfla_lds_plane.h) hands the same answers to the tests.  acc_size = sizeof(Num<T>::acc), elem_size = sizeof(T).
+// Unfold forward: whole gather planes only.
+inline PlaneGeo unfold_fwd_geometry(int acc_size, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf) {
+  return plane_geometry(Hs * Ws, acc_size, B, C, Hf * Wf, true);
+}
+// resample2d: forward and d/d input2 gather from planes of the arithmetic type, d/d input1 scatters into double planes.
+// 16-bit storage: the scatter planes are whole and have one owner each (the flush is a plain read-modify-write).
+inline PlaneGeo rs_gather_geometry(int acc_size, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k,
+                                   int dil, int chunk) {
+  return lds_geometry(Hi, Wi, acc_size, B, C, H, W, (k - 1) * dil + 1, chunk);
+}
+inline PlaneGeo rs_scatter_geometry(int elem_size, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k,
+                                    int dil) {
+  return elem_size == 2 ? plane_geometry(Hi * Wi, sizeof(lds_acc_t), B, C, H * W, false)
+                        : lds_geometry(Hi, Wi, sizeof(lds_acc_t), B, C, H, W, (k - 1) * dil + 1);
 }
 
 // Launch a kernel with `lds` bytes of dynamic LDS; above 64 KB the per-kernel limit has to be raised first.

@@ -89,10 +89,12 @@ __device__ __forceinline__ void rs_fwd_pixel(const Taps<A, KH> &t, const PT *__r
     return tiny ? val / t.sum : val * inv;
   };
   if constexpr (std::is_same<A, float>::value && std::is_same<PT, float>::value && N == 4) {
-    // kernel_size 4 / 5 in float, no clamped column in the wave: the sixteen normalised weights wy[r] wx[q] / sum once per
-    // pixel, then per channel 8 reads of pairs + 8 packed multiply-adds (the channel loop was ~60 instructions, 9 of the
-    // forward's 21 us at (1,64,256,176))
-    if (__all(consecutive)) {
+    // kernel_size 4 / 5 in float: the sixteen normalised weights wy[r] wx[q] / sum once per pixel, then per channel 8 packed
+    // multiply-adds; where no lane of the wave has a tap column clamped, 8 reads of pairs feed them (the channel loop was
+    // ~60 instructions, 9 of the forward's 21 us at (1,64,256,176)).  A wave with a clamped column reads its taps one by one
+    // and combines them with the SAME arithmetic: which pixels share a wave depends on the launch geometry (G, split, row
+    // windows), and a pixel's result must not (tests/test_plane_geometry_gpu.py: forwards bit-identical over geometries).
+    {
       typedef float v2f __attribute__((ext_vector_type(2)));
       v2f w2[N][2];
 #pragma unroll
@@ -123,13 +125,27 @@ __device__ __forceinline__ void rs_fwd_pixel(const Taps<A, KH> &t, const PT *__r
       // (A software pipeline over the channels -- channel c + 1's taps requested before channel c's are combined -- was
       // measured and dropped: 19.9 -> 25.6 us at (1,64,256,176); the second register set costs more waves than the overlap
       // buys.  profiles/r5_config2_sweeps.txt)
-      for (int c = 0; c < nch; ++c) {
-        A v[N][N];
-        request(base, v);
-        pin_taps<A, N>(v);
-        *o = Num<T>::from(combine2(v));
-        base += plane_sz;
-        o += ostride;
+      if (__all(consecutive)) {
+        for (int c = 0; c < nch; ++c) {
+          A v[N][N];
+          request(base, v);
+          pin_taps<A, N>(v);
+          *o = Num<T>::from(combine2(v));
+          base += plane_sz;
+          o += ostride;
+        }
+      } else {
+        for (int c = 0; c < nch; ++c) {
+          A v[N][N];
+#pragma unroll
+          for (int r = 0; r < N; ++r)
+#pragma unroll
+            for (int q = 0; q < N; ++q) v[r][q] = plane[ro[r] + co[q]];
+          pin_taps<A, N>(v);
+          *o = Num<T>::from(combine2(v));
+          plane += plane_sz;
+          o += ostride;
+        }
       }
       return;
     }
@@ -923,7 +939,7 @@ static int resample2d_fwd(const T *in1, const T *in2, T *out, int64_t B, int64_t
     }
   }
   if (tuning(6) != 1) {
-    PlaneGeo pg = lds_geometry(Hi, Wi, sizeof(A), B, C, H, W, (k - 1) * dil + 1, 1);
+    PlaneGeo pg = rs_gather_geometry(sizeof(A), B, C, Hi, Wi, H, W, k, dil, 1);
     if (pg.G > 0) {
       const int64_t blocks = B * pg.ngroups * pg.split;
       if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
@@ -994,9 +1010,8 @@ static int resample2d_bwd(const T *in1, const T *in2, const T *gout, T *gin1, ty
     }
   }
   // double scatter planes.  bf16 storage: whole planes, one owner each (the flush is a plain read-modify-write)
-  PlaneGeo pg1 = kBf16 ? plane_geometry(Hi * Wi, sizeof(lds_acc_t), B, C, H * W, false)
-                       : lds_geometry(Hi, Wi, sizeof(lds_acc_t), B, C, H, W, (k - 1) * dil + 1);
-  PlaneGeo pg2 = lds_geometry(Hi, Wi, sizeof(A), B, C, H, W, (k - 1) * dil + 1);          // gather planes
+  PlaneGeo pg1 = rs_scatter_geometry((int)sizeof(T), B, C, Hi, Wi, H, W, k, dil);
+  PlaneGeo pg2 = rs_gather_geometry(sizeof(A), B, C, Hi, Wi, H, W, k, dil, 0);            // gather planes
   // flag word `trunc`: bit 0 = the reference's int() truncation quirk; bit 1 = grad_in1 arrives UNINITIALISED and is to be
   // overwritten -- honoured by the kernels where every element has exactly one writer, zero-filled here otherwise
   const bool lds_path = (tuning(6) != 1 || kBf16) && pg1.G > 0 && pg2.G > 0;

@@ -75,7 +75,9 @@ const char *gfla_status_string(int status);
  *   key 2: block_extractor backward  0 auto, 1 force global-atomics kernel
  *   key 3: aggregate fwd/bwd         0 auto, 1 force global kernels
  *   key 4: cap on G, the channel planes one workgroup keeps in LDS (0 auto)
- *   key 5: split, workgroups sharing one (b, channel group) (0 auto)
+ *   key 5: split, workgroups sharing one (b, channel group) (0 auto).  Ignored where a kernel cannot split: the 16-bit
+ *          backward kernels flush each plane from one owner (block_extractor / aggregation / unfold backward, resample2d
+ *          d/d input1), so they keep split = 1
  *   key 6: resample2d fwd/bwd        0 auto, 1 force global kernels
  *   key 7: row windows for planes larger than the LDS budget   0 on, 1 off (use global kernels)
  *   key 10: LDS budget per workgroup in KB (0 = 64; up to 160)
@@ -846,6 +848,10 @@ int gfla_head_conv3x3_bwd_bf16(const uint16_t *x, const float *w, const uint16_t
 
 /* ---- generator inference convolutions (csrc/gen_conv.hip): gfla_gen_conv_*, declared and documented in gfla_gen_conv.h ---- */
 #include "gfla_gen_conv.h"
+
+/* ---- launch geometry of the planes-in-LDS kernels (csrc/lds_plane.h), for tests: gfla_lds_plane_geometry, declared and
+ * documented in gfla_lds_plane.h ---- */
+#include "gfla_lds_plane.h"
 
 #ifdef __cplusplus
 }
