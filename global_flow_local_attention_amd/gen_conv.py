@@ -22,8 +22,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from ._conv_common import SFX as _SFX, SRC_TYPE as _SRC_TYPE, autocast_dtype, cached, rounded_bias
 from .head_conv import MAX_COUT as _HEAD_MAX_COUT
-from .vgg import _SFX, _SRC_TYPE, _cached
 
 IMPLS = _lib.IMPLS
 PADDINGS = ("zeros", "reflect")
@@ -43,8 +43,7 @@ def out_size(geometry, H, W):
 
 
 def packed_weights(weight, dtype, geometry):
-    """torch's `weight` ((Cout,Cin,k,k); T2K3: (Cin,Cout,3,3)) packed for the kernels in compute type `dtype`.  Cached per
-    parameter (vgg._cached): a frozen network packs once."""
+    """torch's `weight` ((Cout,Cin,k,k); T2K3: (Cin,Cout,3,3)) packed in compute type `dtype`, once per frozen parameter."""
     def make():
         w = weight.detach().contiguous()
         cout, cin = (w.size(1), w.size(0)) if geometry == T2K3 else (w.size(0), w.size(1))
@@ -53,12 +52,7 @@ def packed_weights(weight, dtype, geometry):
         _lib.call("gfla_gen_conv_pack_weights_" + _SFX[dtype], w, _lib.ptr(w), _SRC_TYPE[w.dtype], _lib.ptr(packed), cout,
                   cin, geometry)
         return packed
-    return _cached(weight, "gen_conv%d" % geometry, dtype, make)
-
-
-def _rounded_bias(bias, dtype):
-    """the bias as the kernel reads it: rounded to the compute type, held in float32"""
-    return _cached(bias, "gen_conv_b", dtype, lambda: bias.detach().to(dtype).float().contiguous())
+    return cached(weight, "gen_conv%d" % geometry, dtype, make)
 
 
 def _validate(x, weight, bias, geometry, padding, pre_slope, add):
@@ -124,14 +118,13 @@ def _kernel_inputs(x, weight, bias, add):
 
 def _launch(x, weight, bias, geometry, padding, pre_slope, add, cout, ho, wo):
     if torch.is_autocast_enabled():
-        get = getattr(torch, "get_autocast_dtype", None)
-        x = x.to(get("cuda") if get is not None else torch.get_autocast_gpu_dtype())
+        x = x.to(autocast_dtype())
     if x.dtype not in _SFX:
         raise _lib.Unsupported("%s: no kernel for %s" % (_NAMES[geometry], x.dtype))
     x = x.contiguous()
     B, Cin, H, W = x.shape
     wp = packed_weights(weight, x.dtype, geometry)
-    b32 = None if bias is None else _rounded_bias(bias, x.dtype)
+    b32 = None if bias is None else rounded_bias(bias, x.dtype, "gen_conv_b")
     if add is not None:
         add = add.detach().to(x.dtype).contiguous()
     y = x.new_empty((B, cout, ho, wo))

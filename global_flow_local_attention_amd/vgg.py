@@ -1,4 +1,4 @@
-"""VGG19 feature extractor on the library's own kernels (csrc/conv3x3.hip, csrc/maxpool2x2.hip).
+"""VGG19 feature extractor on the library's own kernels (csrc/conv3x3.hip on csrc/conv_igemm.h, csrc/maxpool2x2.hip).
 
 The reference builds its extractor from torchvision (`VGG19`, external_function.py:323-444): sixteen 3x3 convolutions
 with ReLU and four 2x2 max pools, frozen, which VGGLoss / StyleLoss / PerceptualLoss / PerceptualCorrectness push two
@@ -7,8 +7,6 @@ state-dict keys, running `conv3x3 + bias + ReLU` as an implicit GEMM on the matr
 kernels: no vendor convolution library on the path.  Weights are not part of this package: load a state dict saved from
 the reference's class (`load_state_dict`, strict) or torchvision's (`load_torchvision_state_dict`).
 """
-import weakref
-
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -16,10 +14,9 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._conv_common import SFX as _SFX, SRC_TYPE as _SRC_TYPE, autocast_dtype, cached, rounded_bias
 
 IMPLS = _lib.IMPLS
-_SFX = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
-_SRC_TYPE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 # torchvision's configuration E: index in `features` of every convolution, by stage; a pool closes stages 1-4
 _CONV_INDEX = ((0, 2), (5, 7), (10, 12, 14, 16), (19, 21, 23, 25), (28, 30, 32, 34))
@@ -31,23 +28,6 @@ _SLICES = (("relu1_1", (0, 1)), ("relu1_2", (2, 3)), ("relu2_1", (4, 5, 6)), ("r
            ("relu4_1", (18, 19, 20)), ("relu4_2", (21, 22)), ("relu4_3", (23, 24)), ("relu4_4", (25, 26)),
            ("relu5_1", (27, 28, 29)), ("relu5_2", (30, 31)), ("relu5_3", (32, 33)), ("relu5_4", (34, 35)))
 LAYERS = tuple(name for name, _ in _SLICES)
-
-# packed weights and rounded biases of frozen parameters: (data_ptr, _version, dtype, device, shape, what) ->
-# (weak reference to the parameter, tensor)
-_PACK_CACHE = {}
-_PACK_CACHE_MAX = 512
-
-
-def _cached(param, what, dtype, make):
-    key = (param.data_ptr(), param._version, dtype, param.device, tuple(param.shape), what)
-    hit = _PACK_CACHE.get(key)
-    if hit is not None and hit[0]() is param:
-        return hit[1]
-    if len(_PACK_CACHE) >= _PACK_CACHE_MAX:
-        _PACK_CACHE.clear()
-    value = make()
-    _PACK_CACHE[key] = (weakref.ref(param), value)
-    return value
 
 
 def packed_weights(weight, dtype, layout):
@@ -61,12 +41,7 @@ def packed_weights(weight, dtype, layout):
         _lib.call("gfla_conv3x3_pack_weights_" + _SFX[dtype], w, _lib.ptr(w), _SRC_TYPE[w.dtype], _lib.ptr(packed), cout, cin,
                   layout)
         return packed
-    return _cached(weight, "w%d" % layout, dtype, make)
-
-
-def _rounded_bias(bias, dtype):
-    """the bias as the kernel reads it: rounded to the compute type, held in float32"""
-    return _cached(bias, "b", dtype, lambda: bias.detach().to(dtype).float().contiguous())
+    return cached(weight, "w%d" % layout, dtype, make)
 
 
 class Conv3x3ReluFunction(Function):
@@ -90,7 +65,7 @@ class Conv3x3ReluFunction(Function):
         x = x.contiguous()
         B, Cin, H, W = x.shape
         Cout = weight.size(0)
-        wp, b32 = packed_weights(weight, x.dtype, 0), _rounded_bias(bias, x.dtype)
+        wp, b32 = packed_weights(weight, x.dtype, 0), rounded_bias(bias, x.dtype, "b")
         y = x.new_empty((B, Cout, H, W))
         _lib.call("gfla_conv3x3_relu_fwd_" + _SFX[x.dtype], x, _lib.ptr(x), _lib.ptr(wp), _lib.ptr(b32), _lib.ptr(y), B, Cin,
                   Cout, H, W)
@@ -251,8 +226,7 @@ class VGG19Features(nn.Module):
 
     def forward(self, image):
         if image.is_cuda and torch.is_autocast_enabled():
-            get = getattr(torch, "get_autocast_dtype", None)
-            image = image.to(get("cuda") if get is not None else torch.get_autocast_gpu_dtype())
+            image = image.to(autocast_dtype())
         out, x = {}, image
         for name in LAYERS:
             x = getattr(self, name)(x)

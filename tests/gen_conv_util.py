@@ -1,5 +1,5 @@
 """Shared by the generator-convolution tests: float64 host references built from the very tensors the kernels read, the
-derived error bar, a pure-Python emulation of the three packed index maps of csrc/gen_conv.hip and of what the kernel
+derived error bar, a pure-Python emulation of the three packed index maps of csrc/conv_igemm.h and of what the kernel
 computes from a packed array, and generator-shaped blocks (the documented structures of the reference's EncoderBlock,
 ResBlock, ResBlockDecoder, Jump and Output, written here: none of the reference's code)."""
 import torch
@@ -56,7 +56,71 @@ def bar(S, y64, K, dtype, has_add):
     return 2.0 * (K + 2 + (1 if has_add else 0)) * 2.0 ** -24 * S + UNIT[dtype] * y64.abs()
 
 
-# ---- emulation of the packed layouts (csrc/gen_conv.hip: gen_conv_pack_kernel, gen_conv_kernel) ------------------------
+# ---- the per-call cases and their seeded host inputs (test_gen_conv_gpu.py, conv_family_util.py) ----------------------
+DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+ALL = ("f32", "f16", "bf16")
+
+
+def _cases(rows, deep):
+    """(dtype name, shape, options) for every row in every dtype, plus the longest reduction in float32 and bfloat16"""
+    return [(n, s, o) for s, o in rows for n in ALL] + [(n, deep, {}) for n in ("f32", "bf16")]
+
+
+def case_id(v):
+    if isinstance(v, str):
+        return v
+    if isinstance(v, tuple):
+        return "x".join(map(str, v))
+    return "-".join(sorted(k if v[k] is True else "%s%s" % (k, v[k]) for k in v)) or "plain"
+
+
+# (B, Cin, Cout, H, W): first layer with one padded chunk; nothing a multiple of anything, tiles straddle both edges; all
+# halo; a map of two rows; several channel chunks and channel blocks with activation and addend
+S1K3_CASES = _cases([((1, 3, 64, 9, 7), {}), ((2, 20, 40, 33, 17), {}), ((2, 20, 40, 33, 17), {"reflect": True}),
+                     ((1, 64, 64, 1, 1), {}), ((1, 16, 32, 2, 40), {"reflect": True}),
+                     ((3, 128, 96, 16, 11), {"reflect": True, "slope": 0.1, "add": True})], (1, 512, 512, 4, 3))
+# odd both ways; the smallest map (one output pixel); three rows (the last one dropped) and more than two tiles across
+S2K4_CASES = _cases([((1, 3, 64, 10, 8), {}), ((2, 20, 40, 33, 17), {"slope": 0.1}), ((1, 21, 32, 2, 2), {}),
+                     ((1, 64, 64, 3, 70), {}), ((3, 128, 96, 16, 22), {})], (1, 512, 512, 8, 6))
+# one input pixel; odd sizes over several tiles with an addend; one row; the addend aliasing the output
+T2K3_CASES = _cases([((1, 5, 7, 1, 1), {}), ((2, 20, 40, 17, 9), {"add": True}), ((1, 16, 32, 1, 40), {}),
+                     ((3, 128, 96, 8, 11), {"alias": True})], (1, 512, 512, 4, 3))
+
+
+def conv_inputs(geometry, shape, dtype, seed, with_add):
+    B, Cin, Cout, H, W = shape
+    k = 4 if geometry == S2K4 else 3
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, Cin, H, W, generator=g).to(dtype)
+    wshape = (Cin, Cout, k, k) if geometry == T2K3 else (Cout, Cin, k, k)
+    fan = (4 if geometry == T2K3 else k * k) * Cin
+    w = (torch.randn(wshape, generator=g) * (2.0 / fan) ** 0.5).to(dtype)      # rounded as the packing does
+    b = (torch.randn(Cout, generator=g) * 0.2).to(dtype)
+    add = torch.randn((B, Cout) + out_size(geometry, H, W), generator=g).to(dtype) if with_add else None
+    return x, w, b, add
+
+
+def call(gfla, geometry, x, w, b, reflect=False, slope=None, add=None):
+    if geometry == S1K3:
+        return gfla.conv3x3(x, w, b, padding="reflect" if reflect else "zeros", pre_slope=slope, add=add)
+    if geometry == S2K4:
+        return gfla.conv4x4_down(x, w, b, pre_slope=slope)
+    return gfla.conv_transpose3x3_up(x, w, b, add=add, pre_slope=slope)
+
+
+def call_in_place(x, w, b, add):
+    """T2K3 through the C entry point with the addend's buffer as the output"""
+    from global_flow_local_attention_amd import _lib, gen_conv
+    x = x.contiguous()
+    B, Cin, H, W = x.shape
+    y = add.clone()
+    wp = gen_conv.packed_weights(w, x.dtype, T2K3)
+    _lib.call("gfla_gen_conv_fwd_" + _lib.SUFFIX[x.dtype], x, _lib.ptr(x), _lib.ptr(wp), _lib.ptr(b.float().contiguous()),
+              _lib.ptr(y), _lib.ptr(y), B, Cin, w.size(1), H, W, T2K3, 0, 0, 0.0)
+    return y
+
+
+# ---- emulation of the packed layouts (csrc/conv_igemm.h: conv_igemm_pack_kernel, conv_igemm_kernel) ------------------
 def packed_dims(cout, cin, ck):
     """(NCH, MP): chunks of the input channels and padded output channels"""
     return -(-cin // ck), -(-cout // 32) * 32

@@ -1,6 +1,6 @@
 """VGG19Features without a GPU: the exported symbols and their argument checks, the reference's state-dict keys and
 slicing, the float64 host route against golden values from the reference's own VGG19 class
-(tests/golden/make_vgg_golden.py), and the packed-weight index maps of csrc/conv3x3.hip against a direct convolution."""
+(tests/golden/make_vgg_golden.py), and the packed-weight index maps of csrc/conv_igemm.h against a direct convolution."""
 import ctypes
 
 import pytest

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import vgg_util as vu
+from vgg_util import conv_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -21,16 +22,6 @@ DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 CONV_SHAPES = [(1, 3, 64, 9, 7), (2, 20, 40, 33, 17), (1, 64, 64, 1, 1), (1, 16, 32, 1, 40), (3, 128, 96, 16, 11)]
 CONV_CASES = [(n, s) for s in CONV_SHAPES for n in ("f32", "f16", "bf16")] + \
              [(n, (1, 512, 512, 4, 3)) for n in ("f32", "bf16")]
-
-
-def conv_inputs(shape, dtype, seed):
-    B, Cin, Cout, H, W = shape
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, Cin, H, W, generator=g).to(dtype)
-    w = (torch.randn(Cout, Cin, 3, 3, generator=g) * (2.0 / (9 * Cin)) ** 0.5).to(dtype)   # rounded as the packing does
-    b = (torch.randn(Cout, generator=g) * 0.2).to(dtype)
-    gy = torch.randn(B, Cout, H, W, generator=g).to(dtype)
-    return x, w, b, gy
 
 
 @pytest.mark.parametrize("name,shape", CONV_CASES, ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)))

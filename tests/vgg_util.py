@@ -1,5 +1,5 @@
 """Shared by the VGG19 tests: the golden file, float64 host references with the derived error bars of the issue, an
-emulation of the packed-weight index maps of csrc/conv3x3.hip, and torchvision's configuration-E `features` stack."""
+emulation of the packed-weight index maps of csrc/conv_igemm.h, and torchvision's configuration-E `features` stack."""
 import os
 
 import numpy as np
@@ -68,7 +68,17 @@ def dgrad_ref64(g, y_kernel, w):
     return F.conv_transpose2d(gm, w, padding=1), F.conv_transpose2d(gm.abs(), w.abs(), padding=1)
 
 
-# ---- emulation of the packed layouts (csrc/conv3x3.hip: conv3x3_pack_kernel) -------------------------------------------
+def conv_inputs(shape, dtype, seed):
+    B, Cin, Cout, H, W = shape
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, Cin, H, W, generator=g).to(dtype)
+    w = (torch.randn(Cout, Cin, 3, 3, generator=g) * (2.0 / (9 * Cin)) ** 0.5).to(dtype)   # rounded as the packing does
+    b = (torch.randn(Cout, generator=g) * 0.2).to(dtype)
+    gy = torch.randn(B, Cout, H, W, generator=g).to(dtype)
+    return x, w, b, gy
+
+
+# ---- emulation of the packed layouts (csrc/conv_igemm.h: conv_igemm_pack_kernel) -------------------------------------
 def packed_dims(cout, cin, layout, ck):
     """(NCH, MP): chunks of the reduction axis and padded result channels"""
     m, k = (cin, cout) if layout else (cout, cin)

@@ -6,8 +6,8 @@ fed with the map the network produces there), for an (8, 3, 256, 176) image in f
 
 usage: python tools/bench_vgg19.py [--iters N] [--batch B] [--out profiles/vgg19_bench.jsonl]
 Every shape is warmed up on both routes first; the two routes alternate inside each round; one HIP event pair around
-each call; medians are reported (us).  TF/s = 2 * 9 * Cin * Cout * B * H * W (the convolution's own operations) over the
-median time of the call: a rate of the whole call, not a kernel's share of peak."""
+each call; medians and quartiles are reported (us).  TF/s = 2 * 9 * Cin * Cout * B * H * W (the convolution's own
+operations) over the median time of the call: a rate of the whole call, not a kernel's share of peak."""
 import argparse
 import json
 import os
@@ -25,7 +25,7 @@ IMPLS = (("kernels", "auto"), ("torch", "torch"))
 
 
 def timed_pair(fns, iters, warmup=3):
-    """median time (us) of each callable; the callables alternate inside every round"""
+    """(median, first quartile, third quartile) in us of each callable; the callables alternate inside every round"""
     for _ in range(warmup):
         for fn in fns:
             fn()
@@ -39,7 +39,11 @@ def timed_pair(fns, iters, warmup=3):
             b.record()
             b.synchronize()
             times[k].append(a.elapsed_time(b) * 1e3)
-    return [statistics.median(t) for t in times]
+    out = []
+    for t in times:
+        q = statistics.quantiles(t, n=4)
+        out.append((statistics.median(t), round(q[0], 1), round(q[2], 1)))
+    return out
 
 
 def he_init(module, seed):
@@ -94,9 +98,10 @@ def main():
             ya, yb = nets["kernels"](image)["relu5_4"].float(), nets["torch"](image)["relu5_4"].float()
         row = {"what": "network", "dtype": name, "B": a.batch, "H": a.height, "W": a.width,
                "relu5_4_rel_diff": ((ya - yb).abs().max() / yb.abs().max()).item()}
-        row["kernels_fwd_us"], row["torch_fwd_us"] = timed_pair([forward(nets["kernels"]), forward(nets["torch"])], a.iters)
-        row["kernels_fwd_bwd_us"], row["torch_fwd_bwd_us"] = timed_pair(
-            [forward_backward(nets["kernels"]), forward_backward(nets["torch"])], a.iters)
+        for what, make in (("fwd", forward), ("fwd_bwd", forward_backward)):
+            res = timed_pair([make(nets["kernels"]), make(nets["torch"])], a.iters)
+            for (key, _), (med, q1, q3) in zip(IMPLS, res):
+                row["%s_%s_us" % (key, what)], row["%s_%s_q1_q3_us" % (key, what)] = med, [q1, q3]
         row["fwd_speedup"] = round(row["torch_fwd_us"] / row["kernels_fwd_us"], 3)
         row["fwd_bwd_speedup"] = round(row["torch_fwd_bwd_us"] / row["kernels_fwd_bwd_us"], 3)
         print(json.dumps(row), flush=True)
@@ -119,11 +124,11 @@ def main():
                     with torch.no_grad():
                         return conv(x)
                 return run
-            tk, tt = timed_pair([layer("kernels"), layer("torch")], a.iters)
+            (tk, k1, k3), (tt, _, _) = timed_pair([layer("kernels"), layer("torch")], a.iters)
             B, Cin, H, W = x.shape
             flop = 2.0 * 9 * Cin * convs["kernels"][n].out_channels * B * H * W
             row = {"what": "conv", "layer": n, "dtype": name, "Cin": Cin, "Cout": convs["kernels"][n].out_channels, "H": H,
-                   "W": W, "kernels_us": round(tk, 1), "torch_us": round(tt, 1),
+                   "W": W, "kernels_us": round(tk, 1), "kernels_q1_q3_us": [k1, k3], "torch_us": round(tt, 1),
                    "kernels_tflops": round(flop / tk * 1e-6, 1), "torch_tflops": round(flop / tt * 1e-6, 1)}
             print(json.dumps(row), flush=True)
             rows.append(row)
