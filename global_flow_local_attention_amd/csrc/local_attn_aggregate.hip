@@ -19,6 +19,7 @@
 #include "be_bwd_lds.h"
 #include "patch_mfma.h"
 #include "rs_taps.h"
+#include "agg_stream.h"
 
 namespace gfla {
 
@@ -411,19 +412,9 @@ __global__ __launch_bounds__(kLdsThreads) void agg_fwd_lds_kernel(
 //      of ds_read_b32, no per-column clamp -- consumed by v_pk_fma_f32 on the register pair a b64 read lands in.
 // Non-finite source values: the window is one word wider than the patch and that word carries weight 0, so an
 // inf / NaN there reaches this pixel (0 * inf), one column further than in the reference.
+// Layout, decode, staging pipeline and row reader: agg_stream.h.
 // ----------------------------------------------------------------------------------------------
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr unsigned kAggNotDense = 0xffffffffu;  // packed word of a pixel whose taps are not a dense patch
-constexpr unsigned kAggSkip = 0xfffffffeu;      // lane without a pixel (tile overhang)
 constexpr int kAggCoefThreads = 256;
-
-template <int K>
-constexpr int agg_coef_slots() { return (K + 1) * (K + 2); }
-// floats per pixel in the table: the coefficients + the packed word, padded to whole 16-byte vectors -- a lane fetches
-// its record with a few dwordx4 loads (the texture addresser spends ~16 cycles per wave load whatever its width: one
-// dword load per coefficient was the bottleneck of the first version of this kernel)
-constexpr int agg_record_floats(int k) { return ((k + 1) * (k + 2) + 1 + 3) & ~3; }
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <typename T, int K>
 __global__ __launch_bounds__(kAggCoefThreads) void agg_coef_kernel(
@@ -432,15 +423,11 @@ __global__ __launch_bounds__(kAggCoefThreads) void agg_coef_kernel(
   constexpr int KK = K * K, NS = agg_coef_slots<K>(), NR = agg_record_floats(K);
   __shared__ float coef[NS * kAggCoefThreads];  // [slot][thread]: a private, dynamically indexable column per lane
   const int HW = H * W;
-  const int b = blockIdx.y;
-  // wave <-> tile of the main kernel (same lane -> pixel mapping), record vectors written [tile][vector][lane]
-  const int lane = threadIdx.x & 63, t = blockIdx.x * (kAggCoefThreads / 64) + (threadIdx.x >> 6);
-  if (t >= ntile) return;
-  const int tw = 1 << tw_log2, th = 64 >> tw_log2, tiles_x = (W + tw - 1) >> tw_log2;
-  const int ty = t / tiles_x, tx = t - ty * tiles_x;
-  const int yf = ty * th + (lane >> tw_log2), xf = (tx << tw_log2) + (lane & (tw - 1));
-  if (yf >= H || xf >= W) return;
-  const int p = yf * W + xf;
+  AggLane d;  // grid: x = groups of blockDim/64 tiles, y = sample (so the launch needs B <= 65535)
+  d.b = blockIdx.y;
+  d.pixel(blockIdx.x * (kAggCoefThreads / 64) + (int)(threadIdx.x >> 6), tw_log2, ntile, H, W);
+  if (!d.active) return;
+  const int b = d.b, p = d.p;
   float a[KK];
   const T *lg = logits + (int64_t)b * KK * HW + p;
 #pragma unroll
@@ -465,9 +452,9 @@ __global__ __launch_bounds__(kAggCoefThreads) void agg_coef_kernel(
     for (int t = 0; t < KK; ++t) ao[(int64_t)t * HW] = Num<T>::from(a[t]);
   }
   PatchTaps<float, K> tp;
-  tp.init(Num<T>::ld(flow + (int64_t)(b * 2 + 0) * HW + p), Num<T>::ld(flow + (int64_t)(b * 2 + 1) * HW + p), xf, yf,
+  tp.init(Num<T>::ld(flow + (int64_t)(b * 2 + 0) * HW + p), Num<T>::ld(flow + (int64_t)(b * 2 + 1) * HW + p), d.xf, d.yf,
           Hs, Ws);
-  f32x4 *rec = reinterpret_cast<f32x4 *>(table) + ((int64_t)b * ntile + t) * (NR / 4) * 64 + lane;
+  f32x4 *rec = d.record<NR>(reinterpret_cast<f32x4 *>(table), ntile);
   if (!tp.dense) {
     rec[(NS >> 2) * 64][NS & 3] = __uint_as_float(kAggNotDense);
     return;
@@ -512,83 +499,22 @@ __global__ __launch_bounds__(kAggCoefThreads) void agg_coef_kernel(
   }
 }
 
-// LDS layout of a plane: rows in INTERLEAVED PAIRS,
-//     word(y, x) = (y / 2) * pitch + (x / 2) * 4 + (y % 2) * 2 + (x % 2),     pitch = 32 (mod 64), >= 2 * Ws
-// A word pair (even x) stays contiguous (one ds_read_b64), rows y and y+1 of a pair never share a bank (they occupy
-// alternate 8-byte slots), and consecutive row pairs are 32 banks apart: a lane group whose addresses span <= 8 word
-// pairs of <= 4 plane rows -- a 16 x 2 or 8 x 4 pixel tile with a coherent flow -- reads without bank conflicts (zero
-// flow: 4 % conflict cycles; the bench's flow, which moves ~1 pixel per pixel, still loses 40 %, down from 60 % for
-// row-major planes read by 64 pixels of one row).
-// A chunk of planes is moved in two halves so that the global loads of the NEXT chunk are in flight while the current
-// one is being read: agg_chunk_load (global -> registers, word pairs) ... agg_chunk_store (registers -> LDS).
-constexpr int kAggPre = 8;  // word pairs per thread and chunk (the launcher sizes the chunk accordingly)
-
-template <typename T>
-__device__ __forceinline__ void agg_chunk_load(const T *__restrict__ g, int n, f32x2 (&pre)[kAggPre]) {
-#pragma unroll
-  for (int j = 0; j < kAggPre; ++j) {
-    // unconditional (index clamped): a load under `if (i < n)` turns into a branch + s_waitcnt per load
-    const int i = min(j * (int)blockDim.x + (int)threadIdx.x, n - 1);
-    if constexpr (sizeof(T) == 4) {
-      pre[j] = reinterpret_cast<const f32x2 *>(g)[i];
-    } else if constexpr (std::is_same<T, f16_t>::value) {
-      const unsigned raw = reinterpret_cast<const unsigned *>(g)[i];  // two f16
-      pre[j] = f32x2{Num<f16_t>::ld(reinterpret_cast<const f16_t *>(&raw)), Num<f16_t>::ld(reinterpret_cast<const f16_t *>(&raw) + 1)};
-    } else {
-      const unsigned raw = reinterpret_cast<const unsigned *>(g)[i];  // two bf16
-      pre[j] = f32x2{__uint_as_float(raw << 16), __uint_as_float(raw & 0xffff0000u)};
-    }
-  }
-}
-// LDS word offsets of the thread's kAggPre word pairs inside a chunk buffer (the same for every chunk: computed once,
-// two 16-bit offsets per register; the chunk buffer has < 2^16 words... in units of 2 words)
-__device__ __forceinline__ void agg_chunk_offsets(int n_max, int per_plane, int wp, int pitch, int plane_sz,
-                                                  unsigned (&off)[kAggPre / 2]) {
-  const unsigned m_pl = 0xffffffffu / (unsigned)per_plane + 1u, m_wp = 0xffffffffu / (unsigned)wp + 1u;  // n * d < 2^32
-#pragma unroll
-  for (int j = 0; j < kAggPre; ++j) {
-    const int i = min(j * (int)blockDim.x + (int)threadIdx.x, n_max - 1);
-    const int c = (int)__umulhi((unsigned)i, m_pl);
-    const int rem = i - c * per_plane;
-    const int y = (int)__umulhi((unsigned)rem, m_wp);
-    const int xp = rem - y * wp;
-    const unsigned o = (unsigned)(c * plane_sz + (y >> 1) * pitch + (xp << 2) + ((y & 1) << 1)) >> 1;  // even word -> /2
-    if (j & 1) off[j >> 1] |= o << 16; else off[j >> 1] = o;
-  }
-}
-__device__ __forceinline__ void agg_chunk_store(float *lds, int n, const f32x2 (&pre)[kAggPre],
-                                                const unsigned (&off)[kAggPre / 2]) {
-#pragma unroll
-  for (int j = 0; j < kAggPre; ++j) {
-    const int i = j * (int)blockDim.x + (int)threadIdx.x;
-    const unsigned o = (j & 1) ? off[j >> 1] >> 16 : off[j >> 1] & 0xffffu;
-    if (i < n) *reinterpret_cast<f32x2 *>(lds + 2 * o) = pre[j];
-  }
-}
-
-// workgroup <-> (sample, tile group = blockDim/64 tiles, channel range [sg*CS, sg*CS+CS)); wave <-> tile; lane <-> pixel.
 // The lane's record is fetched ONCE and stays in registers while the channels of the range stream through LDS in
-// chunks of CH planes, double buffered.
-// <= 12 waves per workgroup: 170 VGPRs per lane (record 43 + two channels x two rows in flight 28 + next chunk 16 + ...)
+// chunks of CH planes (AggStage).  CHT = planes per chunk, compile time: the CHT results of a chunk stay in registers
+// and are stored once per chunk behind the pipeline's wait, from a uniform base + a per-lane offset (scalar-base store
+// form).  170 VGPRs per lane (record 43 + two channels x two rows in flight 28 + next chunk 16 + ...).
 //
-// Two things the ISA of the first version showed (round 4; each cost an exposed round trip per step):
-//   * a result store inside the channel loop: its address / data registers are overwritten by the next channel pair, so
-//     hipcc waits for the store -- and the memory counter is in order: waiting for the YOUNGEST store waits for the next
-//     chunk's prefetch loads as well (s_waitcnt vmcnt(0) at the top of the pair loop: the double buffering was synchronous).
-//     Now the CHT results of a chunk stay in registers (CHT = planes per chunk, compile time) and are stored once per chunk,
-//     behind the wait the staging needs anyway, from a uniform base + a per-lane offset (scalar-base store form);
-//   * the last word of a row window is the low half of a 64-bit read whose high half is dead: hipcc reused that register
-//     for the next address and had to wait for the read to land first (s_waitcnt lgkmcnt(0) in the middle of every burst of
-//     reads).  The pair is kept alive until the row has been consumed.
-constexpr int kAggStreamWaves = 12;
-// timing ablations of agg_fwd_stream_kernel (tools/ubench/build_agg_abl.sh builds variant libraries with
-// -DGFLA_AGG_ABL=bits; results are garbage): 1 = no LDS reads in the row loop, 2 = no prefetch / staging of the next chunk,
-// 4 = no workgroup barrier in the chunk loop, 8 = no arithmetic on the rows
+// The last word of a row window is the low half of a 64-bit read whose high half is dead: hipcc reused that register for
+// the next address and had to wait for the read to land first (s_waitcnt lgkmcnt(0) in the middle of every burst of
+// reads).  The pair is kept alive until the row has been consumed.
+//
+// Timing ablations (tools/ubench/build_agg_abl.sh builds variant libraries with -DGFLA_AGG_ABL=bits; results are
+// garbage): 1 = no LDS reads in the row loop, 2 = no prefetch / staging of the next chunk, 4 = no workgroup barrier in
+// the chunk loop, 8 = no arithmetic on the rows
 #ifndef GFLA_AGG_ABL
 #define GFLA_AGG_ABL 0
 #endif
 constexpr int kAggAbl = GFLA_AGG_ABL;
-constexpr int kAggMaxChunk = 8;   // planes per chunk the forward kernel is instantiated for (2, 4, 6, 8)
 template <typename T, int K, int CHT>
 __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_fwd_stream_kernel(
     const T *__restrict__ src, const T *__restrict__ flow, const T *__restrict__ logits,
@@ -597,119 +523,70 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_fwd_stream_kernel(
   constexpr int KK = K * K, NP = (K + 1) / 2, NS = agg_coef_slots<K>(), NR = agg_record_floats(K);
   static_assert(K % 2 == 1, "paired reads are laid out for odd K");
   extern __shared__ __attribute__((aligned(16))) unsigned char gfla_smem[];
-  float *lds = reinterpret_cast<float *>(gfla_smem);
-  // every XCD gets a contiguous run of the (sample, channel range, tile group) index space: the tile groups that
-  // stage the same planes, and the channel ranges that read the same records, share one L2
-  const int per_xcd = (total + kNumXCD - 1) / kNumXCD;
-  int bid = (blockIdx.x % kNumXCD) * per_xcd + blockIdx.x / kNumXCD;
-  if (bid >= total) return;
-  const int tg = bid % tgroups;
-  bid /= tgroups;
-  const int sg = bid % nsuper;
-  const int b = bid / nsuper;
-  const int c_begin = sg * CS, c_end = min(C, c_begin + CS);
-  const int plane_sz = ((Hs + 1) >> 1) * pitch;
-  const int buf_sz = CH * plane_sz + 4;  // + the word pair a window may read past the last row
+  AggLane d;
+  if (!d.stream(C, CS, nsuper, tgroups, total, tw_log2, ntile, H, W)) return;
+  const int b = d.b, c_begin = d.c_begin, c_end = d.c_end, p = d.p;
   const int HW = H * W;
   const float inv_kk = 1.f / (float)KK;
-  const int tw = 1 << tw_log2, th = 64 >> tw_log2;
-  const int tiles_x = (W + tw - 1) >> tw_log2;
-  const int lane = threadIdx.x & 63;
-  const int t = tg * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
 
   // the lane's pixel: packed word + coefficients (w2[r][i] = words (2i, 2i+1) of the aligned row window, w1[r] = word K+1)
   f32x2 w2[K + 1][NP];
   float w1[K + 1];
   unsigned m = kAggSkip;
-  int p = 0;
-  if (t < ntile) {
-    const int ty = t / tiles_x, tx = t - ty * tiles_x;
-    const int yf = ty * th + (lane >> tw_log2), xf = (tx << tw_log2) + (lane & (tw - 1));
-    if (yf < H && xf < W) {
-      p = yf * W + xf;
-      const f32x4 *rec = reinterpret_cast<const f32x4 *>(table) + ((int64_t)b * ntile + t) * (NR / 4) * 64 + lane;
-      f32x4 q[NR / 4];
+  if (d.active) {
+    const f32x4 *rec = d.record<NR>(reinterpret_cast<const f32x4 *>(table), ntile);
+    f32x4 q[NR / 4];
 #pragma unroll
-      for (int v = 0; v < NR / 4; ++v) q[v] = rec[v * 64];  // 1 KB per load instruction, fully coalesced
+    for (int v = 0; v < NR / 4; ++v) q[v] = rec[v * 64];  // 1 KB per load instruction, fully coalesced
 #pragma unroll
-      for (int r = 0; r <= K; ++r) {
+    for (int r = 0; r <= K; ++r) {
 #pragma unroll
-        for (int i = 0; i < NP; ++i) {
-          w2[r][i].x = q[(r * (K + 2) + 2 * i) >> 2][(r * (K + 2) + 2 * i) & 3];
-          w2[r][i].y = q[(r * (K + 2) + 2 * i + 1) >> 2][(r * (K + 2) + 2 * i + 1) & 3];
-        }
-        w1[r] = q[(r * (K + 2) + K + 1) >> 2][(r * (K + 2) + K + 1) & 3];
+      for (int i = 0; i < NP; ++i) {
+        w2[r][i].x = q[(r * (K + 2) + 2 * i) >> 2][(r * (K + 2) + 2 * i) & 3];
+        w2[r][i].y = q[(r * (K + 2) + 2 * i + 1) >> 2][(r * (K + 2) + 2 * i + 1) & 3];
       }
-      m = __float_as_uint(q[NS >> 2][NS & 3]);
+      w1[r] = q[(r * (K + 2) + K + 1) >> 2][(r * (K + 2) + K + 1) & 3];
     }
+    m = __float_as_uint(q[NS >> 2][NS & 3]);
   }
 
-  const int wp = Ws >> 1;              // word pairs per row (Ws is even)
-  const int per_plane = Hs * wp;       // word pairs per plane
-  const T *s0 = src + ((int64_t)b * C + c_begin) * Hs * Ws;
-  f32x2 pre[kAggPre];
-  unsigned off[kAggPre / 2];
-  agg_chunk_offsets(CH * per_plane, per_plane, wp, pitch, plane_sz, off);
-  int gc = min(CH, c_end - c_begin);
-  agg_chunk_load<T>(s0, gc * per_plane, pre);
-  {  // words no load ever writes must be finite: they meet weight 0
-    const int nrow = CH * ((Hs + 1) >> 1);
-    for (int u = 0; u < 2; ++u) {
-      float *bf = lds + u * buf_sz;
-      if (pitch >= 2 * Ws + 4)
-        for (int i = threadIdx.x; i < nrow * 4; i += blockDim.x) bf[(i >> 2) * pitch + 2 * Ws + (i & 3)] = 0.f;
-      if (threadIdx.x < 4) bf[CH * plane_sz + threadIdx.x] = 0.f;
-    }
-  }
-  agg_chunk_store(lds, gc * per_plane, pre, off);
-  __syncthreads();
+  AggStage<T, (kAggAbl & 2) != 0> st{reinterpret_cast<float *>(gfla_smem), src + ((int64_t)b * C + c_begin) * Hs * Ws,
+                                     CH, Hs, Ws, pitch, c_begin, c_end};
+  st.prologue();
 
   int ro[K + 1];
   if (m < kAggSkip) {
     const int xa = (int)(m & 0xffffu), y0 = (int)(m >> 16) - 16;
 #pragma unroll
-    for (int r = 0; r <= K; ++r) {
-      const int yc = clampi(y0 + r, 0, Hs - 1);
-      ro[r] = (yc >> 1) * pitch + ((yc & 1) << 1) + (xa << 1);  // word pairs of a row sit 4 words apart
-    }
+    for (int r = 0; r <= K; ++r) ro[r] = agg_row_window(clampi(y0 + r, 0, Hs - 1), xa, pitch);
   }
   T *ob = out + ((int64_t)b * C + c_begin) * HW;   // uniform: the stores take a scalar base + the lane's pixel offset
-  __builtin_amdgcn_s_waitcnt(0x0F70);              // (record and first chunk: all landed; see the end of the loop body)
-  int cur = 0;
+  __builtin_amdgcn_s_waitcnt(0x0F70);              // record and first chunk: all landed
   for (int cb = c_begin; cb < c_end; cb += CH) {
-    const int gn = min(CH, c_end - cb - CH);  // planes of the next chunk (<= 0: none): in flight during this one
-    // UNCONDITIONAL (the last chunk re-requests one word pair of its own first plane): with the loads under a branch hipcc
-    // cannot count them, and every later wait for an older store becomes vmcnt(0) -- a wait for these loads
-    if constexpr (!(kAggAbl & 2))
-      agg_chunk_load<T>(s0 + (int64_t)(gn > 0 ? cb + CH - c_begin : 0) * Hs * Ws, gn > 0 ? gn * per_plane : 1, pre);
-    gc = min(CH, c_end - cb);
-    const float *pl = lds + cur * buf_sz;
+    const int gn = st.next_planes(cb);
+    st.prefetch(cb, gn);
+    const int gc = min(CH, c_end - cb);
+    const float *pl = st.planes();
     float res[CHT];
 #pragma unroll
     for (int c = 0; c < CHT; ++c) res[c] = 0.f;
     if (m < kAggSkip) {
       // One patch row of one channel: NP + 1 ds_read_b64 (word K+1 as the first half of a 64-bit read: a ds_read_b32 is
-      // banked mod 32 and conflicts on this layout).  The empty asm statements keep the reads apart: merged into
-      // ds_read2_b64 they would run at half the LDS rate (MI355X_MICROARCH.md, LDS table).
+      // banked mod 32 and conflicts on this layout)
       auto load_row = [&](const float *rp, f32x2(&v)[NP], f32x2 &u) {
         if constexpr (kAggAbl & 1) {
 #pragma unroll
-          for (int i = 0; i < NP; ++i) v[i] = f32x2{(float)lane, (float)(size_t)rp};
-          u = f32x2{(float)lane, 1.f};
+          for (int i = 0; i < NP; ++i) v[i] = f32x2{(float)d.lane, (float)(size_t)rp};
+          u = f32x2{(float)d.lane, 1.f};
           return;
         }
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-          v[i] = *reinterpret_cast<const f32x2 *>(rp + 4 * i);
-          asm volatile("" ::: "memory");
-        }
-        u = *reinterpret_cast<const f32x2 *>(rp + 4 * NP);
-        asm volatile("" ::: "memory");
+        agg_load_row<NP>(rp, v);
+        agg_load_row<1>(rp + 4 * NP, &u);
       };
 #pragma unroll
       for (int c = 0; c < CHT; c += 2) {  // two channels at a time: independent accumulation chains
         // (a chunk shorter than CHT re-reads its last plane: finite values, results never stored)
-        const float *p0_ = pl + min(c, gc - 1) * plane_sz, *p1_ = pl + min(c + 1, gc - 1) * plane_sz;
+        const float *p0_ = pl + min(c, gc - 1) * st.plane_sz, *p1_ = pl + min(c + 1, gc - 1) * st.plane_sz;
         f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
         float s0_ = 0.f, s1_ = 0.f;
         f32x2 v0[2][NP], v1[2][NP];
@@ -743,7 +620,7 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_fwd_stream_kernel(
         if (c + 1 < CHT) res[c + 1] = (acc1.x + acc1.y + s1_) * inv_kk;
       }
     } else if (m == kAggNotDense) {
-      // tap by tap exactly as block_extractor does; rolled loops that re-derive a_ij from the logits
+      // tap by tap; a_ij is re-derived from the logits (yf, xf from p: not kept in registers for this branch)
       const int yf = p / W, xf = p - yf * W;
       const T *lg = logits + (int64_t)b * KK * HW + p;
       const float fx0 = Num<T>::ld(flow + (int64_t)(b * 2 + 0) * HW + p);
@@ -761,22 +638,18 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_fwd_stream_kernel(
 #pragma unroll
       for (int c = 0; c < CHT; ++c) {
         if (c >= gc) break;
-        const float *plc = pl + c * plane_sz;
         float acc = 0;
+        const float *plc = pl + c * st.plane_sz;
 #pragma unroll 1
         for (int i = 0; i < K; ++i) {
-          const float dy = (fy0 + (float)(i - K / 2)) + (float)yf;
-          const float fdy = floorf(dy);
-          const int yTc = clampi((int)fdy, 0, Hs - 1), yBc = clampi((int)(fdy + 1), 0, Hs - 1);
-          const int yT = (yTc >> 1) * pitch + ((yTc & 1) << 1), yB = (yBc >> 1) * pitch + ((yBc & 1) << 1);
-          const float yB_P = dy - fdy, yT_P = 1 - yB_P;
+          const AggTapAxis ty = agg_tap_axis<K>(fy0, i, yf, Hs);
+          const int yT = agg_row_base(ty.lo, pitch), yB = agg_row_base(ty.hi, pitch);
+          const float yB_P = ty.w_hi, yT_P = 1 - yB_P;
 #pragma unroll 1
           for (int j = 0; j < K; ++j) {
-            const float dx = (fx0 + (float)(j - K / 2)) + (float)xf;
-            const float fdx = floorf(dx);
-            const int xLc = clampi((int)fdx, 0, Ws - 1), xRc = clampi((int)(fdx + 1), 0, Ws - 1);
-            const int xL = ((xLc >> 1) << 2) + (xLc & 1), xR = ((xRc >> 1) << 2) + (xRc & 1);
-            const float xR_P = dx - fdx, xL_P = 1 - xR_P;
+            const AggTapAxis tx = agg_tap_axis<K>(fx0, j, xf, Ws);
+            const int xL = agg_col_word(tx.lo), xR = agg_col_word(tx.hi);
+            const float xR_P = tx.w_hi, xL_P = 1 - xR_P;
             float aij = Num<T>::ld(lg + (int64_t)(i * K + j) * HW);
             if (apply_softmax) aij = exp_t<float>(aij - sm_max) * sm_inv;
             float v = (xL_P * yT_P) * plc[yT + xL];
@@ -788,16 +661,9 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_fwd_stream_kernel(
         }
         res[c] = acc * inv_kk;
       }
-      // (rare branch, taken by a wave with a flow within rounding of an integer.)  Its loads have all been consumed; saying
-      // so on every path out of it keeps them from turning the dense path's register reuse into waits for the prefetch
-      __builtin_amdgcn_s_waitcnt(0x0F70);
+      agg_taps_done();
     }
-    if constexpr (!(kAggAbl & 2)) cur ^= 1;
-    if constexpr (!(kAggAbl & 2))
-      if (gn > 0) agg_chunk_store(lds + cur * buf_sz, gn * per_plane, pre, off);
-    // every memory load so far has landed (the staging above needed the prefetch; the tap-by-tap branch its own): said
-    // unconditionally, so that nothing but the result stores below is pending when the loop comes round
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt / lgkmcnt untouched
+    st.commit(gn);
     asm volatile("" ::: "memory");
     // the chunk's results, behind the wait the staging needed anyway; they fly during the next chunk
     if (m != kAggSkip) {
@@ -809,62 +675,6 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_fwd_stream_kernel(
     if constexpr (!(kAggAbl & 4))
       __syncthreads();  // the next chunk has landed, and nobody still reads the buffer the one after it will overwrite
   }
-}
-
-// Launch geometry of agg_fwd_stream_kernel.
-struct AggStreamGeo {
-  int CH, CS, nsuper, tgroups, threads, pitch, tw_log2, ntile;
-  unsigned lds;
-};
-inline AggStreamGeo agg_stream_geometry(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k) {
-  AggStreamGeo g{0, 0, 1, 1, 0, 0, 4, 0, 0};
-  // tile width: the one that wastes the fewest lanes on the overhang (16 on ties); tuning key 16 overrides
-  int twl = 4;
-  double best_eff = -1;
-  for (int cand : {4, 3, 5}) {
-    const int64_t tw = 1 << cand, th = 64 >> cand;
-    const double eff = (double)(H * W) / (double)(ceil_div(W, tw) * tw * ceil_div(H, th) * th);
-    if (eff > best_eff + 1e-9) {
-      best_eff = eff;
-      twl = cand;
-    }
-  }
-  if (tuning(16) == 8 || tuning(16) == 16 || tuning(16) == 32) twl = tuning(16) == 8 ? 3 : tuning(16) == 16 ? 4 : 5;
-  const int64_t ntile = ceil_div(W, 1 << twl) * ceil_div(H, 64 >> twl);
-  const int64_t tmax = tuning(9) >= 64 && tuning(9) <= kAggStreamWaves * 64 ? tuning(9) / 64 : kAggStreamWaves;  // tiles (waves) per workgroup
-  const int64_t tgroups = ceil_div(ntile, tmax);
-  const int64_t twg = ceil_div(ntile, tgroups);  // balanced
-  const int64_t threads = twg * 64;
-  int pitch = (int)(ceil_div(2 * Ws + 32, 64) * 64 - 32);  // smallest value >= 2 Ws that is 32 mod 64
-  if (tuning(17) >= 2 * Ws && !(tuning(17) & 3)) pitch = tuning(17);  // experiment: pair pitch in words
-  const int64_t per_plane = ceil_div(Hs, 2) * pitch * 4;
-  const int64_t budget = 160 * 1024 - 64;
-  // chunk: as many planes as two buffers fit and kAggPre word pairs per thread cover
-  int64_t CH = std::min<int64_t>((budget / 2 - 16) / per_plane, kAggPre * threads / (Hs * (Ws / 2)));
-  if (CH > C) CH = C;
-  if (CH > kAggMaxChunk) CH = kAggMaxChunk;   // the forward kernel keeps a chunk's results in registers
-  if (tuning(4) > 0 && tuning(4) < CH) CH = tuning(4);
-  if (CH >= 2) CH &= ~1LL;  // channel pairs
-  if (CH < 1) return g;
-  // channel ranges: more of them = more workgroups, fewer chunks each (the first chunk of a workgroup is not overlapped)
-  int64_t best_ns = 1;
-  double best_cost = -1;
-  for (int64_t ns = 1; ns * CH <= C || ns == 1; ns *= 2) {
-    const int64_t CS = ceil_div(ceil_div(C, ns), CH) * CH;
-    const int64_t nsr = ceil_div(C, CS);
-    const int64_t wgs = B * tgroups * nsr;
-    const double rounds = (double)ceil_div(wgs, kNumCU);
-    const double cost = rounds * (1.3 + (double)(CS / CH));
-    if (best_cost < 0 || cost < best_cost - 1e-9) {
-      best_cost = cost;
-      best_ns = ns;
-    }
-  }
-  if (tuning(5) > 0) best_ns = tuning(5);
-  const int64_t CS = ceil_div(ceil_div(C, best_ns), CH) * CH;
-  g = AggStreamGeo{(int)CH, (int)CS, (int)ceil_div(C, CS), (int)tgroups, (int)threads, pitch, twl, (int)ntile,
-                   (unsigned)(2 * (CH * per_plane + 16))};
-  return g;
 }
 
 // d/d a_ij (the attention gradient before the softmax Jacobian):
@@ -1004,13 +814,12 @@ __global__ __launch_bounds__(512) void agg_ga_lds_kernel(
     atomic_add(gflow + (int64_t)(b * 2 + 1) * HW + p, gy_acc);
   }
 }
-
-// d/d a_ij and d/d flow with the machinery of agg_fwd_stream_kernel (same workgroup <-> (sample, tile group, channel
-// range) decomposition, same double-buffered interleaved planes, same paired reads): per channel the lane accumulates
-// g_c * v_c over its (K+1) x (K+2)-word aligned WINDOW (48 packed-FMA accumulators for K = 5) instead of reading the
-// (K+1)^2 patch with clamped per-column ds_read_b32; the window sums are mapped back to patch sums once per pixel at
-// the end (an 8-way select per patch entry: the x clamp and the window's parity), then mixed into d/d a_ij and
-// d/d flow exactly as agg_ga_lds_kernel does.  One atomic per (ij, channel range) publishes the sums.
+// d/d a_ij and d/d flow on the machinery of agg_fwd_stream_kernel (agg_stream.h: the same decode, staging pipeline and
+// paired reads): per channel the lane accumulates g_c * v_c over its (K+1) x (K+2)-word aligned WINDOW (48 packed-FMA
+// accumulators for K = 5) instead of reading the (K+1)^2 patch with clamped per-column ds_read_b32; the window sums are
+// mapped back to patch sums once per pixel at the end (an 8-way select per patch entry: the x clamp and the window's
+// parity), then mixed into d/d a_ij and d/d flow exactly as agg_ga_lds_kernel does.  One atomic per (ij, channel range)
+// publishes the sums.
 // EPI = 1: the same accumulation for resample2d's d/d input2 (kernel_size 4, dilation 1: a K = 3 patch around
 // floor(p + flow) - 1): `flow` is input2 (dx, dy, sigma), `gflow` its (B, 3, H, W) gradient, the epilogue is
 // rs_bwd2_finish on the row / column sums of the patch sums (resample2d_kernel.cu:273-328); glogits / attn unused.
@@ -1025,32 +834,12 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_ga_stream_kernel(
   constexpr int KK = K * K, NP = (K + 1) / 2, NW = 2 * NP + 2;  // NW = words of the row window (K + 3)
   static_assert(K % 2 == 1, "paired reads are laid out for odd K");
   extern __shared__ __attribute__((aligned(16))) unsigned char gfla_smem[];
-  float *lds = reinterpret_cast<float *>(gfla_smem);
-  const int per_xcd = (total + kNumXCD - 1) / kNumXCD;
-  int bid = (blockIdx.x % kNumXCD) * per_xcd + blockIdx.x / kNumXCD;
-  if (bid >= total) return;
-  const int tg = bid % tgroups;
-  bid /= tgroups;
-  const int sg = bid % nsuper;
-  const int b = bid / nsuper;
-  const int c_begin = sg * CS, c_end = min(C, c_begin + CS);
-  const int plane_sz = ((Hs + 1) >> 1) * pitch;
-  const int buf_sz = CH * plane_sz + 4;
+  AggLane d;
+  if (!d.stream(C, CS, nsuper, tgroups, total, tw_log2, ntile, H, W)) return;
+  const int b = d.b, c_begin = d.c_begin, c_end = d.c_end, p = d.p, yf = d.yf, xf = d.xf;
+  const bool active = d.active;
   const int HW = H * W;
   const float inv_kk = EPI == 1 ? 1.f : 1.f / (float)KK;
-  const int tw = 1 << tw_log2, th = 64 >> tw_log2;
-  const int tiles_x = (W + tw - 1) >> tw_log2;
-  const int lane = threadIdx.x & 63;
-  const int t = tg * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
-  bool active = false;
-  int p = 0, yf = 0, xf = 0;
-  if (t < ntile) {
-    const int ty = t / tiles_x, tx = t - ty * tiles_x;
-    yf = ty * th + (lane >> tw_log2);
-    xf = (tx << tw_log2) + (lane & (tw - 1));
-    active = yf < H && xf < W;
-    if (active) p = yf * W + xf;
-  }
   constexpr int NF = EPI == 1 ? 3 : 2;  // planes of `flow`
   const float fx0 = Num<T>::ld(flow + (int64_t)(b * NF + 0) * HW + p);
   const float fy0 = Num<T>::ld(flow + (int64_t)(b * NF + 1) * HW + p);
@@ -1074,10 +863,7 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_ga_stream_kernel(
   const int xa = clampi(px0, 0, Ws - (K + 1)) & ~1;
   int ro[K + 1];
 #pragma unroll
-  for (int r = 0; r <= K; ++r) {
-    const int yc = clampi(py0 + r, 0, Hs - 1);
-    ro[r] = (yc >> 1) * pitch + ((yc & 1) << 1) + (xa << 1);
-  }
+  for (int r = 0; r <= K; ++r) ro[r] = agg_row_window(clampi(py0 + r, 0, Hs - 1), xa, pitch);
   f32x2 Pw[K + 1][NP + 1];  // window sums: words (2i, 2i+1) of patch row r
 #pragma unroll
   for (int r = 0; r <= K; ++r)
@@ -1087,24 +873,9 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_ga_stream_kernel(
   const T *at = attn ? attn + (int64_t)b * KK * HW + p : nullptr;
   float gx_acc = 0.f, gy_acc = 0.f;
 
-  const int wp = Ws >> 1, per_plane = Hs * wp;
-  const T *s0 = src + ((int64_t)b * C + c_begin) * Hs * Ws;
-  f32x2 pre[kAggPre];
-  unsigned off[kAggPre / 2];
-  agg_chunk_offsets(CH * per_plane, per_plane, wp, pitch, plane_sz, off);
-  int gc = min(CH, c_end - c_begin);
-  agg_chunk_load<T>(s0, gc * per_plane, pre);
-  {  // words no load ever writes must be finite: they meet weight 0 / are never selected
-    const int nrow = CH * ((Hs + 1) >> 1);
-    for (int u = 0; u < 2; ++u) {
-      float *bf = lds + u * buf_sz;
-      if (pitch >= 2 * Ws + 4)
-        for (int i = threadIdx.x; i < nrow * 4; i += blockDim.x) bf[(i >> 2) * pitch + 2 * Ws + (i & 3)] = 0.f;
-      if (threadIdx.x < 4) bf[CH * plane_sz + threadIdx.x] = 0.f;
-    }
-  }
-  agg_chunk_store(lds, gc * per_plane, pre, off);
-  __syncthreads();
+  AggStage<T> st{reinterpret_cast<float *>(gfla_smem), src + ((int64_t)b * C + c_begin) * Hs * Ws, CH, Hs, Ws, pitch,
+                 c_begin, c_end};
+  st.prologue();
 
   const T *go_b = gout + ((int64_t)b * C + c_begin) * HW;   // uniform base; the lane's pixel is the offset
   // raw upstream gradients of the chunk about to be computed (gcur) and of the one after it (gnxt); channels beyond the
@@ -1113,38 +884,29 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_ga_stream_kernel(
   const int cs_n = c_end - c_begin;
 #pragma unroll
   for (int c = 0; c < CHT; ++c) gcur[c] = Num<T>::ld(go_b + (int64_t)min(c, cs_n - 1) * HW + p);
-  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): nothing pending when the loop is entered (see agg_fwd_stream_kernel)
-  int cur = 0;
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): nothing pending when the loop is entered
   for (int cb = c_begin; cb < c_end; cb += CH) {
-    const int gn = min(CH, c_end - cb - CH);
+    const int gn = st.next_planes(cb);
 #pragma unroll
     for (int c = 0; c < CHT; ++c) gnxt[c] = Num<T>::ld(go_b + (int64_t)min(cb + CH - c_begin + c, cs_n - 1) * HW + p);
-    // unconditional, as in agg_fwd_stream_kernel (the last chunk re-requests one word pair)
-    agg_chunk_load<T>(s0 + (int64_t)(gn > 0 ? cb + CH - c_begin : 0) * Hs * Ws, gn > 0 ? gn * per_plane : 1, pre);
-    gc = min(CH, c_end - cb);
-    const float *pl = lds + cur * buf_sz;
+    st.prefetch(cb, gn);
+    const int gc = min(CH, c_end - cb);
+    const float *pl = st.planes();
     if (dense) {
-      auto load_row = [&](const float *rp, f32x2(&v)[NP + 1]) {
-#pragma unroll
-        for (int i = 0; i <= NP; ++i) {
-          v[i] = *reinterpret_cast<const f32x2 *>(rp + 4 * i);
-          asm volatile("" ::: "memory");
-        }
-      };
 #pragma unroll
       for (int c = 0; c < CHT; c += 2) {
         // a chunk shorter than CHT: weight 0 on a re-read of its last plane
         const float g0 = c < gc ? gcur[c] * inv_kk : 0.f, g1 = c + 1 < gc ? gcur[c + 1 < CHT ? c + 1 : c] * inv_kk : 0.f;
-        const float *p0_ = pl + min(c, gc - 1) * plane_sz, *p1_ = pl + min(c + 1, gc - 1) * plane_sz;
+        const float *p0_ = pl + min(c, gc - 1) * st.plane_sz, *p1_ = pl + min(c + 1, gc - 1) * st.plane_sz;
         const f32x2 gg0 = {g0, g0}, gg1 = {g1, g1};
         f32x2 v0[2][NP + 1], v1[2][NP + 1];
-        load_row(p0_ + ro[0], v0[0]);
-        load_row(p1_ + ro[0], v1[0]);
+        agg_load_row<NP + 1>(p0_ + ro[0], v0[0]);
+        agg_load_row<NP + 1>(p1_ + ro[0], v1[0]);
 #pragma unroll
         for (int r = 0; r <= K; ++r) {
           if (r < K) {
-            load_row(p0_ + ro[r + 1], v0[(r + 1) & 1]);
-            load_row(p1_ + ro[r + 1], v1[(r + 1) & 1]);
+            agg_load_row<NP + 1>(p0_ + ro[r + 1], v0[(r + 1) & 1]);
+            agg_load_row<NP + 1>(p1_ + ro[r + 1], v1[(r + 1) & 1]);
           }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1156,24 +918,20 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_ga_stream_kernel(
         }
       }
     } else if (active) {
-      // rare (a tap within rounding of an integer): tap by tap, published directly
+      // tap by tap, published directly
       for (int c = 0; c < gc; ++c) {
         const float go = Num<T>::ld(go_b + (int64_t)(cb - c_begin + c) * HW + p) * inv_kk;
-        const float *plc = pl + (size_t)c * plane_sz;
+        const float *plc = pl + (size_t)c * st.plane_sz;
 #pragma unroll 1
         for (int i = 0; i < K; ++i) {
-          const float dy = (fy0 + (float)(i - K / 2)) + (float)yf;
-          const float fdy = floorf(dy);
-          const int yTc = clampi((int)fdy, 0, Hs - 1), yBc = clampi((int)(fdy + 1), 0, Hs - 1);
-          const int yT = (yTc >> 1) * pitch + ((yTc & 1) << 1), yB = (yBc >> 1) * pitch + ((yBc & 1) << 1);
-          const float yB_P = dy - fdy, yT_P = 1 - yB_P;
+          const AggTapAxis ty = agg_tap_axis<K>(fy0, i, yf, Hs);
+          const int yT = agg_row_base(ty.lo, pitch), yB = agg_row_base(ty.hi, pitch);
+          const float yB_P = ty.w_hi, yT_P = 1 - yB_P;
 #pragma unroll 1
           for (int j = 0; j < K; ++j) {
-            const float dx = (fx0 + (float)(j - K / 2)) + (float)xf;
-            const float fdx = floorf(dx);
-            const int xLc = clampi((int)fdx, 0, Ws - 1), xRc = clampi((int)(fdx + 1), 0, Ws - 1);
-            const int xL = ((xLc >> 1) << 2) + (xLc & 1), xR = ((xRc >> 1) << 2) + (xRc & 1);
-            const float xR_P = dx - fdx, xL_P = 1 - xR_P;
+            const AggTapAxis tx = agg_tap_axis<K>(fx0, j, xf, Ws);
+            const int xL = agg_col_word(tx.lo), xR = agg_col_word(tx.hi);
+            const float xR_P = tx.w_hi, xL_P = 1 - xR_P;
             const float vTL = plc[yT + xL], vTR = plc[yT + xR], vBL = plc[yB + xL], vBR = plc[yB + xR];
             float bs = (xL_P * yT_P) * vTL;
             bs += (xR_P * yT_P) * vTR;
@@ -1188,11 +946,9 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_ga_stream_kernel(
           }
         }
       }
-      __builtin_amdgcn_s_waitcnt(0x0F70);   // (as in agg_fwd_stream_kernel: nothing of this branch stays pending)
+      agg_taps_done();
     }
-    cur ^= 1;
-    if (gn > 0) agg_chunk_store(lds + cur * buf_sz, gn * per_plane, pre, off);
-    __builtin_amdgcn_s_waitcnt(0x0F70);     // the prefetch and the next chunk's gradients have landed
+    st.commit(gn);   // the prefetch and the next chunk's gradients have landed
 #pragma unroll
     for (int c = 0; c < CHT; ++c) gcur[c] = gnxt[c];
     __syncthreads();
@@ -1263,22 +1019,17 @@ template <typename T>
 int rs_bwd2_stream(const T *in1, const T *in2, const T *gout, float *gin2, int64_t B, int64_t C, int64_t Hi, int64_t Wi,
                    int64_t H, int64_t W, hipStream_t stream) {
   constexpr int k = 3;
-  if (tuning(3) == 1 || tuning(8) == 1 || Wi < k + 1 || (Wi & 1) || Wi >= 32768 || Hi >= 32000 ||
-      B * C * Hi * Wi >= (1LL << 31) || B * C * H * W >= (1LL << 31) || B > 65535)
+  // B <= 65535 and B C H W < 2^31: bounds this entry has always had.  The kernel needs neither (it decodes the sample
+  // from blockIdx.x and indexes the flow map in 64 bits); dropping them would move calls onto another kernel.
+  if (!agg_stream_enabled() || !agg_stream_shape_ok(B, C, Hi, Wi, k, true) || B * C * H * W >= (1LL << 31))
     return GFLA_ERR_UNSUPPORTED;
-  const AggStreamGeo pg = agg_stream_geometry(B, C, Hi, Wi, H, W, k);
-  const int64_t total = B * pg.nsuper * pg.tgroups;
-  const int64_t padded = ceil_div(total, kNumXCD) * kNumXCD;
-  if (pg.CH <= 0 || padded > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-#define GFLA_RS2_LAUNCH(CV)                                                                                              \
-  launch_lds(agg_ga_stream_kernel<T, 3, 1, CV>, dim3((unsigned)padded), dim3(pg.threads), pg.lds, stream, in1, in2, gout, \
-             (float *)nullptr, (const T *)nullptr, gin2, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, pg.CH, pg.CS, pg.nsuper, \
-             pg.tgroups, pg.pitch, (int)total, pg.tw_log2, pg.ntile)
-  if (pg.CH <= 2) GFLA_RS2_LAUNCH(2);
-  else if (pg.CH <= 4) GFLA_RS2_LAUNCH(4);
-  else if (pg.CH <= 6) GFLA_RS2_LAUNCH(6);
-  else GFLA_RS2_LAUNCH(8);
-#undef GFLA_RS2_LAUNCH
+  AggStreamPlan pl;
+  if (!agg_stream_plan(B, C, Hi, Wi, H, W, k, pl)) return GFLA_ERR_UNSUPPORTED;
+  const AggStreamGeo &pg = pl.pg;
+  GFLA_AGG_CHT_SWITCH(pg.CH, launch_lds(agg_ga_stream_kernel<T, 3, 1, CHT>, dim3((unsigned)pl.padded), dim3(pg.threads), pg.lds,
+                                        stream, in1, in2, gout, (float *)nullptr, (const T *)nullptr, gin2, (int)C, (int)Hi,
+                                        (int)Wi, (int)H, (int)W, pg.CH, pg.CS, pg.nsuper, pg.tgroups, pg.pitch,
+                                        (int)pl.total, pg.tw_log2, pg.ntile));
   return launch_status();
 }
 template int rs_bwd2_stream<float>(const float *, const float *, const float *, float *, int64_t, int64_t, int64_t, int64_t,
@@ -1345,6 +1096,7 @@ static int agg_check(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, in
     default: { constexpr int K = 5; __VA_ARGS__; } break; \
   }
 
+
 template <typename T>
 static int aggregate_fwd(const T *src, const T *flow, const T *logits, T *out, T *attn_out, int64_t B,
                          int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k, int sm,
@@ -1356,39 +1108,20 @@ static int aggregate_fwd(const T *src, const T *flow, const T *logits, T *out, T
   using A = typename Num<T>::acc;
   if constexpr (std::is_same<A, float>::value) {
     // coefficient-table path: needs the caller's workspace (gfla_aggregate_fwd_workspace_bytes)
-    // k = 3 has 16 patch words per output instead of 36: there the per-group setup of agg_fwd_lds_kernel costs less than
-    // the extra pass (23 us against 20 + 5 at the bench shape); tuning key 8 = 2 forces the table path, 1 disables it
-    if (workspace && tuning(3) != 1 && tuning(8) != 1 && (k >= 5 || tuning(8) == 2) && (k & 1) && Ws >= k + 1 && !(Ws & 1) && Ws < 32768 && Hs < 32000 &&
-        B * C * Hs * Ws < (1LL << 31)) {
-      AggStreamGeo pg = agg_stream_geometry(B, C, Hs, Ws, H, W, k);
-      const int64_t total = B * pg.nsuper * pg.tgroups;
-      const int64_t padded = ceil_div(total, kNumXCD) * kNumXCD;
-      if (pg.CH > 0 && padded <= 0x7fffffffLL && B <= 65535) {
-        float *table = static_cast<float *>(workspace);
-        const dim3 cgrid((unsigned)ceil_div(pg.ntile, kAggCoefThreads / 64), (unsigned)B);
-#define GFLA_AGG_TAB(KV)                                                                                                  \
-  agg_coef_kernel<T, KV><<<cgrid, dim3(kAggCoefThreads), 0, stream>>>(flow, logits, attn_out, table, (int)Hs, (int)Ws,        \
-                                                                      (int)H, (int)W, sm, pg.tw_log2, pg.ntile);           \
-  GFLA_AGG_MAIN(KV)
-#define GFLA_AGG_LAUNCH(KV, CV)                                                                                           \
-  launch_lds(agg_fwd_stream_kernel<T, KV, CV>, dim3((unsigned)padded), dim3(pg.threads), pg.lds, stream, src, flow, logits, \
-             (const float *)table, out, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, sm, pg.CH, pg.CS, pg.nsuper, pg.tgroups, \
-             pg.pitch, (int)total, pg.tw_log2, pg.ntile)
-#define GFLA_AGG_MAIN(KV)                                          \
-  if (pg.CH <= 2) GFLA_AGG_LAUNCH(KV, 2);                          \
-  else if (pg.CH <= 4) GFLA_AGG_LAUNCH(KV, 4);                     \
-  else if (pg.CH <= 6) GFLA_AGG_LAUNCH(KV, 6);                     \
-  else GFLA_AGG_LAUNCH(KV, 8)
-        switch (k) {
-          case 1: GFLA_AGG_TAB(1); break;
-          case 3: GFLA_AGG_TAB(3); break;
-          default: GFLA_AGG_TAB(5); break;
-        }
-#undef GFLA_AGG_TAB
-#undef GFLA_AGG_MAIN
-#undef GFLA_AGG_LAUNCH
-        return launch_status();
-      }
+    AggStreamPlan pl;
+    if (workspace && agg_stream_wanted(k) && agg_stream_shape_ok(B, C, Hs, Ws, k, true) &&
+        agg_stream_plan(B, C, Hs, Ws, H, W, k, pl)) {
+      const AggStreamGeo &pg = pl.pg;
+      float *table = static_cast<float *>(workspace);
+      const dim3 cgrid((unsigned)ceil_div(pg.ntile, kAggCoefThreads / 64), (unsigned)B);
+      GFLA_AGG_ODD_K_SWITCH(
+          k, agg_coef_kernel<T, K><<<cgrid, dim3(kAggCoefThreads), 0, stream>>>(flow, logits, attn_out, table, (int)Hs, (int)Ws,
+                                                                               (int)H, (int)W, sm, pg.tw_log2, pg.ntile);
+          GFLA_AGG_CHT_SWITCH(pg.CH, launch_lds(agg_fwd_stream_kernel<T, K, CHT>, dim3((unsigned)pl.padded), dim3(pg.threads),
+                                                pg.lds, stream, src, flow, logits, (const float *)table, out, (int)C, (int)Hs,
+                                                (int)Ws, (int)H, (int)W, sm, pg.CH, pg.CS, pg.nsuper, pg.tgroups, pg.pitch,
+                                                (int)pl.total, pg.tw_log2, pg.ntile)));
+      return launch_status();
     }
   }
   if (tuning(3) != 1) {
@@ -1396,7 +1129,7 @@ static int aggregate_fwd(const T *src, const T *flow, const T *logits, T *out, T
     if (pg.G > 0) {
       const int64_t blocks = B * pg.ngroups * pg.split;
       if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-      GFLA_K_SWITCH(k, launch_lds(agg_fwd_lds_kernel<T, K>, dim3((unsigned)blocks), dim3(kLdsThreads), pg.lds_bytes, stream, 
+      GFLA_K_SWITCH(k, launch_lds(agg_fwd_lds_kernel<T, K>, dim3((unsigned)blocks), dim3(kLdsThreads), pg.lds_bytes, stream,
                            src, flow, logits, out, attn_out, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, sm, pg.G, pg.ngroups, pg.split));
       return launch_status();
     }
@@ -1412,58 +1145,40 @@ template <typename T>
 static int launch_agg_ga(const T *src, const T *flow, const T *attn, const T *gout, typename Num<T>::acc *glogits,
                          typename Num<T>::acc *gflow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k, int sm, hipStream_t stream) {
   using A = typename Num<T>::acc;
+  bool launched = false;
   if constexpr (std::is_same<A, float>::value) {
-    // streaming kernel (interleaved planes, paired reads); tuning key 8 = 1: round 1's kernel
-    if (tuning(3) != 1 && tuning(8) != 1 && (k >= 5 || tuning(8) == 2) && (k & 1) && Ws >= k + 1 && !(Ws & 1) && Ws < 32768 && Hs < 32000 &&
-        B * C * Hs * Ws < (1LL << 31)) {
-      const AggStreamGeo pg = agg_stream_geometry(B, C, Hs, Ws, H, W, k);
-      const int64_t total = B * pg.nsuper * pg.tgroups;
-      const int64_t padded = ceil_div(total, kNumXCD) * kNumXCD;
-      if (pg.CH > 0 && padded <= 0x7fffffffLL) {
-#define GFLA_AGG_GA_LAUNCH(KV, CV)                                                                                       \
-  launch_lds(agg_ga_stream_kernel<T, KV, 0, CV>, dim3((unsigned)padded), dim3(pg.threads), pg.lds, stream, src, flow, gout, \
-             (float *)glogits, gflow ? attn : (const T *)nullptr, (float *)gflow, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, \
-             pg.CH, pg.CS, pg.nsuper, pg.tgroups, pg.pitch, (int)total, pg.tw_log2, pg.ntile)
-#define GFLA_AGG_GA(KV)                                 \
-  if (pg.CH <= 2) GFLA_AGG_GA_LAUNCH(KV, 2);            \
-  else if (pg.CH <= 4) GFLA_AGG_GA_LAUNCH(KV, 4);       \
-  else if (pg.CH <= 6) GFLA_AGG_GA_LAUNCH(KV, 6);       \
-  else GFLA_AGG_GA_LAUNCH(KV, 8)
-        switch (k) {
-          case 1: GFLA_AGG_GA(1); break;
-          case 3: GFLA_AGG_GA(3); break;
-          default: GFLA_AGG_GA(5); break;
-        }
-#undef GFLA_AGG_GA
-#undef GFLA_AGG_GA_LAUNCH
-        int st = launch_status();
-        if (st == GFLA_OK && sm && glogits) {
-          const int64_t n = B * H * W;
-          GFLA_K_SWITCH(k, agg_softmax_bwd_kernel<T, K><<<dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, stream>>>(
-                               attn, glogits, n, (int)(H * W)));
-          st = launch_status();
-        }
-        return st;
-      }
+    // streaming kernel (interleaved planes, paired reads); no coefficient pass here, so no bound on B
+    AggStreamPlan pl;
+    if (agg_stream_wanted(k) && agg_stream_shape_ok(B, C, Hs, Ws, k, false) && agg_stream_plan(B, C, Hs, Ws, H, W, k, pl)) {
+      const AggStreamGeo &pg = pl.pg;
+      GFLA_AGG_ODD_K_SWITCH(
+          k, GFLA_AGG_CHT_SWITCH(pg.CH, launch_lds(agg_ga_stream_kernel<T, K, 0, CHT>, dim3((unsigned)pl.padded), dim3(pg.threads),
+                                                   pg.lds, stream, src, flow, gout, (float *)glogits,
+                                                   gflow ? attn : (const T *)nullptr, (float *)gflow, (int)C, (int)Hs, (int)Ws,
+                                                   (int)H, (int)W, pg.CH, pg.CS, pg.nsuper, pg.tgroups, pg.pitch, (int)pl.total,
+                                                   pg.tw_log2, pg.ntile)));
+      launched = true;
     }
   }
-  const int threads = 512;
-  const int64_t ntiles = ceil_div(H * W, threads);
-  int64_t G = kLdsBudget / (Hs * Ws * (int64_t)sizeof(A));
-  if (G < 1) return GFLA_ERR_UNSUPPORTED;
-  if (G > C) G = C;
-  int64_t nsuper = 1;  // split the channels until the launch has >= 4 workgroups per CU
-  while (B * ntiles * nsuper < 4 * kNumCU && nsuper * 2 * G <= C) nsuper *= 2;
-  const int64_t CS = ceil_div(C, nsuper);
-  nsuper = ceil_div(C, CS);
-  if (G > CS) G = CS;
-  const int64_t blocks = B * nsuper * ntiles;
-  if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-  const unsigned lds = (unsigned)(G * Hs * Ws * sizeof(A));
-  const int64_t padded = ceil_div(blocks, kNumXCD) * kNumXCD;  // the XCD remap needs a multiple of 8
-  GFLA_K_SWITCH(k, agg_ga_lds_kernel<T, K><<<dim3((unsigned)padded), dim3(threads), lds, stream>>>(
-                       src, flow, gout, glogits, gflow ? attn : nullptr, gflow, (int)C, (int)Hs, (int)Ws, (int)H, (int)W,
-                       (int)G, (int)nsuper, (int)CS, (int)ntiles, (int)blocks));
+  if (!launched) {
+    const int threads = 512;
+    const int64_t ntiles = ceil_div(H * W, threads);
+    int64_t G = kLdsBudget / (Hs * Ws * (int64_t)sizeof(A));
+    if (G < 1) return GFLA_ERR_UNSUPPORTED;
+    if (G > C) G = C;
+    int64_t nsuper = 1;  // split the channels until the launch has >= 4 workgroups per CU
+    while (B * ntiles * nsuper < 4 * kNumCU && nsuper * 2 * G <= C) nsuper *= 2;
+    const int64_t CS = ceil_div(C, nsuper);
+    nsuper = ceil_div(C, CS);
+    if (G > CS) G = CS;
+    const int64_t blocks = B * nsuper * ntiles;
+    if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
+    const unsigned lds = (unsigned)(G * Hs * Ws * sizeof(A));
+    const int64_t padded = ceil_div(blocks, kNumXCD) * kNumXCD;  // the XCD remap needs a multiple of 8
+    GFLA_K_SWITCH(k, agg_ga_lds_kernel<T, K><<<dim3((unsigned)padded), dim3(threads), lds, stream>>>(
+                         src, flow, gout, glogits, gflow ? attn : nullptr, gflow, (int)C, (int)Hs, (int)Ws, (int)H, (int)W,
+                         (int)G, (int)nsuper, (int)CS, (int)ntiles, (int)blocks));
+  }
   int st = launch_status();
   if (st == GFLA_OK && sm && glogits) {
     const int64_t n = B * H * W;
@@ -1560,26 +1275,72 @@ static int local_attn_source_bwd(const T *src, const T *flow, const T *gunf, con
 
 }  // namespace gfla
 
-using gfla::bf16_t;
-using gfla::f16_t;
+// ---- extern "C": one definer per GFLA_DECL_* family of include/gfla_hip.h, instantiated per suffix --------------------
+namespace gfla {
+// element type behind an entry point's suffix (16-bit storage crosses the ABI as uint16_t)
+typedef float elem_f32;
+typedef double elem_f64;
+typedef bf16_t elem_bf16;
+typedef f16_t elem_f16;
+template <typename E, typename S>
+static inline auto as(S *p) { return reinterpret_cast<std::conditional_t<std::is_const<S>::value, const E, E> *>(p); }
+}  // namespace gfla
+
+#define GFLA_SHAPE_PARAMS int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W
+#define GFLA_SHAPE_ARGS B, C, Hs, Ws, H, W
+
+#define GFLA_DEF_AGGREGATE_FWD(SFX, T)                                                                                   \
+  int gfla_local_attn_aggregate_fwd_##SFX(const T *s, const T *f, const T *l, T *o, T *a, GFLA_SHAPE_PARAMS, int k, int sm, \
+                                          gfla_stream_t st) {                                                            \
+    using E = gfla::elem_##SFX;                                                                                          \
+    return gfla::aggregate_fwd<E>(gfla::as<E>(s), gfla::as<E>(f), gfla::as<E>(l), gfla::as<E>(o), gfla::as<E>(a),        \
+                                  GFLA_SHAPE_ARGS, k, sm, st);                                                           \
+  }
+#define GFLA_DEF_AGGREGATE_FWD_WS(SFX, T)                                                                                \
+  int gfla_local_attn_aggregate_fwd_ws_##SFX(const T *s, const T *f, const T *l, T *o, T *a, void *workspace,            \
+                                             GFLA_SHAPE_PARAMS, int k, int sm, gfla_stream_t st) {                       \
+    using E = gfla::elem_##SFX;                                                                                          \
+    return gfla::aggregate_fwd<E>(gfla::as<E>(s), gfla::as<E>(f), gfla::as<E>(l), gfla::as<E>(o), gfla::as<E>(a),        \
+                                  GFLA_SHAPE_ARGS, k, sm, st, workspace);                                                \
+  }
+// R = type of the gradients that are reductions over channels (grad_flow, grad_logits): T for f32 / f64 (AGGREGATE_BWD,
+// SOURCE_BWD), float for 16-bit storage (BWD16)
+#define GFLA_DEF_AGGREGATE_BWD(SFX, T, R)                                                                                \
+  int gfla_local_attn_aggregate_bwd_##SFX(const T *s, const T *f, const T *a, const T *go, T *gs, R *gf, R *gl,          \
+                                          GFLA_SHAPE_PARAMS, int k, int sm, gfla_stream_t st) {                          \
+    using E = gfla::elem_##SFX;                                                                                          \
+    return gfla::aggregate_bwd<E>(gfla::as<E>(s), gfla::as<E>(f), gfla::as<E>(a), gfla::as<E>(go), gfla::as<E>(gs), gf,  \
+                                  gl, GFLA_SHAPE_ARGS, k, sm, st);                                                       \
+  }
+#define GFLA_DEF_SOURCE_BWD(SFX, T, R)                                                                                   \
+  int gfla_local_attn_source_bwd_##SFX(const T *s, const T *f, const T *gu, const T *a, const T *go, T *gs, R *gf,       \
+                                       GFLA_SHAPE_PARAMS, int k, int layout, gfla_stream_t st) {                         \
+    using E = gfla::elem_##SFX;                                                                                          \
+    return gfla::local_attn_source_bwd<E>(gfla::as<E>(s), gfla::as<E>(f), gfla::as<E>(gu), gfla::as<E>(a),               \
+                                          gfla::as<E>(go), gfla::as<E>(gs), gf, GFLA_SHAPE_ARGS, k, layout, st);         \
+  }
 
 extern "C" {
-int gfla_local_attn_aggregate_fwd_f32(const float *s, const float *f, const float *l, float *o, float *a,
-                                      int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W,
-                                      int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_fwd<float>(s, f, l, o, a, B, C, Hs, Ws, H, W, k, sm, st);
-}
-int gfla_local_attn_aggregate_fwd_f64(const double *s, const double *f, const double *l, double *o,
-                                      double *a, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H,
-                                      int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_fwd<double>(s, f, l, o, a, B, C, Hs, Ws, H, W, k, sm, st);
-}
-int gfla_local_attn_aggregate_fwd_bf16(const uint16_t *s, const uint16_t *f, const uint16_t *l,
-                                       uint16_t *o, uint16_t *a, int64_t B, int64_t C, int64_t Hs,
-                                       int64_t Ws, int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_fwd<bf16_t>(reinterpret_cast<const bf16_t *>(s), reinterpret_cast<const bf16_t *>(f),
-                                     reinterpret_cast<const bf16_t *>(l), reinterpret_cast<bf16_t *>(o),
-                                     reinterpret_cast<bf16_t *>(a), B, C, Hs, Ws, H, W, k, sm, st);
+GFLA_DEF_AGGREGATE_FWD(f32, float)
+GFLA_DEF_AGGREGATE_FWD(f64, double)
+GFLA_DEF_AGGREGATE_FWD(bf16, uint16_t)
+GFLA_DEF_AGGREGATE_FWD(f16, uint16_t)
+GFLA_DEF_AGGREGATE_FWD_WS(f32, float)
+GFLA_DEF_AGGREGATE_FWD_WS(bf16, uint16_t)
+GFLA_DEF_AGGREGATE_FWD_WS(f16, uint16_t)
+GFLA_DEF_AGGREGATE_BWD(f32, float, float)
+GFLA_DEF_AGGREGATE_BWD(f64, double, double)
+GFLA_DEF_SOURCE_BWD(f32, float, float)
+GFLA_DEF_SOURCE_BWD(f64, double, double)
+GFLA_DEF_AGGREGATE_BWD(bf16, uint16_t, float)  // this file's part of GFLA_DECL_BWD16 (bf16: declared long-hand there)
+GFLA_DEF_AGGREGATE_BWD(f16, uint16_t, float)
+GFLA_DEF_SOURCE_BWD(bf16, uint16_t, float)
+GFLA_DEF_SOURCE_BWD(f16, uint16_t, float)
+/* the _ws twin of AGGREGATE_BWD exists for f32 only: workspace = gfla_scatter_workspace_bytes */
+int gfla_local_attn_aggregate_bwd_ws_f32(const float *s, const float *f, const float *a, const float *go, float *gs,
+                                         float *gf, float *gl, void *workspace, GFLA_SHAPE_PARAMS, int k, int sm,
+                                         gfla_stream_t st) {
+  return gfla::aggregate_bwd<float>(s, f, a, go, gs, gf, gl, GFLA_SHAPE_ARGS, k, sm, st, workspace);
 }
 /* scratch for the coefficient-table forward: (k+1)(k+2) floats + one packed word per flow pixel */
 int64_t gfla_aggregate_fwd_workspace_bytes(int64_t B, int64_t H, int64_t W, int k) {
@@ -1588,41 +1349,19 @@ int64_t gfla_aggregate_fwd_workspace_bytes(int64_t B, int64_t H, int64_t W, int 
   for (int l = 3; l <= 5; ++l) tiles = std::max<int64_t>(tiles, gfla::ceil_div(W, 1 << l) * gfla::ceil_div(H, 64 >> l));
   return B * tiles * 64 * (int64_t)gfla::agg_record_floats(k) * 4;
 }
-/* launch geometry of the table path (host logic only, for the CPU tests):
- * out[0..8] = channels per chunk, channels per range, ranges, tile groups, threads, LDS row-pair pitch (words), tile
- * width, tiles per sample, dynamic LDS bytes; returns GFLA_ERR_UNSUPPORTED where the plain kernels are used */
+/* launch geometry the table path WOULD use for these sizes (host logic only, for the CPU tests): out[0..8] = channels
+ * per chunk, channels per range, ranges, tile groups, threads, LDS row-pair pitch (words), tile width, tiles per sample,
+ * dynamic LDS bytes.  GFLA_ERR_UNSUPPORTED where the stream kernels cannot take the shape (agg_stream_shape_ok, or no
+ * chunk fits LDS); whether the default dispatch takes the path (agg_stream_wanted) is not part of the answer */
 int gfla_aggregate_fwd_geometry(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k, int64_t *out) {
   if (!out) return GFLA_ERR_NULL_POINTER;
   if (B <= 0 || C <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || k < 1 || k > 5) return GFLA_ERR_BAD_SHAPE;
-  if (!(k & 1) || Ws < k + 1 || (Ws & 1) || Ws >= 32768 || Hs >= 32000 || B * C * Hs * Ws >= (1LL << 31) || B > 65535)
-    return GFLA_ERR_UNSUPPORTED;
+  if (!gfla::agg_stream_shape_ok(B, C, Hs, Ws, k, true)) return GFLA_ERR_UNSUPPORTED;
   const gfla::AggStreamGeo g = gfla::agg_stream_geometry(B, C, Hs, Ws, H, W, k);
   if (g.CH <= 0) return GFLA_ERR_UNSUPPORTED;
   const int64_t v[9] = {g.CH, g.CS, g.nsuper, g.tgroups, g.threads, g.pitch, 1 << g.tw_log2, g.ntile, g.lds};
   for (int i = 0; i < 9; ++i) out[i] = v[i];
   return GFLA_OK;
-}
-int gfla_local_attn_aggregate_fwd_ws_f32(const float *s, const float *f, const float *l, float *o, float *a,
-                                         void *workspace, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H,
-                                         int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_fwd<float>(s, f, l, o, a, B, C, Hs, Ws, H, W, k, sm, st, workspace);
-}
-int gfla_local_attn_aggregate_fwd_ws_bf16(const uint16_t *s, const uint16_t *f, const uint16_t *l, uint16_t *o,
-                                          uint16_t *a, void *workspace, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
-                                          int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_fwd<bf16_t>(reinterpret_cast<const bf16_t *>(s), reinterpret_cast<const bf16_t *>(f),
-                                     reinterpret_cast<const bf16_t *>(l), reinterpret_cast<bf16_t *>(o),
-                                     reinterpret_cast<bf16_t *>(a), B, C, Hs, Ws, H, W, k, sm, st, workspace);
-}
-int gfla_local_attn_aggregate_bwd_f32(const float *s, const float *f, const float *a, const float *go,
-                                      float *gs, float *gf, float *gl, int64_t B, int64_t C, int64_t Hs,
-                                      int64_t Ws, int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_bwd<float>(s, f, a, go, gs, gf, gl, B, C, Hs, Ws, H, W, k, sm, st);
-}
-int gfla_local_attn_aggregate_bwd_ws_f32(const float *s, const float *f, const float *a, const float *go, float *gs,
-                                         float *gf, float *gl, void *workspace, int64_t B, int64_t C, int64_t Hs,
-                                         int64_t Ws, int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_bwd<float>(s, f, a, go, gs, gf, gl, B, C, Hs, Ws, H, W, k, sm, st, workspace);
 }
 /* 1 when gfla_local_attn_aggregate_bwd_<storage> takes source planes of Hs x Ws (elem_size 2 = bf16, 4 = f32, 8 = f64).
  * f32 / f64 always do (global-memory kernels behind the planes-in-LDS ones); bf16 storage exists for the planes-in-LDS
@@ -1632,68 +1371,5 @@ int gfla_aggregate_bwd_supported(int64_t Hs, int64_t Ws, int elem_size) {
   if (Hs <= 0 || Ws <= 0 || (elem_size != 2 && elem_size != 4 && elem_size != 8)) return 0;
   if (elem_size != 2) return 1;
   return Hs * Ws * (int64_t)(sizeof(gfla::lds_acc_t) + sizeof(float)) <= gfla::lds_budget() ? 1 : 0;
-}
-/* bf16 storage: grad_source bf16; grad_flow and grad_logits FLOAT32 (reductions over channels, accumulated across
- * workgroups) */
-int gfla_local_attn_aggregate_bwd_bf16(const uint16_t *s, const uint16_t *f, const uint16_t *a, const uint16_t *go,
-                                       uint16_t *gs, float *gf, float *gl, int64_t B, int64_t C, int64_t Hs,
-                                       int64_t Ws, int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_bwd<bf16_t>(reinterpret_cast<const bf16_t *>(s), reinterpret_cast<const bf16_t *>(f),
-                                     reinterpret_cast<const bf16_t *>(a), reinterpret_cast<const bf16_t *>(go),
-                                     reinterpret_cast<bf16_t *>(gs), gf, gl, B, C, Hs, Ws, H, W, k, sm, st);
-}
-int gfla_local_attn_aggregate_bwd_f64(const double *s, const double *f, const double *a, const double *go,
-                                      double *gs, double *gf, double *gl, int64_t B, int64_t C,
-                                      int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k, int sm,
-                                      gfla_stream_t st) {
-  return gfla::aggregate_bwd<double>(s, f, a, go, gs, gf, gl, B, C, Hs, Ws, H, W, k, sm, st);
-}
-int gfla_local_attn_source_bwd_f32(const float *s, const float *f, const float *gu, const float *a, const float *go,
-                                   float *gs, float *gf, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H,
-                                   int64_t W, int k, int layout, gfla_stream_t st) {
-  return gfla::local_attn_source_bwd<float>(s, f, gu, a, go, gs, gf, B, C, Hs, Ws, H, W, k, layout, st);
-}
-int gfla_local_attn_source_bwd_bf16(const uint16_t *s, const uint16_t *f, const uint16_t *gu, const uint16_t *a,
-                                    const uint16_t *go, uint16_t *gs, float *gf, int64_t B, int64_t C, int64_t Hs,
-                                    int64_t Ws, int64_t H, int64_t W, int k, int layout, gfla_stream_t st) {
-  return gfla::local_attn_source_bwd<bf16_t>(reinterpret_cast<const bf16_t *>(s), reinterpret_cast<const bf16_t *>(f),
-                                             reinterpret_cast<const bf16_t *>(gu), reinterpret_cast<const bf16_t *>(a),
-                                             reinterpret_cast<const bf16_t *>(go), reinterpret_cast<bf16_t *>(gs), gf, B, C,
-                                             Hs, Ws, H, W, k, layout, st);
-}
-int gfla_local_attn_source_bwd_f64(const double *s, const double *f, const double *gu, const double *a,
-                                   const double *go, double *gs, double *gf, int64_t B, int64_t C, int64_t Hs,
-                                   int64_t Ws, int64_t H, int64_t W, int k, int layout, gfla_stream_t st) {
-  return gfla::local_attn_source_bwd<double>(s, f, gu, a, go, gs, gf, B, C, Hs, Ws, H, W, k, layout, st);
-}
-/* f16 storage: the bf16 entry points' twins (same kernels, IEEE binary16 loads and stores) */
-int gfla_local_attn_aggregate_fwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *l,
-                                      uint16_t *o, uint16_t *a, int64_t B, int64_t C, int64_t Hs,
-                                      int64_t Ws, int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_fwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
-                                    reinterpret_cast<const f16_t *>(l), reinterpret_cast<f16_t *>(o),
-                                    reinterpret_cast<f16_t *>(a), B, C, Hs, Ws, H, W, k, sm, st);
-}
-int gfla_local_attn_aggregate_fwd_ws_f16(const uint16_t *s, const uint16_t *f, const uint16_t *l, uint16_t *o,
-                                         uint16_t *a, void *workspace, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
-                                         int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_fwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
-                                    reinterpret_cast<const f16_t *>(l), reinterpret_cast<f16_t *>(o),
-                                    reinterpret_cast<f16_t *>(a), B, C, Hs, Ws, H, W, k, sm, st, workspace);
-}
-int gfla_local_attn_aggregate_bwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *a, const uint16_t *go,
-                                      uint16_t *gs, float *gf, float *gl, int64_t B, int64_t C, int64_t Hs,
-                                      int64_t Ws, int64_t H, int64_t W, int k, int sm, gfla_stream_t st) {
-  return gfla::aggregate_bwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
-                                    reinterpret_cast<const f16_t *>(a), reinterpret_cast<const f16_t *>(go),
-                                    reinterpret_cast<f16_t *>(gs), gf, gl, B, C, Hs, Ws, H, W, k, sm, st);
-}
-int gfla_local_attn_source_bwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *gu, const uint16_t *a,
-                                   const uint16_t *go, uint16_t *gs, float *gf, int64_t B, int64_t C, int64_t Hs,
-                                   int64_t Ws, int64_t H, int64_t W, int k, int layout, gfla_stream_t st) {
-  return gfla::local_attn_source_bwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
-                                            reinterpret_cast<const f16_t *>(gu), reinterpret_cast<const f16_t *>(a),
-                                            reinterpret_cast<const f16_t *>(go), reinterpret_cast<f16_t *>(gs), gf, B, C,
-                                            Hs, Ws, H, W, k, layout, st);
 }
 }
