@@ -19,7 +19,7 @@ from .instance_norm import (InstanceNormAct, InstanceNormActFunction, fuse_insta
                             instance_norm_act)
 from .head_conv import (HeadConv3x3, HeadConv3x3Function, flow_mask_heads, fuse_output_heads, head_conv3x3,  # noqa: F401
                         patch_reference_flow_heads, torch_head_conv3x3)
-from .gen_conv import (InferenceConv, conv3x3, conv4x4_down, conv_transpose3x3_up, fuse_inference_convs,  # noqa: F401
+from .gen_conv import (GenConvFunction, InferenceConv, conv3x3, conv4x4_down, conv_transpose3x3_up, fuse_inference_convs,  # noqa: F401
                        patch_reference_convs, torch_gen_conv)
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401

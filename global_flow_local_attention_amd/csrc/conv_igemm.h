@@ -39,6 +39,12 @@
 //   kCvVggFwd  y = max(0, bias + conv(x, w)), S1K3 only
 //   kCvVggBwd  dx = conv(g [ysaved > 0], w), S1K3 only, the weights packed mirrored with Cin <-> Cout (the extractor is
 //              frozen: no weight gradient); no bias, no ReLU
+//   kCvGrad    dx = act'(x) conv(g, w) on the adjoint geometry, the weights packed for it: S1K3 mirrored with Cin <-> Cout,
+//              S2K3 (the adjoint of T2K3: k 3, s 2, p 1, halo (2 TH + 1) x (2 TW + 1), the taps as stored) and U2K4 (the
+//              adjoint of S2K4: tiled over the half-resolution grid, four output phases of 2 x 2 taps, halo (TH + 2) x
+//              (TW + 2) of g); aux = x, act'(x) = x > 0 ? 1 : slope read by the lane that writes the element; no bias
+//   kCvGradPad the S1K3 adjoint on the (H + 2) x (W + 2) padded domain of a reflect convolution, stored as float32 (the
+//              fold onto x follows in gen_conv_bwd.hip)
 //
 // The reduction order per output element is chunk ascending, tap ascending, then the k of the MFMA.  No atomics anywhere.
 #pragma once
@@ -56,14 +62,16 @@ typedef __bf16 cv_bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int kCvRec = 32;        // bytes of one pixel (or one output channel) of one chunk
 constexpr int kCvMB = 2;          // 32-channel MFMA tiles per wave
 constexpr int64_t kCvMaxC = 1 << 16;
-enum { kCvGen = 0, kCvVggFwd = 1, kCvVggBwd = 2 };
+enum { kCvGen = 0, kCvVggFwd = 1, kCvVggBwd = 2, kCvGrad = 3, kCvGradPad = 4 };
 
 // per geometry: 32-pixel MFMA tiles per wave, output phases per tiled pixel, taps, and the 4-byte words of the halo tile a
 // thread stages per chunk (8 * largest halo / 256, rounded up)
 struct CvGeo {
   int NB, PH, TAPS, ITEMS;
 };
-constexpr CvGeo kCvGeo[3] = {{2, 1, 9, 11}, {2, 1, 16, 21}, {1, 4, 9, 6}};
+// 0 .. 2: the forward geometries; 3, 4: the adjoints of the two strided ones (gen_conv_bwd.hip), never an entry point's
+constexpr int kCvS2K3 = 3, kCvU2K4 = 4;
+constexpr CvGeo kCvGeo[5] = {{2, 1, 9, 11}, {2, 1, 16, 21}, {1, 4, 9, 6}, {2, 1, 9, 19}, {1, 4, 16, 7}};
 
 template <typename T>
 constexpr int cv_ck() { return kCvRec / (int)sizeof(T); }
@@ -102,11 +110,11 @@ static void cv_out_size(int geometry, int64_t H, int64_t W, int64_t *Hout, int64
   *Wout = geometry == 0 ? W : geometry == 1 ? (W - 2) / 2 + 1 : 2 * W;
 }
 
-static CvTile cv_tile(int geometry, int64_t Cout, int64_t H, int64_t W) {
+// the tile of a TH_ x TW_ tiled map; Hout and Wout are the caller's to fill
+static CvTile cv_tile_of(int geometry, int64_t Cout, int64_t TH_, int64_t TW_) {
   CvTile g;
-  cv_out_size(geometry, H, W, &g.Hout, &g.Wout);
-  const int64_t TH_ = geometry == 1 ? g.Hout : H, TW_ = geometry == 1 ? g.Wout : W;    // the tiled map
-  g.WM = (geometry == 1 || Cout > 64) ? 2 : 1;
+  g.Hout = g.Wout = 0;
+  g.WM = (geometry == 1 || geometry == kCvS2K3 || Cout > 64) ? 2 : 1;
   const int pixels = (4 / g.WM) * kCvGeo[geometry].NB * 32;
   int64_t best = -1;
   g.tw_log2 = 5;
@@ -121,7 +129,19 @@ static CvTile cv_tile(int geometry, int64_t Cout, int64_t H, int64_t W) {
   g.TH = pixels >> g.tw_log2;
   g.tilesX = (int)ceil_div(TW_, TW);
   g.tilesY = (int)ceil_div(TH_, g.TH);
-  g.halo = geometry == 0 ? (g.TH + 2) * (TW + 2) : geometry == 1 ? (2 * g.TH + 2) * (2 * TW + 2) : (g.TH + 1) * (TW + 1);
+  g.halo = geometry == 0 || geometry == kCvU2K4 ? (g.TH + 2) * (TW + 2)
+           : geometry == 1                      ? (2 * g.TH + 2) * (2 * TW + 2)
+           : geometry == kCvS2K3                ? (2 * g.TH + 1) * (2 * TW + 1)
+                                                : (g.TH + 1) * (TW + 1);
+  return g;
+}
+
+static CvTile cv_tile(int geometry, int64_t Cout, int64_t H, int64_t W) {
+  int64_t Hout, Wout;
+  cv_out_size(geometry, H, W, &Hout, &Wout);
+  CvTile g = cv_tile_of(geometry, Cout, geometry == 1 ? Hout : H, geometry == 1 ? Wout : W);
+  g.Hout = Hout;
+  g.Wout = Wout;
   return g;
 }
 
@@ -133,7 +153,9 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
                                                                const float *__restrict__ bias, const T *aux, T *y, int Cin,
                                                                int Cout, int H, int W, int Hout, int Wout, int tw_log2,
                                                                int WM, int tilesX, int reflect, int pre_act, float slope) {
-  static_assert(V == kCvGen || G == 0, "the VGG variants exist for S1K3 only");
+  static_assert(G <= 2 || V == kCvGrad, "the adjoint geometries exist for the gradient variant only");
+  static_assert(V == kCvGen || V == kCvGrad || G == 0, "the VGG variants and the padded-domain gradient exist for S1K3 only");
+  static_assert(V != kCvGrad || (G != 1 && G != 2), "a gradient runs on the adjoint geometry");
   constexpr int CK = cv_ck<T>(), MB = kCvMB, NB = kCvGeo[G].NB, PH = kCvGeo[G].PH, TAPS = kCvGeo[G].TAPS;
   constexpr int ITEMS = kCvGeo[G].ITEMS;
   extern __shared__ __attribute__((aligned(16))) unsigned char cv_smem[];   // [2][halo pixel][32 bytes]
@@ -141,12 +163,15 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, kh = lane >> 5;
   const int WN = 4 / WM, wm = wave % WM, wn = wave / WM;
   const int TW = 1 << tw_log2, RS = 32 >> tw_log2, TH = WN * NB * RS;
-  const int HW = G == 0 ? TW + 2 : G == 1 ? 2 * TW + 2 : TW + 1;              // halo width and height, in input pixels
-  const int HH = G == 0 ? TH + 2 : G == 1 ? 2 * TH + 2 : TH + 1;
+  // halo width and height, in input pixels
+  const int HW = G == 0 || G == kCvU2K4 ? TW + 2 : G == 1 ? 2 * TW + 2 : G == kCvS2K3 ? 2 * TW + 1 : TW + 1;
+  const int HH = G == 0 || G == kCvU2K4 ? TH + 2 : G == 1 ? 2 * TH + 2 : G == kCvS2K3 ? 2 * TH + 1 : TH + 1;
   const int NPIX = HW * HH, bufB = NPIX * kCvRec;
   const int tyi = blockIdx.x / tilesX, txi = blockIdx.x - tyi * tilesX;
   const int y0 = tyi * TH, x0 = txi * TW;                                     // origin of the tile in the tiled map
-  const int iy0 = G == 0 ? y0 - 1 : G == 1 ? 2 * y0 - 1 : y0, ix0 = G == 0 ? x0 - 1 : G == 1 ? 2 * x0 - 1 : x0;
+  constexpr int O0 = V == kCvGradPad ? 2 : 1;      // kCvGradPad: the output is the padded domain, one pixel further out
+  const int iy0 = G == 0 || G == kCvU2K4 ? y0 - O0 : G == 1 || G == kCvS2K3 ? 2 * y0 - 1 : y0;
+  const int ix0 = G == 0 || G == kCvU2K4 ? x0 - O0 : G == 1 || G == kCvS2K3 ? 2 * x0 - 1 : x0;
   const int64_t plane = (int64_t)H * W, oplane = (int64_t)Hout * Wout;
   const T *xb = x + (int64_t)blockIdx.z * Cin * plane;
   const int NCH = (Cin + CK - 1) / CK, MP = (Cout + 31) / 32 * 32;
@@ -212,7 +237,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
 
   // B operand: column l31 of pixel tile s = wn * NB + j is pixel (py, px) of the tile's RS rows
   const int py = l31 >> tw_log2, px = l31 & (TW - 1);
-  constexpr int PS = G == 1 ? 2 : 1;                                          // input pixels per tiled pixel
+  constexpr int PS = G == 1 || G == kCvS2K3 ? 2 : 1;                                          // input pixels per tiled pixel
   int boff[NB];
 #pragma unroll
   for (int j = 0; j < NB; ++j) boff[j] = (PS * ((wn * NB + j) * RS + py) * HW + PS * px) * kCvRec + kh * 16;
@@ -225,7 +250,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
   const unsigned char *wa[MB];
 #pragma unroll
   for (int i = 0; i < MB; ++i) {
-    cb[i] = V == kCvGen ? blockIdx.y * (WM * MB) + i * WM + wm : (blockIdx.y * WM + wm) * MB + i;
+    cb[i] = V == kCvVggFwd || V == kCvVggBwd ? (blockIdx.y * WM + wm) * MB + i : blockIdx.y * (WM * MB) + i * WM + wm;
     mv[i] = cb[i] * 32 < MP;
     wa[i] = wp + (int64_t)(mv[i] ? cb[i] * 32 + l31 : 0) * kCvRec + kh * 16;
   }
@@ -239,11 +264,15 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
     const unsigned char *Bs = cv_smem + (ch & 1) * bufB;
 #pragma unroll
     for (int tap = 0; tap < TAPS; ++tap) {
-      constexpr int KW = G == 1 ? 4 : 3;
+      constexpr int KW = G == 1 || G == kCvU2K4 ? 4 : 3;
       const int ky = tap / KW, kx = tap % KW;
-      // T2K3: the phase a tap feeds and the neighbour it reads; the others: one phase, the tap's own offset
-      const int ph = G == 2 ? 2 * (ky != 1) + (kx != 1) : 0;
-      const int toff = (G == 2 ? (ky == 0) * HW + (kx == 0) : ky * HW + kx) * kCvRec;
+      // T2K3: the phase a tap feeds and the neighbour it reads; U2K4: odd taps feed the even phase (ky 1: the pixel itself,
+      // ky 3: the one before), even taps the odd phase (ky 0: the one after, ky 2: itself), the halo starting one pixel
+      // before the tile; the others: one phase, the tap's own offset
+      const int ph = G == 2 ? 2 * (ky != 1) + (kx != 1) : G == kCvU2K4 ? 2 * !(ky & 1) + !(kx & 1) : 0;
+      const int toff = (G == 2         ? (ky == 0) * HW + (kx == 0)
+                        : G == kCvU2K4 ? (1 + (ky == 0) - (ky == 3)) * HW + 1 + (kx == 0) - (kx == 3)
+                                       : ky * HW + kx) * kCvRec;
       uint4 bf[NB];
 #pragma unroll
       for (int j = 0; j < NB; ++j) bf[j] = *reinterpret_cast<const uint4 *>(Bs + boff[j] + toff);
@@ -262,7 +291,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
 
   // C/D layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   T *ob = y + (int64_t)blockIdx.z * Cout * oplane;
-  const T *ab = V == kCvGen && aux ? aux + (int64_t)blockIdx.z * Cout * oplane : nullptr;
+  const T *ab = (V == kCvGen || V == kCvGrad) && aux ? aux + (int64_t)blockIdx.z * Cout * oplane : nullptr;
 #pragma unroll
   for (int i = 0; i < MB; ++i) {
     if (!mv[i]) continue;
@@ -271,6 +300,8 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
       const int gy = y0 + (wn * NB + j) * RS + py, gx = x0 + px;             // pixel of the tiled map
       if constexpr (G == 2) {
         if (gy >= H || gx >= W) continue;
+      } else if constexpr (G == kCvU2K4) {
+        if (2 * gy >= Hout || 2 * gx >= Wout) continue;
       } else {
         if (gy >= Hout || gx >= Wout) continue;
       }
@@ -296,13 +327,28 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
             o.v[1] = (T)v1;
             *reinterpret_cast<Pack<T, 2> *>(ob + at) = o;
           }
+        } else if constexpr (G == kCvU2K4) {         // odd H or W: the last row / column of the odd phases does not exist
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            const int oy = 2 * gy + (p >> 1), ox = 2 * gx + (p & 1);
+            if (oy >= Hout || ox >= Wout) continue;
+            const int64_t at = (int64_t)co * oplane + (int64_t)oy * Wout + ox;
+            float v = acc[i][j * PH + p][r];
+            if (ab && pre_act && !(Num<T>::ld(ab + at) > 0.f)) v *= slope;
+            ob[at] = (T)v;
+          }
         } else {
           const int64_t at = (int64_t)co * oplane + (int64_t)gy * Wout + gx;
           float v = acc[i][j][r];
-          if constexpr (V != kCvVggBwd) v += b;
+          if constexpr (V == kCvGen || V == kCvVggFwd) v += b;
           if constexpr (V == kCvVggFwd) v = fmaxf(v, 0.f);
-          if (ab) v += Num<T>::ld(ab + at);
-          ob[at] = (T)v;
+          if constexpr (V == kCvGrad) {              // act'(x) of the element this lane writes: x > 0 ? 1 : slope
+            if (ab && pre_act && !(Num<T>::ld(ab + at) > 0.f)) v *= slope;
+          } else {
+            if (ab) v += Num<T>::ld(ab + at);
+          }
+          if constexpr (V == kCvGradPad) reinterpret_cast<float *>(y)[(int64_t)blockIdx.z * Cout * oplane + at] = v;
+          else ob[at] = (T)v;
         }
       }
     }
@@ -354,6 +400,8 @@ static int cv_pack(const void *w, int src_type, void *packed, int64_t M, int64_t
 }
 
 // everything that can be wrong with a shape, for the launch and for the host-only geometry query alike
+static int cv_check_tile(int geometry, int64_t Cout, const CvTile &g, CvTile *tile, int64_t *cblocks);
+
 static int cv_check(int geometry, int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int pad_mode, CvTile *tile,
                     int64_t *cblocks) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || geometry < 0 || geometry > 2 || pad_mode < 0 || pad_mode > 1)
@@ -362,7 +410,11 @@ static int cv_check(int geometry, int64_t B, int64_t Cin, int64_t Cout, int64_t 
   if (geometry == 1 && (H < 2 || W < 2)) return GFLA_ERR_BAD_SHAPE;
   if (H > 0x7fffffffLL || W > 0x7fffffffLL || H * W > 0x7fffffffLL || B > 65535 || Cin > kCvMaxC || Cout > kCvMaxC)
     return GFLA_ERR_UNSUPPORTED;
-  const CvTile g = cv_tile(geometry, Cout, H, W);
+  return cv_check_tile(geometry, Cout, cv_tile(geometry, Cout, H, W), tile, cblocks);
+}
+
+// the limits of a launch with tile g (Hout and Wout filled in)
+static int cv_check_tile(int geometry, int64_t Cout, const CvTile &g, CvTile *tile, int64_t *cblocks) {
   if (g.Hout * g.Wout > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
   const int64_t tiles = (int64_t)g.tilesX * g.tilesY;
   *cblocks = ceil_div(ceil_div(Cout, 32), g.WM * kCvMB);

@@ -1,6 +1,6 @@
 // The convolutions of the generators' bodies (base_function.py:334-391 EncoderBlock / ResBlock, 508-531 ResBlockDecoder,
-// 672-691 Jump), forward only, frozen weights: the entry points of the three geometries of conv_igemm.h in its generator
-// variant.
+// 672-691 Jump), forward: the entry points of the three geometries of conv_igemm.h in its generator variant.  The
+// gradients are in gen_conv_bwd.hip (data) and gen_conv_wgrad.hip (weight, bias).
 //
 //   y = bias + conv(act(x), w) (+ add),   act = identity | LeakyReLU(pre_slope), rounded to T once while it is staged
 //

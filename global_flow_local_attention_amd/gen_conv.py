@@ -1,4 +1,5 @@
-"""The convolutions of the generators' bodies on the library's own kernels, for inference (csrc/gen_conv.hip).
+"""The convolutions of the generators' bodies on the library's own kernels (csrc/gen_conv.hip; the gradients:
+csrc/gen_conv_bwd.hip, csrc/gen_conv_wgrad.hip).
 
 Every EncoderBlock, ResBlock, ResBlockDecoder and Jump of the reference (base_function.py:334-391, 508-531, 672-691) is
 built from three convolutions: Conv2d(k 3, s 1) with zero or reflection padding, Conv2d(k 4, s 2, p 1) and
@@ -7,19 +8,23 @@ each is one launch on the matrix cores, with the activation applied while the in
 the epilogue:
 
     conv3x3, conv4x4_down, conv_transpose3x3_up     functional forms
+    GenConvFunction                                 the autograd Function on the kernels (grad="kernels")
     InferenceConv                                   module with the replaced convolution's Parameters and names
     fuse_inference_convs                            rewrite the convolutions of a network in place
     patch_reference_convs                           the reference's block classes, rewritten as they are built
 
-The kernels are forward kernels for frozen weights.  Whenever a gradient could be asked for -- grad mode is on and x, the
-weight, the bias or the addend requires one -- and for CPU tensors, float64 and impl="torch", the calls take the exact
-torch composition (F.leaky_relu -> F.pad(reflect) -> F.conv2d / F.conv_transpose2d -> + add): training is untouched.
+Whenever a gradient could be asked for -- grad mode is on and x, the weight, the bias or the addend requires one -- the
+keyword `grad` decides: "torch" (the default everywhere) takes the exact torch composition (F.leaky_relu -> F.pad(reflect)
+-> F.conv2d / F.conv_transpose2d -> + add), so training is untouched; "kernels" runs GenConvFunction, whose backward is
+the library's data, weight and bias gradient kernels.  CPU tensors, float64 and impl="torch" always take the composition.
 """
 import ctypes
 
 import torch
 import torch.nn.functional as F
 from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._conv_common import SFX as _SFX, SRC_TYPE as _SRC_TYPE, autocast_dtype, cached, rounded_bias
@@ -27,6 +32,7 @@ from .head_conv import MAX_COUT as _HEAD_MAX_COUT
 
 IMPLS = _lib.IMPLS
 PADDINGS = ("zeros", "reflect")
+GRADS = ("torch", "kernels")
 S1K3, S2K4, T2K3 = 0, 1, 2
 _KERNEL_SIZE = {S1K3: 3, S2K4: 4, T2K3: 3}
 _NAMES = {S1K3: "conv3x3", S2K4: "conv4x4_down", T2K3: "conv_transpose3x3_up"}
@@ -53,6 +59,26 @@ def packed_weights(weight, dtype, geometry):
                   cin, geometry)
         return packed
     return cached(weight, "gen_conv%d" % geometry, dtype, make)
+
+
+def packed_grad_weights(weight, dtype, geometry):
+    """torch's `weight` packed for the data gradient (the adjoint geometry) in compute type `dtype`; cached on the
+    parameter's version, so a stepped optimizer repacks"""
+    def make():
+        w = weight.detach().contiguous()
+        cout, cin = (w.size(1), w.size(0)) if geometry == T2K3 else (w.size(0), w.size(1))
+        esize = torch.empty((), dtype=dtype).element_size()
+        packed = _lib.workspace("gfla_gen_conv_grad_packed_bytes", w, cout, cin, geometry, esize,
+                                what="gen_conv packed gradient weights")
+        _lib.call("gfla_gen_conv_pack_grad_weights_" + _SFX[dtype], w, _lib.ptr(w), _SRC_TYPE[w.dtype], _lib.ptr(packed),
+                  cout, cin, geometry)
+        return packed
+    return cached(weight, "gen_conv_grad%d" % geometry, dtype, make)
+
+
+def _check_grad(grad):
+    if grad not in GRADS:
+        raise ValueError("grad: one of %s (got %r)" % (GRADS, grad))
 
 
 def _validate(x, weight, bias, geometry, padding, pre_slope, add):
@@ -133,18 +159,90 @@ def _launch(x, weight, bias, geometry, padding, pre_slope, add, cout, ho, wo):
     return y
 
 
-def _gen_conv(x, weight, bias, geometry, padding, pre_slope, add, impl):
+class GenConvFunction(Function):
+    """(x, weight, bias | None, add | None, geometry, padding, pre_slope, (Cout, Hout, Wout)) -> y on the library's kernels,
+    with the gradients of all four tensors.
+
+    x: float32 / float16 / bfloat16 on the GPU (under torch.autocast the caller casts it first, so a float32 x gets a
+    float32 gradient through the cast).  Saved for the backward: x and the weight, nothing else -- act(x) is recomputed
+    while the gradient kernels stage it.  The backward launches only what needs_input_grad asks for: the data gradient
+    (x's dtype), the weight and bias gradients (float32 sums, rounded once to the parameter's dtype); the addend's
+    gradient is grad_y in the addend's dtype.  No atomics anywhere: bit-identical from call to call.
+    The decision is made here, in the forward: whatever the backward would need that the library refuses raises
+    _lib.Unsupported before anything is launched, and the caller takes the torch composition for the whole call."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, add, geometry, padding, pre_slope, dims):
+        cout, ho, wo = dims
+        need_x, need_w, need_b, need_add = ctx.needs_input_grad[:4]
+        need_b = need_b and bias is not None
+        B, Cin, H, W = x.shape
+        if need_x or need_w or need_b:
+            esize = x.element_size()
+            _lib.workspace_bytes("gfla_gen_conv_bwd_workspace_bytes", B, Cin, cout, H, W, geometry, PADDINGS.index(padding),
+                                 esize, what="gen_conv backward")
+            _lib.workspace_bytes("gfla_gen_conv_grad_packed_bytes", cout, Cin, geometry, esize, what="gen_conv backward")
+        y = _launch(x, weight, bias, geometry, padding, pre_slope, add, cout, ho, wo)
+        ctx.conf = (cout, geometry, PADDINGS.index(padding), int(pre_slope is not None), float(pre_slope or 0.0))
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.add_dtype = None if add is None else add.dtype
+        if need_x or need_w or need_b:
+            ctx.save_for_backward(x.contiguous(), weight)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        need_x, need_w, need_b, need_add = ctx.needs_input_grad[:4]
+        need_b = need_b and ctx.bias_dtype is not None
+        need_add = need_add and ctx.add_dtype is not None
+        g_add = g.to(ctx.add_dtype) if need_add else None
+        dx = dw = db = None
+        if need_x or need_w or need_b:
+            x, weight = ctx.saved_tensors
+            cout, geometry, pad_mode, pre_act, slope = ctx.conf
+            B, Cin, H, W = x.shape
+            sfx = _SFX[x.dtype]
+            gy = g.to(x.dtype).contiguous()
+            ws = _lib.workspace("gfla_gen_conv_bwd_workspace_bytes", x, B, Cin, cout, H, W, geometry, pad_mode,
+                                x.element_size(), what="gen_conv backward")
+            tail = (B, Cin, cout, H, W, geometry, pad_mode, pre_act, slope)
+            if need_x:
+                dx = torch.empty_like(x)
+                wp = packed_grad_weights(weight, x.dtype, geometry)
+                _lib.call("gfla_gen_conv_bwd_data_" + sfx, x, _lib.ptr(gy), _lib.ptr(x), _lib.ptr(wp), _lib.ptr(dx),
+                          _lib.ptr(ws), *tail)
+            if need_w or need_b:
+                dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device) if need_w else None
+                db = torch.empty(cout, dtype=torch.float32, device=x.device) if need_b else None
+                _lib.call("gfla_gen_conv_bwd_weight_" + sfx, x, _lib.ptr(gy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(db),
+                          _lib.ptr(ws), *tail)
+                if dw is not None and dw.dtype != weight.dtype:
+                    dw = dw.to(weight.dtype)
+                if db is not None and db.dtype != ctx.bias_dtype:
+                    db = db.to(ctx.bias_dtype)
+        return dx, dw, db, g_add, None, None, None, None
+
+
+def _gen_conv(x, weight, bias, geometry, padding, pre_slope, add, impl, grad="torch"):
     _lib.check_impl(impl)
+    _check_grad(grad)
     cout, ho, wo = _validate(x, weight, bias, geometry, padding, pre_slope, add)
-    if impl == "auto" and _kernel_inputs(x, weight, bias, add) and not _needs_grad(x, weight, bias, add):
+    if impl == "auto" and _kernel_inputs(x, weight, bias, add):
+        needs = _needs_grad(x, weight, bias, add)
         try:
-            return _launch(x.detach(), weight, bias, geometry, padding, pre_slope, add, cout, ho, wo)
+            if not needs:
+                return _launch(x.detach(), weight, bias, geometry, padding, pre_slope, add, cout, ho, wo)
+            if grad == "kernels":
+                xk = x.to(autocast_dtype()) if torch.is_autocast_enabled() else x
+                if xk.dtype in _SFX:
+                    return GenConvFunction.apply(xk, weight, bias, add, geometry, padding, pre_slope, (cout, ho, wo))
         except _lib.Unsupported:
             pass
     return torch_gen_conv(x, weight, bias, geometry, padding, pre_slope, add)
 
 
-def conv3x3(x, weight, bias=None, padding="zeros", pre_slope=None, add=None, impl="auto"):
+def conv3x3(x, weight, bias=None, padding="zeros", pre_slope=None, add=None, impl="auto", grad="torch"):
     """conv2d(pad(leaky_relu(x, pre_slope)), weight (Cout,Cin,3,3)) + bias (+ add), stride 1, one pixel of padding "zeros"
     | "reflect" (reflect needs H, W >= 2), output H x W.  pre_slope None: no pre-activation.  add: a tensor of the output's
     shape, added in float32 before the one rounding of a 16-bit result.
@@ -152,35 +250,40 @@ def conv3x3(x, weight, bias=None, padding="zeros", pre_slope=None, add=None, imp
     off, or none of x, weight, bias, add requires one); parameters stored in another float type are packed into x's
     dtype; under torch.autocast x is cast to the autocast dtype.  Everything else -- CPU tensors, float64, a gradient
     needed, shapes the library refuses (_lib.Unsupported) -- takes the torch composition (torch_gen_conv), as "torch"
-    always does."""
-    return _gen_conv(x, weight, bias, S1K3, padding, pre_slope, add, impl)
+    always does.
+    grad "torch" (default): as above.  "kernels": a GPU call in float32 / float16 / bfloat16 that needs a gradient runs
+    GenConvFunction -- the same forward launch, and the library's data / weight / bias gradient kernels behind it; if the
+    library refuses any part of that, the whole call takes the composition.  Anything else raises ValueError."""
+    return _gen_conv(x, weight, bias, S1K3, padding, pre_slope, add, impl, grad)
 
 
-def conv4x4_down(x, weight, bias=None, pre_slope=None, impl="auto"):
+def conv4x4_down(x, weight, bias=None, pre_slope=None, impl="auto", grad="torch"):
     """conv2d(leaky_relu(x, pre_slope), weight (Cout,Cin,4,4), bias, stride=2, padding=1): H, W >= 2, odd sizes as torch
     (output (H-2)//2+1 x (W-2)//2+1).  Dispatch as conv3x3."""
-    return _gen_conv(x, weight, bias, S2K4, "zeros", pre_slope, None, impl)
+    return _gen_conv(x, weight, bias, S2K4, "zeros", pre_slope, None, impl, grad)
 
 
-def conv_transpose3x3_up(x, weight, bias=None, add=None, impl="auto", pre_slope=None):
+def conv_transpose3x3_up(x, weight, bias=None, add=None, impl="auto", pre_slope=None, grad="torch"):
     """conv_transpose2d(leaky_relu(x, pre_slope), weight (Cin,Cout,3,3), bias, stride=2, padding=1, output_padding=1)
     (+ add): output 2H x 2W, computed as four output phases of 1 / 2 / 2 / 4 taps, never on a zero-stuffed map.  Dispatch
     as conv3x3."""
-    return _gen_conv(x, weight, bias, T2K3, "zeros", pre_slope, add, impl)
+    return _gen_conv(x, weight, bias, T2K3, "zeros", pre_slope, add, impl, grad)
 
 
 class InferenceConv(nn.Module):
     """[LeakyReLU(pre_slope)] -> [ReflectionPad2d(1)] -> the convolution `conv` (+ add) as one op.  `weight` and `bias` are
     conv's own Parameter objects under conv's names, so state dicts interchange; conv itself is kept (unregistered) and
-    runs whenever the kernels do not: CPU, float64, a gradient needed, impl="torch"."""
+    runs whenever the kernels do not: CPU, float64, a gradient needed (unless grad="kernels": then GenConvFunction),
+    impl="torch"."""
 
-    def __init__(self, conv, geometry, padding="zeros", pre_slope=None, impl="auto"):
+    def __init__(self, conv, geometry, padding="zeros", pre_slope=None, impl="auto", grad="torch"):
         super(InferenceConv, self).__init__()
         _lib.check_impl(impl)
+        _check_grad(grad)
         if geometry not in _NAMES or padding not in PADDINGS or (padding == "reflect" and geometry != S1K3):
             raise ValueError("InferenceConv: geometry 0 / 1 / 2, padding 'zeros' or (geometry 0) 'reflect' (got %r, %r)"
                              % (geometry, padding))
-        self.geometry, self.padding, self.impl = geometry, padding, impl
+        self.geometry, self.padding, self.impl, self.grad = geometry, padding, impl, grad
         self.pre_slope = None if pre_slope is None else float(pre_slope)
         self.weight = conv.weight
         if conv.bias is not None:
@@ -191,9 +294,19 @@ class InferenceConv(nn.Module):
         self.train(conv.training)
 
     def forward(self, x, add=None):
-        if self.impl == "auto" and _kernel_inputs(x, self.weight, self.bias, add) and \
-                not _needs_grad(x, self.weight, self.bias, add):
-            return _gen_conv(x, self.weight, self.bias, self.geometry, self.padding, self.pre_slope, add, self.impl)
+        if self.impl == "auto" and _kernel_inputs(x, self.weight, self.bias, add):
+            needs = _needs_grad(x, self.weight, self.bias, add)
+            if not needs:
+                return _gen_conv(x, self.weight, self.bias, self.geometry, self.padding, self.pre_slope, add, self.impl)
+            if self.grad == "kernels":
+                xk = x.to(autocast_dtype()) if torch.is_autocast_enabled() else x
+                if xk.dtype in _SFX:
+                    try:
+                        dims = _validate(x, self.weight, self.bias, self.geometry, self.padding, self.pre_slope, add)
+                        return GenConvFunction.apply(xk, self.weight, self.bias, add, self.geometry, self.padding,
+                                                     self.pre_slope, dims)
+                    except _lib.Unsupported:
+                        pass
         a = x if self.pre_slope is None else F.leaky_relu(x, self.pre_slope)
         if self.padding == "reflect":
             a = F.pad(a, (1, 1, 1, 1), mode="reflect")
@@ -204,9 +317,9 @@ class InferenceConv(nn.Module):
         return y if add is None else y + add
 
     def extra_repr(self):
-        return "%s, %d -> %d, padding=%r, pre_slope=%s, impl=%r" % (
+        return "%s, %d -> %d, padding=%r, pre_slope=%s, impl=%r, grad=%r" % (
             _NAMES[self.geometry], self.original.in_channels, self.original.out_channels, self.padding, self.pre_slope,
-            self.impl)
+            self.impl, self.grad)
 
 
 def _is_reflect_pad(module):
@@ -241,7 +354,7 @@ def _geometry_of(module, has_pad):
     return None
 
 
-def fuse_inference_convs(net, impl="auto"):
+def fuse_inference_convs(net, impl="auto", grad="torch"):
     """Rewrite, in place and recursively, the convolutions of `net` that sit in an nn.Sequential and that the kernels have:
     plain nn.Conv2d (k 3, s 1, p 1, zeros), (k 3, s 1, p 0) directly behind nn.ReflectionPad2d(1), (k 4, s 2, p 1, zeros)
     and plain nn.ConvTranspose2d (k 3, s 2, p 1, output_padding 1).  The convolution's slot becomes an InferenceConv
@@ -251,8 +364,10 @@ def fuse_inference_convs(net, impl="auto"):
     reference's Jump keeps its own as `conv1` and `model.N`) is replaced there by the same InferenceConv.
     Left alone, uncounted: modules with any hook (spectral norm), CoordConv, groups / dilation other than 1, other padding
     modes, 1x1 convolutions, anything inside an ExtractorAttn (`fully_connect_layer`), 3x3 convolutions of at most 8 output
-    channels (head_conv.py's: HeadConv3x3 slots and the flow / mask heads).  Returns the number of convolutions rewritten."""
+    channels (head_conv.py's: HeadConv3x3 slots and the flow / mask heads).  grad: the `grad` of every InferenceConv made
+    ("kernels": training runs on GenConvFunction).  Returns the number of convolutions rewritten."""
     _lib.check_impl(impl)
+    _check_grad(grad)
     inside_attn = set()
     for m in net.modules():
         if hasattr(m, "fully_connect_layer"):
@@ -272,7 +387,7 @@ def fuse_inference_convs(net, impl="auto"):
             at = i - 1 if has_pad else i
             before = seq._modules[names[at - 1]] if at >= 1 else None
             slope = float(before.negative_slope) if type(before) is nn.LeakyReLU else None
-            fused = InferenceConv(conv, geometry, padding, slope, impl)
+            fused = InferenceConv(conv, geometry, padding, slope, impl, grad)
             seq._modules[name] = fused
             if has_pad:
                 seq._modules[names[i - 1]] = nn.Identity()
@@ -304,12 +419,14 @@ def _run_with_add(seq, x, add):
 _REFERENCE_CONV_BLOCKS = ("EncoderBlock", "ResBlock", "ResBlockDecoder", "Jump")
 
 
-def patch_reference_convs(base_function, impl="auto"):
+def patch_reference_convs(base_function, impl="auto", grad="torch"):
     """Wrap the constructors of the reference's EncoderBlock, ResBlock, ResBlockDecoder and Jump so that every block built
     from now on comes out rewritten (fuse_inference_convs on the finished block), and replace ResBlock.forward and
     ResBlockDecoder.forward by versions that hand the residual (x, or shortcut(x)) as `add` to the last InferenceConv of
-    `self.model`; whenever that slot is no InferenceConv they call the original forward.  Idempotent.  Returns the names
-    of the classes wrapped."""
+    `self.model`; whenever that slot is no InferenceConv they call the original forward.  With grad="kernels" the blocks
+    train on GenConvFunction and the residual's gradient flows through its `add`.  Idempotent.  Returns the names of the
+    classes wrapped."""
+    _check_grad(grad)
     wrapped = []
     for name in _REFERENCE_CONV_BLOCKS:
         cls = getattr(base_function, name, None)
@@ -323,7 +440,7 @@ def patch_reference_convs(base_function, impl="auto"):
         def make(orig):
             def __init__(self, *args, **kwargs):
                 orig(self, *args, **kwargs)
-                fuse_inference_convs(self, impl)
+                fuse_inference_convs(self, impl, grad)
             __init__._gfla_fuses_inference_convs = True
             __init__.__wrapped__ = orig
             __init__.__doc__ = orig.__doc__

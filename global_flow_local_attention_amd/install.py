@@ -44,7 +44,7 @@ def _bind_vgg(cls, vgg):
 
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
             dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False, fuse_instance_norm=False,
-            fuse_heads=False, inference_convs=False):
+            fuse_heads=False, inference_convs=False, train_convs=False):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -91,7 +91,15 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     transposed 3x3 convolutions as InferenceConv (gen_conv.py: csrc/gen_conv.hip under eval() / torch.no_grad(), the torch
     composition whenever a gradient could be asked for), and replaces ResBlock.forward / ResBlockDecoder.forward by versions
     that add the residual in the last convolution's epilogue.  Indices, state-dict keys and the Parameter objects are
-    unchanged.  Composes with fuse_instance_norm and fuse_heads.  False (the default) changes nothing."""
+    unchanged.  Composes with fuse_instance_norm and fuse_heads.  False (the default) changes nothing.
+
+    train_convs: with inference_convs, True makes those InferenceConv run the library's own gradient kernels as well
+    (gen_conv.GenConvFunction, grad="kernels": csrc/gen_conv_bwd.hip and csrc/gen_conv_wgrad.hip) whenever a gradient is
+    needed on a GPU map of float32 / float16 / bfloat16, so a training step of the generators' bodies calls no vendor
+    convolution.  False (the default) keeps the torch composition for training.  Without inference_convs it raises
+    ValueError."""
+    if train_convs and not inference_convs:
+        raise ValueError("install: train_convs=True needs inference_convs")
     from . import extractor_attn as _ea
     if strict_mfma is None and allow_vendor_fallback is not None:
         strict_mfma = not allow_vendor_fallback
@@ -148,7 +156,8 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
         patch_reference_flow_heads(importlib.import_module("model.networks.generator"), impl)
     if base_function is not None and inference_convs:
         from .gen_conv import patch_reference_convs
-        patch_reference_convs(base_function, inference_convs if isinstance(inference_convs, str) else "auto")
+        patch_reference_convs(base_function, inference_convs if isinstance(inference_convs, str) else "auto",
+                              "kernels" if train_convs else "torch")
     if vgg is not None:
         from . import losses
         external_function = importlib.import_module("model.networks.external_function")

@@ -3,7 +3,7 @@
  *
  * ---- generator inference convolutions (base_function.py:334-391 EncoderBlock / ResBlock, 508-531 ResBlockDecoder, 672-691
  * Jump; csrc/gen_conv.hip) -------------------------------------------------------------------------------------------------
- * Forward only, frozen weights.  x (B,Cin,H,W) contiguous in its storage type T (float32 / float16 / bfloat16), read as
+ * Forward (frozen or trainable weights) and, further down, the gradients.  x (B,Cin,H,W) contiguous in its storage type T (float32 / float16 / bfloat16), read as
  * stored; sums are float32 on the matrix cores, a 16-bit result is rounded to nearest even once.  groups 1, dilation 1.
  *   a = pre_act ? leaky_relu(x, pre_slope) rounded to T : x
  *   y = bias + conv(a, w) (+ add)
@@ -25,7 +25,27 @@
  * No atomics: bit-identical from call to call.  NULL x / packed / y (w, out, Hout, Wout) -> -1; non-positive sizes,
  * geometry, pad_mode, src_type or elem_size out of range, pad_mode 1 with another geometry than 0 or with H or W < 2,
  * geometry 1 with H or W < 2 -> -2; a plane of x or y beyond 2^31 - 1, B > 65535 or more than 65536 channels ->
- * GFLA_ERR_UNSUPPORTED, nothing is launched.  Additive: GFLA_ABI_VERSION stays 8. */
+ * GFLA_ERR_UNSUPPORTED, nothing is launched.  Additive: GFLA_ABI_VERSION stays 8.
+ *
+ * ---- gradients (csrc/gen_conv_bwd.hip, csrc/gen_conv_wgrad.hip) -------------------------------------------------------
+ * `geometry`, `pad_mode`, `pre_act`, `pre_slope`, B, Cin, Cout, H, W are the forward's everywhere; grad_y has y's shape
+ * and type, x is the forward's input as stored (nothing else is saved: a is recomputed from it).
+ *   grad_x = act'(x) adj(grad_y, w),  act'(x) = x > 0 ? 1 : pre_slope (1 without pre_act); x's shape and type, rounded once
+ *   grad_w[co][ci][tap] = sum over (b, pixel) of grad_y a, float32 in torch's layout ((Cout,Cin,k,k); geometry 2:
+ *                         (Cin,Cout,3,3));  grad_b[co] = sum of grad_y, float32
+ * `packed_grad`: gfla_gen_conv_grad_packed_bytes(Cout, Cin, geometry, sizeof(T)) bytes, 16-byte aligned, written by
+ *           gfla_gen_conv_pack_grad_weights_<T> from torch's weight as stored: the packing of the adjoint geometry
+ *           [tap][chunk of 32 / sizeof(T) OUTPUT channels][Cin padded to 32][chunk]; geometry 0: taps mirrored (9),
+ *           geometry 1: the 16 taps as stored (four phases of 2 x 2 over the half-resolution grid), geometry 2: the 9 taps
+ *           as stored (a Conv2d(k 3, s 2, p 1) of grad_y).
+ * `workspace`: gfla_gen_conv_bwd_workspace_bytes(B, Cin, Cout, H, W, geometry, pad_mode, sizeof(T)) bytes, uninitialised,
+ *           16-byte aligned; enough for either call.  bwd_data reads it only with pad_mode 1 (the gradient on the padded
+ *           domain, float32, folded onto x by a second launch; NULL is accepted otherwise); bwd_weight holds the float32
+ *           partial sums of the split reduction in it, summed in a fixed order by a second launch.
+ * gfla_gen_conv_bwd_weight: grad_w or grad_b may be NULL (not computed); both NULL -> -1; x and workspace may be NULL
+ *           when grad_w is.
+ * No atomics: bit-identical from call to call.  Status codes as above: NULL -> -1, the forward's bad shapes -> -2, the
+ * forward's limits or B x (pixels of the reduction) beyond 2^31 - 1 -> GFLA_ERR_UNSUPPORTED, nothing is launched. */
 #ifndef GFLA_GEN_CONV_H_
 #define GFLA_GEN_CONV_H_
 
@@ -38,9 +58,25 @@ int gfla_gen_conv_geometry(int geometry, int64_t Cout, int64_t H, int64_t W, int
   int gfla_gen_conv_fwd_##SFX(const T *x, const void *packed, const float *bias, const T *add, T *y, int64_t B,          \
                               int64_t Cin, int64_t Cout, int64_t H, int64_t W, int geometry, int pad_mode, int pre_act,  \
                               double pre_slope, gfla_stream_t stream);
+int64_t gfla_gen_conv_grad_packed_bytes(int64_t Cout, int64_t Cin, int geometry, int elem_size);
+int64_t gfla_gen_conv_bwd_workspace_bytes(int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int geometry,
+                                          int pad_mode, int elem_size);
+#define GFLA_DECL_GEN_CONV_BWD(SFX, T)                                                                                   \
+  int gfla_gen_conv_pack_grad_weights_##SFX(const void *w, int src_type, void *packed, int64_t Cout, int64_t Cin,        \
+                                            int geometry, gfla_stream_t stream);                                         \
+  int gfla_gen_conv_bwd_data_##SFX(const T *grad_y, const T *x, const void *packed_grad, T *grad_x, void *workspace,     \
+                                   int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int geometry,             \
+                                   int pad_mode, int pre_act, double pre_slope, gfla_stream_t stream);                   \
+  int gfla_gen_conv_bwd_weight_##SFX(const T *grad_y, const T *x, float *grad_w, float *grad_b, void *workspace,         \
+                                     int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int geometry,           \
+                                     int pad_mode, int pre_act, double pre_slope, gfla_stream_t stream);
 GFLA_DECL_GEN_CONV(f32, float)
 GFLA_DECL_GEN_CONV(f16, uint16_t)
 GFLA_DECL_GEN_CONV(bf16, uint16_t)
 #undef GFLA_DECL_GEN_CONV
+GFLA_DECL_GEN_CONV_BWD(f32, float)
+GFLA_DECL_GEN_CONV_BWD(f16, uint16_t)
+GFLA_DECL_GEN_CONV_BWD(bf16, uint16_t)
+#undef GFLA_DECL_GEN_CONV_BWD
 
 #endif /* GFLA_GEN_CONV_H_ */
