@@ -24,7 +24,7 @@ enum FcWgrad {
   kWgradDirect32,  // fc_wgrad_f32 partials, reduced by fc_wgrad_reduce
   kWgradDirect16,  // fc_wgrad on the f16-split records into dw_s / dw_t, unscaled by fc_unpack_wgrad
   kWgradWino32,    // Winograd domain, float32 operands; reduced (and transformed back) by fc_wino_wgrad_reduce
-  kWgradWino16,    // the same with two-term f16 operands (fc_wino.hip: fc_wino16_wgrad_kernel)
+  kWgradWino16,    // the same with two-term f16 operands (fc_wino16.hip: fc_wino16_wgrad_kernel)
 };
 static bool fc_wgrad_wino(FcWgrad w) { return w == kWgradWino32 || w == kWgradWino16; }
 
@@ -217,11 +217,7 @@ static int fc_pack_weight_sets(const FcLayout &L, const float *w0, unsigned char
 static int fc_wino_jobs(const WnConvJob *jobs, int njobs, const uint32_t *const *amax, const uint32_t *amax_w, bool w16, int64_t B,
                         int nch, int k, hipStream_t stream) {
   if (!w16) return fc_wino_conv_jobs(jobs, njobs, B, nch, k, stream);
-  Wn16ConvJob j16[2];
-  for (int j = 0; j < njobs && j < 2; ++j)
-    j16[j] = Wn16ConvJob{jobs[j].X, reinterpret_cast<const uint32_t *>(jobs[j].U), amax[j], jobs[j].out, jobs[j].out_bs, jobs[j].ldo,
-                         jobs[j].n_valid, jobs[j].M, jobs[j].Wv, jobs[j].Wp, jobs[j].S};
-  return fc_wino16_conv_jobs(j16, njobs, B, nch, k, amax_w, stream);
+  return fc_wino16_conv_jobs(jobs, njobs, amax, B, nch, k, amax_w, stream);
 }
 
 // the forward convolution of the wanted halves (out_s / out_t; NULL: not wanted) on the packed records of the workspace:

@@ -189,14 +189,14 @@ int64_t fc_packed_bytes(int64_t B, int nch, int64_t S, int mode);
 int64_t fc_wpack_bytes(int ntiles, int nch, int k, int mode);
 int fc_tr_probe(const short *image, int n_halves, const int *offsets, short *out, hipStream_t stream);
 
-// fc_wino.hip (arithmetic mode 4)
+// fc_wino.hip (arithmetic mode 4: float32 operands; mode 5 runs its k = 3 weight gradient here)
 int64_t fc_wino_wpack_bytes(int n_in, int n_out);
 int fc_wino_pack_weights(const float *w0, float *u_ft, float *u_fs, float *u_dt, float *u_ds, int C, int k,
                          hipStream_t stream);
 bool fc_wino_fits(int M, int Wv, int Wp, int k);
 struct WnConvJob {   // one convolution of fc_wino_conv_jobs: the arguments of fc_wino_conv that may differ between the jobs
   PackedDesc X;
-  const float *U;
+  const float *U;   // fc_wino_pack_weights' floats, or fc_wino16_pack_weights' (hi, lo) words for fc_wino16_conv_jobs
   float *out;
   int64_t out_bs;
   int ldo, n_valid, M, Wv, Wp;
@@ -214,28 +214,20 @@ struct WwJob {   // one Winograd-domain weight gradient (fc_wino_wgrad's argumen
   int Ho, Wo, Wp;
 };
 int fc_wino_wgrad_jobs(const WwJob *jobs, int njobs, int cpad, int64_t B, int k, hipStream_t stream);
-int fc_wino16_wgrad_jobs(const WwJob *jobs, int njobs, int cpad, int64_t B, int k, const uint32_t *const *amax_x,
-                         const uint32_t *const *amax_z, hipStream_t stream);
 int fc_wino_wgrad(const PackedDesc &X, const float *Z, int64_t z_bs, int64_t z_lead, float *part, int cpad, int64_t B, int Ho,
                   int Wo, int Wp, int64_t SX, int k, hipStream_t stream);
 int fc_wino_wgrad_reduce(float *part, int nsplit, float *grad_w0, int C, int c_off, int cpad, int k, hipStream_t stream);
 int fc_wino_wgrad_reduce2(float *part_s, int nsplit_s, float *part_t, int nsplit_t, float *grad_w0, int C, int cpad, int k,
                           hipStream_t stream);
 
-// fc_wino16.hip (arithmetic mode 5)
-struct Wn16ConvJob {   // WnConvJob with the two-term f16 weights of fc_wino16_pack_weights and the max |x| slot of the input
-  PackedDesc X;
-  const uint32_t *U;
-  const uint32_t *amax_x;
-  float *out;
-  int64_t out_bs;
-  int ldo, n_valid, M, Wv, Wp;
-  int64_t S;
-};
+// fc_wino16.hip (arithmetic mode 5: two-term f16 operands -- the k = 3 forward convolutions, the k = 5 weight gradient);
+// amax_x[j] / amax_z[j]: the max |x| slots of job j's input and gradient map
 int fc_wino16_pack_weights(const float *w0, const uint32_t *amax_w, float *u_ft, float *u_fs, int C, int k, hipStream_t stream);
 bool fc_wino16_fits(int M, int Wv, int Wp, int k);
-int fc_wino16_conv_jobs(const Wn16ConvJob *jobs, int njobs, int64_t B, int nch, int k, const uint32_t *amax_w,
-                        hipStream_t stream);
+int fc_wino16_conv_jobs(const WnConvJob *jobs, int njobs, const uint32_t *const *amax_x, int64_t B, int nch, int k,
+                        const uint32_t *amax_w, hipStream_t stream);
+int fc_wino16_wgrad_jobs(const WwJob *jobs, int njobs, int cpad, int64_t B, int k, const uint32_t *const *amax_x,
+                         const uint32_t *const *amax_z, hipStream_t stream);
 
 // fc_sample.hip
 int fc_sample_tail_fwd(const float *gs, const float *gt, const float *flow, const float *b0, const float *w1,

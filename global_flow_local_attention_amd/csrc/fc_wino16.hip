@@ -1,6 +1,7 @@
 // Winograd-domain convolutions of ExtractorAttn's first FC layer with TWO-TERM f16 OPERANDS on the f16 matrix cores
-// (arithmetic mode 5), gfx950.  Mode 5 runs only the k = 3 forward here (csrc/fc_block.hip: fc_plan); the formulation below
-// covers both kernel sizes.
+// (arithmetic mode 5), gfx950, and the k = 5 weight gradient on the same operands (second half of the file).  Mode 5 runs
+// only the k = 3 forward on the convolution kernel (csrc/fc_block.hip: fc_plan); the formulation below covers both kernel
+// sizes.  The skeletons the kernels share with their float32 twins of fc_wino.hip are fc_wino_shared.h and fc_wino_wgrad.h.
 //
 // Same formulation, tiling and staging as fc_wino.hip (F(2x2,5x5) / F(4x4,3x3) on the points {0, 1, -1, 2, -1/2, inf}; reference
 // base_function.py:799-807): the transforms B^T d B and A^T M A stay float32 on the vector ALUs.  What changes is the 36
@@ -24,7 +25,7 @@
 //   point, a step ahead; the transform of the NEXT step (fc_wino.hip's, plus the split) runs in the other wave of the SIMD;
 //   epilogue: every wave reduces its nine points to an m x m partial per (tile, channel); the four waves of a channel block
 //   exchange partials through LDS, a quarter of the tiles each, and store 128-byte rows of the (pixel, channel) map.
-#include "fc_wino_shared.h"
+#include "fc_wino_wgrad.h"
 
 namespace gfla {
 
@@ -83,18 +84,6 @@ int fc_wino16_pack_weights(const float *w0, const uint32_t *amax_w, float *u_ft,
 }
 
 // ---- the convolution ---------------------------------------------------------------------------------------------
-struct Wn16KArgs {
-  PackedDesc X;
-  const uint32_t *U;
-  const uint32_t *amax_x;
-  float *out;
-  int64_t out_bs;
-  int ldo, n_valid, Ho, Wv, Wp;
-  WnGeo geo;
-  int ntn;
-  int64_t total_groups, S;
-};
-
 // A^T (m x 6) as a table (the epilogue folds it at compile time)
 template <int M>
 struct WnAT;
@@ -113,75 +102,33 @@ struct WnAT<4> {
 template <int PG_>
 struct PgTag { static constexpr int value = PG_; };
 
-// DBG (timing ablations; results are garbage -- no launcher instantiates them since k = 5 left this kernel): 1 no transform, 2 no MFMAs / A reads,
-// 4 no B reloads, 8 no raw staging, 32 transform without the f16 split (hi only), 64 no epilogue
-extern unsigned long long *g_wino_stamps;   // fc_wino.hip (DBG & 16: per-wave phase times, s_memtime; tools/probe_wino_phases.py)
+// DBG: no timing ablation of this kernel is left (k = 5 went to the direct kernels); the parameter keeps the kernel's symbol
 template <int KS, bool DB = true, int DBG = 0>
-__global__ __launch_bounds__(kWnThreads, 2) void fc_wino16_conv_kernel(Wn16KArgs a0, Wn16KArgs a1, unsigned n0, int nch,
-                                                                      const uint32_t *__restrict__ amax_w,
-                                                                      unsigned long long *stamps) {
-  unsigned long long tk0 = 0, t_first = 0, t_second = 0, t_bar = 0, t_pro = 0, t_epi = 0;
-  if constexpr (DBG & 16) tk0 = __builtin_amdgcn_s_memtime();
-  auto stamp = [&](unsigned long long &slot) {
-    if constexpr (DBG & 16) {
-      __builtin_amdgcn_s_waitcnt(0);
-      const unsigned long long n = __builtin_amdgcn_s_memtime();
-      slot += n - tk0;
-      tk0 = n;
-    }
-  };
+__global__ __launch_bounds__(kWnThreads, 2) void fc_wino16_conv_kernel(WnKArgs a0, WnKArgs a1, unsigned n0, int nch,
+                                                                      const uint32_t *__restrict__ amax_w) {
   constexpr int M = Wn<KS>::M, PITCH = Wn<KS>::PITCH, NP = 9;   // points per wave
   const bool second = blockIdx.x >= n0;
-#define GFLA_PICK(f) (second ? a1.f : a0.f)
-  PackedDesc X;
-  X.base = GFLA_PICK(X.base), X.split_stride = 0, X.batch_stride = GFLA_PICK(X.batch_stride);
-  X.chunk_stride = GFLA_PICK(X.chunk_stride), X.pix_stride = GFLA_PICK(X.pix_stride);
-  const uint32_t *__restrict__ U = GFLA_PICK(U);
-  const uint32_t *__restrict__ amax_x = GFLA_PICK(amax_x);
-  float *__restrict__ out = GFLA_PICK(out);
-  const int64_t out_bs = GFLA_PICK(out_bs), total_groups = GFLA_PICK(total_groups), S = GFLA_PICK(S);
-  const int ldo = GFLA_PICK(ldo), n_valid = GFLA_PICK(n_valid), Ho = GFLA_PICK(Ho), Wv = GFLA_PICK(Wv), Wp = GFLA_PICK(Wp);
-  const int ntn = GFLA_PICK(ntn);
-  WnGeo geo;
-  geo.TH = GFLA_PICK(geo.TH), geo.TW = GFLA_PICK(geo.TW), geo.ngroups = GFLA_PICK(geo.ngroups), geo.span = GFLA_PICK(geo.span);
-  geo.tpg = GFLA_PICK(geo.tpg);
-#undef GFLA_PICK
+  const WnKArgs a = wn_pick(second, a0, a1);
+  const uint32_t *__restrict__ U = reinterpret_cast<const uint32_t *>(a.U);
+  const uint32_t *__restrict__ amax_x = a.amax_x;
+  float *__restrict__ out = a.out;
   extern __shared__ __attribute__((aligned(16))) unsigned char gfla_smem[];
   uint32_t *vbuf = reinterpret_cast<uint32_t *>(gfla_smem);   // [2][36 points][2 quads][32 tiles][4 channels] (hi, lo) words
   unsigned char *raw = gfla_smem + 2 * kWnVFloats * 4;        // [1 or 2][span][PITCH] float32, scaled
-  const int raw_bytes = (geo.span * PITCH + 15) & ~15;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nblk = wave & 1, pg = (wave >> 1) & 3, xh = wave >> 2;
   const int g = lane >> 5, l31 = lane & 31;
   // scales: input (this job's tensor), weights; the epilogue multiplies by their inverses (two exact power-of-two factors)
   const int ex = wn16_scale_exp(*amax_x, kWn16HeadX), ew = wn16_scale_exp(*amax_w, kWn16HeadW);
   const float sx = wn16_pow2(ex), inv_x = wn16_pow2(254 - ex), inv_w = wn16_pow2(254 - ew);
-  // workgroup -> (group of tiles, output-channel tile): ids x and x + 8 run on the same XCD (fc_wino.hip)
-  const int64_t x = blockIdx.x - (second ? n0 : 0u);
-  const int xcd = (int)(x & 7);
-  const int64_t slot = x >> 3;
-  const int ntile = (int)(slot % ntn);
-  const int64_t glin = (slot / ntn) * 8 + xcd;
-  if (glin >= total_groups) return;
-  const int64_t b = glin / geo.ngroups;
-  const int grp = (int)(glin - b * geo.ngroups);
-  const int ntiles = geo.TH * geo.TW;
-  const int tile0 = grp * geo.tpg;
-  const int ty_first = tile0 / geo.TW;
-  const int p0 = M * ty_first * Wp;
-  const int64_t avail = S - p0;
+  WnGroup<KS> grp;
+  if (!grp.claim(a, blockIdx.x - (second ? n0 : 0u))) return;
+  grp.decode(a);
 
   // transform item of this thread: (tile, channel of the 8-channel step), rows 3*xh .. 3*xh + 2 of the point grid
   const int tl = (t & 255) >> 3, c8 = t & 7;
-  int toff;
-  {
-    const int tau = min(tile0 + min(tl, geo.tpg - 1), ntiles - 1);   // (slots behind the group's tiles repeat its last one)
-    const int ty = tau / geo.TW, tx = tau - ty * geo.TW;
-    toff = ((M * ty * Wp + M * tx) - p0) * PITCH + c8 * 4;
-  }
+  const int toff = grp.toff(a, tl, c8);
   // word offset of V[first point of this half][quad c8 >> 2][tile][c8 & 3]
   const int vpos = xh * 18 * 256 + (c8 >> 2) * 128 + tl * 4 + (c8 & 3);
-
-  const unsigned char *xg = X.base + b * X.batch_stride + (int64_t)p0 * X.pix_stride;
 
   f32x16 acc[NP];
 #pragma unroll
@@ -189,75 +136,27 @@ __global__ __launch_bounds__(kWnThreads, 2) void fc_wino16_conv_kernel(Wn16KArgs
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[p][i] = 0.f;
 
-  // raw span of one chunk: global -> registers -> LDS (scaled), as in fc_wino.hip
-  const int npieces = geo.span * 4;
-  u32x4w pf[kWnPF];
-  auto piece_off = [&](int q) -> unsigned {
-    const int pix = q >> 2;
-    return (unsigned)min((int64_t)pix, avail - 1) * (unsigned)X.pix_stride + (unsigned)(q & 3) * 16u;
-  };
-  auto piece_store = [&](int q, u32x4w v, int cc) {
-    const int pix = q >> 2;
-    float f[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) f[e] = pix >= avail ? 0.f : __uint_as_float(v[e]) * sx;
-    float2 *d = reinterpret_cast<float2 *>(raw + (DB ? (cc & 1) * raw_bytes : 0) + pix * PITCH + (q & 3) * 16);
-    d[0] = make_float2(f[0], f[1]);
-    d[1] = make_float2(f[2], f[3]);
-  };
-  auto prefetch = [&](int cc) {
-    const unsigned char *base = xg + (int64_t)cc * X.chunk_stride;
-#pragma unroll
-    for (int i = 0; i < kWnPF; ++i) pf[i] = *reinterpret_cast<const u32x4w *>(base + piece_off(min(t + kWnThreads * i, npieces - 1)));
-  };
-  auto commit = [&](int cc) {
-#pragma unroll
-    for (int i = 0; i < kWnPF; ++i) {
-      // UNCONDITIONAL (threads behind the span rewrite its last piece with the same data, as they loaded it): with the store
-      // under `if (q < npieces)` the consumer of pf[i] sat in a divergent branch, hipcc kept the register "pending" on the
-      // skipped path and the NEXT prefetch -- which reuses pf[i]'s registers for its addresses right behind the multiply half
-      // -- opened with s_waitcnt vmcnt(4) .. vmcnt(0): a wait for the B words requested a moment earlier (seen in the ISA,
-      // round 6; the float32 kernel had carried it since round 3)
-      piece_store(min(t + kWnThreads * i, npieces - 1), pf[i], cc);
-    }
-    const unsigned char *base = xg + (int64_t)cc * X.chunk_stride;
-    for (int q = t + kWnThreads * kWnPF; q < npieces; q += kWnThreads)
-      piece_store(q, *reinterpret_cast<const u32x4w *>(base + piece_off(q)), cc);
-  };
+  WnStage<KS, DB, true> st;   // raw span of a chunk, scaled
+  st.init(a, grp, raw, sx);
 
-  // this lane's B words: U16[ntile][step][point][g][n][4]
+  // this lane's B words: U16[grp.ntile][step][point][g][n][4]
   const int nsteps = 2 * nch;
-  const unsigned ub_wave = __builtin_amdgcn_readfirstlane((unsigned)((((unsigned)ntile * nsteps) * kWnXi + NP * pg) * 2 * kWnN + nblk * 32));
+  const unsigned ub_wave = __builtin_amdgcn_readfirstlane((unsigned)((((unsigned)grp.ntile * nsteps) * kWnXi + NP * pg) * 2 * kWnN + nblk * 32));
   const u32x4w *ub = reinterpret_cast<const u32x4w *>(U) + ub_wave + g * kWnN + l31;
   u32x4w bf[NP];
   auto load_b = [&](int step, int p) { return ub[((unsigned)step * kWnXi + p) * 2 * kWnN]; };
 
-  // transform of step `step` (fc_wino.hip's, then the split): raw -> V[step & 1][point rows 3*HALF..][quad][tile][channel]
+  // transform of step `step` (the shared passes, then the split): raw -> V[step & 1][point rows 3*HALF..][quad][tile][channel]
   auto transform = [&](auto half_tag, int step) {
     constexpr int HALF = decltype(half_tag)::value;
-    const unsigned char *src = raw + (DB ? ((step >> 1) & 1) * raw_bytes : 0) + toff + (step & 1) * 32;
+    const unsigned char *src = raw + (DB ? ((step >> 1) & 1) * st.raw_bytes : 0) + toff + (step & 1) * 32;
     uint32_t *dst = vbuf + (step & 1) * kWnVFloats + vpos;
-    __builtin_amdgcn_s_setprio(3);
-    float tm[3][6];
+    const int row_pitch = a.Wp;
+    auto store_row = [&](int r, const float (&o)[6]) {
 #pragma unroll
-    for (int jp = 0; jp < 3; ++jp) {
-      f32x2v d[6], o[3];
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-        d[i] = f32x2v{*reinterpret_cast<const float *>(src + (i * Wp + 2 * jp) * PITCH),
-                      *reinterpret_cast<const float *>(src + (i * Wp + 2 * jp + 1) * PITCH)};
-      wn_bt3<HALF, f32x2v>(d, o);
-#pragma unroll
-      for (int r = 0; r < 3; ++r) tm[r][2 * jp] = o[r][0], tm[r][2 * jp + 1] = o[r][1];
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      float o[6];
-      wn_bt_pk(tm[r], o);
-#pragma unroll
-      for (int e = 0; e < 6; ++e) dst[(r * 6 + e) * 256] = (DBG & 32) ? (uint32_t)__float_as_uint(o[e]) : wn16_split(o[e]);
-    }
-    __builtin_amdgcn_s_setprio(0);
+      for (int e = 0; e < 6; ++e) dst[(r * 6 + e) * 256] = wn16_split(o[e]);
+    };
+#include "fc_wino_btdb3.inc"
   };
 
   // the wave's 18 MFMAs of step s: 9 points x (words, swapped words), taken in pairs of points so that the two MFMAs of an
@@ -290,72 +189,23 @@ __global__ __launch_bounds__(kWnThreads, 2) void fc_wino16_conv_kernel(Wn16KArgs
         acc[p + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1v, b1v, acc[p + 1], 0, 0, 0);
         acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0v, b0s, acc[p], 0, 0, 0);
         acc[p + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1v, b1s, acc[p + 1], 0, 0, 0);
-        if constexpr (!(DBG & 4)) {
-          bf[p] = load_b(sn, p);
-          bf[p + 1] = load_b(sn, p + 1);
-        }
+        bf[p] = load_b(sn, p);
+        bf[p + 1] = load_b(sn, p + 1);
       } else {
         acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0v, b0v, acc[p], 0, 0, 0);
         acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0v, b0s, acc[p], 0, 0, 0);
-        if constexpr (!(DBG & 4)) bf[p] = load_b(sn, p);
+        bf[p] = load_b(sn, p);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
   };
 
-  prefetch(0);
-  commit(0);
+  st.prefetch(0);
+  st.commit(0);
 #pragma unroll
   for (int p = 0; p < NP; ++p) bf[p] = load_b(0, p);
-  __syncthreads();
-  if (xh == 0) transform(Half0{}, 0);
-  else transform(Half1{}, 0);
-  __syncthreads();
-
-  stamp(t_pro);
-  for (int s = 0; s < nsteps; ++s) {
-    const int cc = s >> 1;
-    const int sn = min(s + 1, nsteps - 1);
-    const bool stage_next = !(s & 1) && cc + 1 < nch;
-    // The request for the next chunk's pixels, the transform and the write of those pixels sit in ONE branch: as two separate
-    // `if (stage_next)` around a shared transform hipcc cannot see that the write always follows the request, keeps the staging
-    // registers "pending" at the loop header and opens the next request with s_waitcnt vmcnt(4) .. vmcnt(0) -- a wait for the
-    // B words the multiply half requested a moment earlier (seen in the ISA, round 6; fc_wino.hip carried it since round 3).
-    constexpr bool kT = !(DBG & 1), kM = !(DBG & 2), kS = !(DBG & 8);
-    if (xh == 0) {
-      if constexpr (kM) multiply(s, sn);
-      __builtin_amdgcn_sched_barrier(0);
-      stamp(t_first);
-      if (kS && stage_next) {
-        prefetch(cc + 1);
-        if constexpr (kT) transform(Half0{}, s + 1);
-        if constexpr (DB) commit(cc + 1);
-      } else {
-        if constexpr (kT) transform(Half0{}, s + 1);
-      }
-      stamp(t_second);
-    } else {
-      if (kS && stage_next) {
-        prefetch(cc + 1);
-        if constexpr (kT) transform(Half1{}, s + 1);
-        if constexpr (DB) commit(cc + 1);
-      } else {
-        if constexpr (kT) transform(Half1{}, s + 1);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      stamp(t_first);
-      if constexpr (kM) multiply(s, sn);
-      stamp(t_second);
-    }
-    __syncthreads();
-    stamp(t_bar);
-    if constexpr (!DB) {
-      if (stage_next) {  // single raw buffer: written between two barriers (large maps only)
-        commit(cc + 1);
-        __syncthreads();
-      }
-    }
-  }
+  auto stamp = [](int) {};
+#include "fc_wino_step_loop.inc"
 
   // epilogue: Y = A^T M A = sum over the points (a, e) of A^T[i][a] A^T[j][e] M[a][e].  A wave holds nine points -- row
   // a = (9 pg) / 6 from column (9 pg) % 6 on and what follows -- of 32 tiles x 32 channels: C/D layout of the 32x32 MFMA,
@@ -364,8 +214,8 @@ __global__ __launch_bounds__(kWnThreads, 2) void fc_wino16_conv_kernel(Wn16KArgs
   // theirs in LDS, the fourth (pg == quarter) adds them to its own and stores.
   float4 *xch = reinterpret_cast<float4 *>(gfla_smem);   // [3 writers][2 channel blocks][4 rows][m*m / 4][64 lanes]
   constexpr int MM4 = M * M / 4;
-  const int col = ntile * kWnN + nblk * 32 + l31;
-  float *ob = out + b * out_bs + col;
+  const int col = grp.ntile * kWnN + nblk * 32 + l31;
+  float *ob = out + grp.b * a.out_bs + col;
   auto partial = [&](auto pg_tag, int i, float (&part)[M * M]) {
     constexpr int PG = decltype(pg_tag)::value;
 #pragma unroll
@@ -405,11 +255,11 @@ __global__ __launch_bounds__(kWnThreads, 2) void fc_wino16_conv_kernel(Wn16KArgs
       for (int qq = 0; qq < QPR; ++qq)
 #pragma unroll
         for (int r = 0; r < 4; ++r) partial(pg_tag, 4 * (q0 + qq) + r, part[qq][r]);
-      if constexpr (!(DBG & 256)) __syncthreads();   // the main loop's LDS (or the previous round's partials) is dead
+      __syncthreads();   // the main loop's LDS (or the previous round's partials) is dead
 #pragma unroll
       for (int qq = 0; qq < QPR; ++qq) {
         const int qd = q0 + qq;
-        if (PG != qd && !(DBG & 256)) {
+        if (PG != qd) {
           const int w3 = (PG - qd - 1) & 3;   // 0..2
           float4 *dst = xch + (((qq * 3 + w3) * 2 + nblk) * 4 * MM4) * 64 + lane;
 #pragma unroll
@@ -420,13 +270,13 @@ __global__ __launch_bounds__(kWnThreads, 2) void fc_wino16_conv_kernel(Wn16KArgs
                                                      part[qq][r][4 * c4 + 3]);
         }
       }
-      if constexpr (!(DBG & 256)) __syncthreads();
+      __syncthreads();
 #pragma unroll
       for (int qq = 0; qq < QPR; ++qq) {
         const int qd = q0 + qq;
         if (PG != qd) continue;
 #pragma unroll
-        for (int w3 = 0; w3 < ((DBG & 256) ? 0 : 3); ++w3) {
+        for (int w3 = 0; w3 < 3; ++w3) {
           const float4 *srcp = xch + (((qq * 3 + w3) * 2 + nblk) * 4 * MM4) * 64 + lane;
 #pragma unroll
           for (int r = 0; r < 4; ++r)
@@ -438,97 +288,275 @@ __global__ __launch_bounds__(kWnThreads, 2) void fc_wino16_conv_kernel(Wn16KArgs
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int slot_ = 8 * qd + 4 * g + r, tau = tile0 + slot_;
-          if (slot_ >= geo.tpg || tau >= ntiles || col >= n_valid) continue;
-          const int ty = tau / geo.TW, tx = tau - ty * geo.TW;
+          const int slot_ = 8 * qd + 4 * g + r, tau = grp.tile0 + slot_;
+          if (slot_ >= a.geo.tpg || tau >= grp.ntiles || col >= a.n_valid) continue;
+          const int ty = tau / a.geo.TW, tx = tau - ty * a.geo.TW;
 #pragma unroll
           for (int i = 0; i < M; ++i) {
             const int yo = M * ty + i;
-            if (yo >= Ho) continue;
+            if (yo >= a.Ho) continue;
 #pragma unroll
             for (int j = 0; j < M; ++j) {
               const int xo = M * tx + j;
-              if (xo < Wv && (!(DBG & 128) || part[qq][r][i * M + j] == 1.2345f))
-                ob[(int64_t)(yo * Wv + xo) * ldo] = (part[qq][r][i * M + j] * inv_x) * inv_w;
+              if (xo < a.Wv) ob[(int64_t)(yo * a.Wv + xo) * a.ldo] = (part[qq][r][i * M + j] * inv_x) * inv_w;
             }
           }
         }
       }
     }
   };
-  if constexpr (DBG & 64) {
-    float keep = 0.f;   // (every accumulator stays live: the MFMAs must not be eliminated with the epilogue)
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) keep += acc[p][i];
-    if (keep == 1.2345f) ob[0] = keep * inv_x * inv_w;
-    return;
-  }
   if (pg == 0) finish(PgTag<0>{});
   else if (pg == 1) finish(PgTag<1>{});
   else if (pg == 2) finish(PgTag<2>{});
   else finish(PgTag<3>{});
-  if constexpr (DBG & 16) {
-    stamp(t_epi);
-    if (stamps && lane == 0) {
-      unsigned long long *o = stamps + ((int64_t)blockIdx.x * 8 + wave) * 6;
-      o[0] = t_pro, o[1] = t_first, o[2] = t_second, o[3] = t_bar, o[4] = t_epi, o[5] = (unsigned long long)xh;
-    }
-  }
 }
 
-static unsigned wn16_lds_bytes(int k, const WnGeo &g, bool double_raw) {
-  const int m = k == 5 ? 2 : 4;
-  const unsigned raw = k == 5 ? wn_raw_bytes<5>(g) : wn_raw_bytes<3>(g);
-  const unsigned main_loop = (unsigned)(2 * kWnVFloats * 4) + (double_raw ? 2u : 1u) * raw;
-  const unsigned exchange = (unsigned)(3 * 2 * 4 * m * m * 64 * 4) * (m == 2 ? 4u : 1u);   // (quarters per round: QPR)
-  return main_loop > exchange ? main_loop : exchange;
-}
-
-static int wn16_launch(const Wn16ConvJob *jobs, int njobs, int64_t B, int nch, const uint32_t *amax_w, hipStream_t stream) {
-  Wn16KArgs a[2];
-  int64_t wgs[2] = {0, 0};
-  bool db = tuning(21) != 1;
-  unsigned lds = 0;
-  for (int j = 0; j < njobs; ++j) db = db && wn16_lds_bytes(3, wn_geometry<3>(jobs[j].M, jobs[j].Wv, jobs[j].Wp), true) <= kWnLdsLimit;
-  for (int j = 0; j < 2; ++j) {
-    const Wn16ConvJob &J = jobs[j < njobs ? j : 0];
-    const WnGeo g = wn_geometry<3>(J.M, J.Wv, J.Wp);
-    const int ntn = (int)ceil_div(J.n_valid, kWnN);
-    const int64_t groups = B * g.ngroups;
-    a[j] = Wn16KArgs{J.X, J.U, J.amax_x, J.out, J.out_bs, J.ldo, J.n_valid, J.M / J.Wv, J.Wv, J.Wp, g, ntn, groups, J.S};
-    if (j < njobs) {
-      wgs[j] = ceil_div(groups, 8) * 8 * ntn;
-      lds = std::max(lds, wn16_lds_bytes(3, g, db));
-    }
-  }
-  if (wgs[0] + wgs[1] > 0x7fffffffLL || lds > kWnLdsLimit) return GFLA_ERR_UNSUPPORTED;
-  auto kern = db ? fc_wino16_conv_kernel<3, true> : fc_wino16_conv_kernel<3, false>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  kern<<<dim3((unsigned)(wgs[0] + wgs[1])), kWnThreads, lds, stream>>>(a[0], a[1], (unsigned)wgs[0], nch, amax_w,
-                                                                         db ? g_wino_stamps : nullptr);
-  return launch_status();
-}
+// epilogue: three writers per channel block, a round of QPR quarters
+constexpr unsigned wn16_exchange(int k) { return (unsigned)(3 * 2 * 4 * (k == 5 ? 2 * 2 : 4 * 4) * 64 * 4) * (k == 5 ? 4u : 1u); }
 
 bool fc_wino16_fits(int M, int Wv, int Wp, int k) {
   if (!fc_wino_fits(M, Wv, Wp, k)) return false;
-  const WnGeo g = k == 5 ? wn_geometry<5>(M, Wv, Wp) : wn_geometry<3>(M, Wv, Wp);
-  return wn16_lds_bytes(k, g, false) <= kWnLdsLimit;
+  const unsigned lds = k == 5 ? wn_lds_bytes<5>(wn_geometry<5>(M, Wv, Wp), false, wn16_exchange(5))
+                              : wn_lds_bytes<3>(wn_geometry<3>(M, Wv, Wp), false, wn16_exchange(3));
+  return lds <= kWnLdsLimit;
 }
 
 // one or two convolutions (same B, input chunks nch, k) in one launch; the contract of fc_wino_conv_jobs with the weights of
-// fc_wino16_pack_weights and the max |x| slot of every job's input
-int fc_wino16_conv_jobs(const Wn16ConvJob *jobs, int njobs, int64_t B, int nch, int k, const uint32_t *amax_w, hipStream_t stream) {
+// fc_wino16_pack_weights and the max |x| slot of every job's input (amax_x[j])
+int fc_wino16_conv_jobs(const WnConvJob *jobs, int njobs, const uint32_t *const *amax_x, int64_t B, int nch, int k,
+                        const uint32_t *amax_w, hipStream_t stream) {
   if (B <= 0 || njobs <= 0) return GFLA_OK;
   if (njobs > 2 || !amax_w || k != 3) return GFLA_ERR_UNSUPPORTED;   // (k = 5 runs on the direct kernels: fc_block.hip)
   for (int j = 0; j < njobs; ++j)
-    if (!jobs[j].amax_x || !fc_wino16_fits(jobs[j].M, jobs[j].Wv, jobs[j].Wp, k)) return GFLA_ERR_UNSUPPORTED;
+    if (!amax_x[j] || !fc_wino16_fits(jobs[j].M, jobs[j].Wv, jobs[j].Wp, k)) return GFLA_ERR_UNSUPPORTED;
   if (njobs == 2 && tuning(21) == 2) {
-    const int st = fc_wino16_conv_jobs(jobs, 1, B, nch, k, amax_w, stream);
-    return st != GFLA_OK ? st : fc_wino16_conv_jobs(jobs + 1, 1, B, nch, k, amax_w, stream);
+    const int st = fc_wino16_conv_jobs(jobs, 1, amax_x, B, nch, k, amax_w, stream);
+    return st != GFLA_OK ? st : fc_wino16_conv_jobs(jobs + 1, 1, amax_x + 1, B, nch, k, amax_w, stream);
   }
-  return wn16_launch(jobs, njobs, B, nch, amax_w, stream);
+  WnLaunch L;
+  const int st = wn_plan<3>(jobs, njobs, amax_x, B, wn16_exchange(3), L);
+  if (st != GFLA_OK) return st;
+  return L.db ? wn_start(fc_wino16_conv_kernel<3, true>, L, nch, stream, amax_w)
+              : wn_start(fc_wino16_conv_kernel<3, false>, L, nch, stream, amax_w);
+}
+
+// =====================================================================================================================
+// The k = 5 weight gradient with TWO-TERM f16 OPERANDS (arithmetic mode 5, round 6).
+//
+// fc_wino_wgrad_kernel spends 4 608 of a step's cycles per wave in v_mfma_f32_16x16x4_f32 (36 points x 4 k steps x 32 cycles),
+// and the float32 matrix instructions run at the f32 VECTOR rate: 0.54-0.56 of that pipe is all the kernel ever reached.  Same
+// formulation and skeleton (fc_wino_wgrad.h: units, staging, pipeline and epilogue) here, but both operands of the 36 point-wise products are split into two f16 terms
+// (as above: hi = RN16(v s), lo = RN16(v s - hi), s a power of two from the tensor's max |x|) and a step's 16 tiles are ONE
+// K = 32 reduction of v_mfma_f32_16x16x32_f16 -- K slots of a lane = its four tiles as (hi, hi, lo, lo | hi, hi, lo, lo) --
+// issued twice per point: against the lifted gradient's words as they are (hi hi + lo lo) and with the words of each pair
+// exchanged, which is a RENAMING of registers (hi lo + lo hi): 72 MFMAs of 16 cycles per step instead of 144 of 32.
+//   A = V[point][tile quad][c][(hi, hi, lo, lo) x 2] from LDS: the transform threads store their two halves of a value as two
+//       16-bit words (a lane = one (tile, channel, half of the points) item as before, but lanes now run over the four tiles of a
+//       quad first: 16-byte records fill up from four lanes);
+//   B = Zh: a lane lifts the dY values of ITS FOUR tiles (tile quad = lane >> 4) of a step, one point row at a time, and splits
+//       PAIRS of tiles: v_cvt_pk_f16_f32 (both hi), two v_fma_mix_f32 (the exact remainders, hi read as f16 from either half),
+//       v_cvt_pk_f16_f32 (both lo) -- two instructions per value, no half swaps;
+//   dY of the NEXT step (16 floats per lane) is requested while this step multiplies.
+// Error: the same as the convolutions' (every product is formed from all four cross terms with f32 accumulation inside the
+// MFMA); the accumulation over the tiles is f32 in both kernels.
+constexpr int kWw16Pitch = 80;      // LDS bytes per raw pixel: the four tiles of a quad are 2 pixels = 40 words = 8 banks apart
+constexpr int kWn16HeadZ = 4;       // A dY A^T grows a gradient by at most 9
+constexpr int kWw16VBytes = kWnXi * 4 * 16 * 16;   // one V buffer: [point][tile quad][channel][16 bytes]
+
+__device__ __forceinline__ void wn16_split_halves(float v, _Float16 &h, _Float16 &l) {
+  asm("" : "+v"(v));   // (opaque: see wn16_split)
+  h = (_Float16)v;
+  float rem;
+  asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(rem) : "v"(v), "v"(h));
+  l = (_Float16)rem;
+}
+// (hi0, hi1) and (lo0, lo1) words of two values (fc_gemm.h)
+__device__ __forceinline__ void wn16_split_pair(float v0, float v1, uint32_t &hi, uint32_t &lo) { fc_split_pair(v0, v1, hi, lo); }
+
+template <int A6>
+__device__ __forceinline__ f32x2v ww_lift2v(f32x2v a, f32x2v b) {
+  if constexpr (A6 == 0) return a;
+  else if constexpr (A6 == 1) return a + b;
+  else if constexpr (A6 == 2) return a - b;
+  else if constexpr (A6 == 3) return __builtin_elementwise_fma(f32x2v{2.f, 2.f}, b, a);
+  else if constexpr (A6 == 4) return __builtin_elementwise_fma(f32x2v{-0.5f, -0.5f}, b, a);
+  else return b;
+}
+
+// DBG (timing ablations, `make PROBES=1` builds only, tuning key 20 = 64 + bits; results are garbage): 1 no input transform,
+// 2 no MFMAs / A reads, 4 no lift / split of dY (constant B words), 8 no dY loads
+template <bool MR, int DBG = 0>
+__global__ __launch_bounds__(kWnThreads, 2) void fc_wino16_wgrad_kernel(WwKArgs a0, WwKArgs a1, int nsplit0, int cpad,
+                                                                       int raw_stride, const uint32_t *__restrict__ amax_x0,
+                                                                       const uint32_t *__restrict__ amax_x1,
+                                                                       const uint32_t *__restrict__ amax_z0,
+                                                                       const uint32_t *__restrict__ amax_z1) {
+  constexpr int KS = 5;
+  const bool second = (int)blockIdx.y >= nsplit0;
+  const WwKArgs a = ww_pick(second, a0, a1);
+  const float *__restrict__ Z = a.Z;
+  float *__restrict__ part = a.part;
+  const int ex = wn16_scale_exp(second ? *amax_x1 : *amax_x0, kWn16HeadX), ez = wn16_scale_exp(second ? *amax_z1 : *amax_z0, kWn16HeadZ);
+  const float sx = wn16_pow2(ex), sz = wn16_pow2(ez), inv_x = wn16_pow2(254 - ex), inv_z = wn16_pow2(254 - ez);
+  constexpr int M = 2, PITCH = kWw16Pitch;
+  extern __shared__ __attribute__((aligned(16))) unsigned char gfla_smem[];
+  unsigned char *vbuf = gfla_smem;                                  // [2][kWw16VBytes]
+  unsigned char *raw = gfla_smem + 2 * kWw16VBytes;                 // [2][rows][L][PITCH] float32, scaled
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, xh = wave >> 2;
+  const int cc = blockIdx.x, sp = (int)blockIdx.y - (second ? nsplit0 : 0);
+  const int64_t u0 = a.total_units * sp / a.nsplit, u1 = a.total_units * (sp + 1) / a.nsplit;
+  WwWalk<KS, MR, PITCH> walk;
+  walk.init(a.geo, raw_stride);
+  WwStage<KS, MR, PITCH, true> st;   // raw rows of a unit, scaled
+  st.init(a, walk, cc, raw, sx);
+
+  f32x4v acc[kWnXi];
+#pragma unroll
+  for (int q = 0; q < kWnXi; ++q) acc[q] = f32x4v{0.f, 0.f, 0.f, 0.f};
+
+  // transform item: tile 4 * (wave & 3) + (lane & 3) of the step's 16, channel lane >> 2, point rows 3*xh..
+  const int tj = lane & 3, tc = lane >> 2, tkg = wave & 3;
+  const int tl = 4 * tkg + tj;
+  // byte offset of this item's hi half inside a (point, quad, channel) record: (hi0, hi1, lo0, lo1, hi2, hi3, lo2, lo3)
+  const int vpos = (tkg * 16 + tc) * 16 + (tj >> 1) * 8 + (tj & 1) * 2;
+  auto transform = [&](auto half_tag, const WwUnit &un, int h, int rbuf, int vb) {
+    constexpr int HALF = decltype(half_tag)::value;
+    const unsigned char *src = walk.window(raw, un, h, tl, tc, rbuf);
+    unsigned char *dst = vbuf + vb * kWw16VBytes + vpos;
+    const int row_pitch = walk.Lr;
+    auto store_row = [&](int r, const float (&o)[6]) {
+#pragma unroll
+      for (int e = 0; e < 6; ++e) {
+        _Float16 hh, ll;
+        wn16_split_halves(o[e], hh, ll);
+        unsigned char *rec = dst + ((HALF * 3 + r) * 6 + e) * (4 * 16 * 16);
+        *reinterpret_cast<_Float16 *>(rec) = hh;
+        *reinterpret_cast<_Float16 *>(rec + 4) = ll;
+      }
+    };
+#include "fc_wino_btdb3.inc"
+  };
+
+  // multiply: this lane's B operand = Zh of the step's tiles 4 kq .. 4 kq + 3, hidden channel 16 wave + (lane & 15)
+  const int kq = lane >> 4, n = wave * 16 + (lane & 15);
+  float dy[4][M][M];   // raw dY values of the step about to be multiplied (masked and scaled at the top of multiply)
+  auto load_dy = [&](const WwUnit &un, int h) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int tile = h * 16 + 4 * kq + j;
+      int tr, tcol;
+      walk.tile_rc(tile < un.nt ? tile : 0, tr, tcol);
+      const float *zp = Z + un.b * a.z_bs + (a.z_lead + (int64_t)(M * (un.ty + tr)) * a.Wp + M * (un.tx0 + tcol)) * kFcHidden + n;
+#pragma unroll
+      for (int i = 0; i < M; ++i)
+#pragma unroll
+        for (int jj = 0; jj < M; ++jj) dy[j][i][jj] = (DBG & 8) ? 1.f : zp[(int64_t)(i * a.Wp + jj) * kFcHidden];
+    }
+  };
+  typedef unsigned int u32x2w __attribute__((ext_vector_type(2)));
+  auto multiply = [&](const WwUnit &un, int h, int vb, const WwUnit &un_next, int h_next, bool any_next) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool live = h * 16 + 4 * kq + j < un.nt;
+#pragma unroll
+      for (int i = 0; i < M; ++i)
+#pragma unroll
+        for (int jj = 0; jj < M; ++jj) dy[j][i][jj] = live ? dy[j][i][jj] * sz : 0.f;
+    }
+    const u32x4w *va = reinterpret_cast<const u32x4w *>(vbuf + vb * kWw16VBytes) + kq * 16 + (lane & 15);
+    // A words run two points ahead of their MFMAs (an LDS round trip is longer than a point's eight split instructions)
+    u32x4w a_q[4];
+    a_q[0] = va[0];
+    a_q[1] = va[64];
+    auto row = [&](auto a6_tag) {
+      constexpr int A6 = decltype(a6_tag)::value;
+      // the row's lift of the four tiles, as PAIRS of tiles (packed f32 adds; a pair is what one split consumes)
+      f32x2v ta01, ta23, tb01, tb23;
+      ta01 = ww_lift2v<A6>(f32x2v{dy[0][0][0], dy[1][0][0]}, f32x2v{dy[0][1][0], dy[1][1][0]});
+      ta23 = ww_lift2v<A6>(f32x2v{dy[2][0][0], dy[3][0][0]}, f32x2v{dy[2][1][0], dy[3][1][0]});
+      tb01 = ww_lift2v<A6>(f32x2v{dy[0][0][1], dy[1][0][1]}, f32x2v{dy[0][1][1], dy[1][1][1]});
+      tb23 = ww_lift2v<A6>(f32x2v{dy[2][0][1], dy[3][0][1]}, f32x2v{dy[2][1][1], dy[3][1][1]});
+      // two points at a time: the second product of a point depends on its first -- the other point's MFMA sits between them
+      auto points = [&](auto e_tag) {
+        constexpr int E = decltype(e_tag)::value;
+        constexpr int q = A6 * 6 + E;
+        u32x4w bw[2], bx[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          if (q + u + 2 < kWnXi && !(DBG & 2)) a_q[(q + u + 2) % 4] = va[(q + u + 2) * 64];
+          f32x2v z01, z23;
+          if (u == 0) z01 = ww_lift2v<E>(ta01, tb01), z23 = ww_lift2v<E>(ta23, tb23);
+          else z01 = ww_lift2v<E + 1>(ta01, tb01), z23 = ww_lift2v<E + 1>(ta23, tb23);
+          uint32_t h01, l01, h23, l23;
+          if constexpr (DBG & 4) {
+            h01 = __float_as_uint(dy[0][0][0]), l01 = __float_as_uint(dy[1][0][0]), h23 = __float_as_uint(dy[2][0][0]), l23 = __float_as_uint(dy[3][0][0]);
+          } else {
+            wn16_split_pair(z01[0], z01[1], h01, l01);
+            wn16_split_pair(z23[0], z23[1], h23, l23);
+          }
+          const u32x2w p01 = u32x2w{h01, l01}, p23 = u32x2w{h23, l23};
+          // (lo, hi) of each pair for the cross terms: one v_pk_mov_b32 per pair (the MFMA wants four consecutive registers).
+          // EARLY-CLOBBER outputs + s_nop: hipcc's hazard recognizer does not look inside inline asm.  Allocated in place the
+          // move landed right behind the first MFMA, which was still reading those registers (wrong sums, measured); a vector
+          // write also needs wait states before an MFMA reads the register (NaNs without the s_nop, measured).
+          u32x2w x01, x23;
+          asm("v_pk_mov_b32 %0, %2, %2 op_sel:[1,0]\n\tv_pk_mov_b32 %1, %3, %3 op_sel:[1,0]\n\ts_nop 3"
+              : "=&v"(x01), "=&v"(x23)
+              : "v"(p01), "v"(p23));
+          bw[u] = u32x4w{p01[0], p01[1], p23[0], p23[1]}, bx[u] = u32x4w{x01[0], x01[1], x23[0], x23[1]};
+        }
+        const f16x8 av0 = __builtin_bit_cast(f16x8, a_q[q % 4]), av1 = __builtin_bit_cast(f16x8, a_q[(q + 1) % 4]);
+        if constexpr (DBG & 2) {
+          acc[q][0] += __uint_as_float(bw[0][0] ^ bx[0][1]), acc[q + 1][0] += __uint_as_float(bw[1][2] ^ bx[1][3]);
+        } else {
+          acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av0, __builtin_bit_cast(f16x8, bw[0]), acc[q], 0, 0, 0);
+          acc[q + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av1, __builtin_bit_cast(f16x8, bw[1]), acc[q + 1], 0, 0, 0);
+          acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av0, __builtin_bit_cast(f16x8, bx[0]), acc[q], 0, 0, 0);
+          acc[q + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av1, __builtin_bit_cast(f16x8, bx[1]), acc[q + 1], 0, 0, 0);
+        }
+      };
+      points(PgTag<0>{}), points(PgTag<2>{}), points(PgTag<4>{});
+    };
+    row(PgTag<0>{}), row(PgTag<1>{}), row(PgTag<2>{}), row(PgTag<3>{}), row(PgTag<4>{}), row(PgTag<5>{});
+    // the NEXT step's dY values: requested now, into the registers this step is done with; they fly through the barrier and
+    // the other half of the next step
+    if (any_next) load_dy(un_next, h_next);
+  };
+
+  constexpr bool T = !(DBG & 1), S = true;
+  auto first = [&](const WwUnit &un) { load_dy(un, 0); };
+#include "fc_wino_wgrad_pipeline.inc"
+
+  // times the two inverse scales
+  float *o = part + (((int64_t)sp * KS * KS) * cpad + cc * kFcChunk) * kFcHidden + wave * 16 + (lane & 15);
+  auto unscaled = [&](float v) { return (v * inv_x) * inv_z; };
+#include "fc_wino_wgrad_epilogue.inc"
+}
+
+// the k = 5 weight gradients of both halves with two-term f16 operands: fc_wino_wgrad_jobs' contract plus the max |x| slots of
+// every job's activations (amax_x) and gradient map (amax_z)
+int fc_wino16_wgrad_jobs(const WwJob *jobs, int njobs, int cpad, int64_t B, int k, const uint32_t *const *amax_x,
+                         const uint32_t *const *amax_z, hipStream_t stream) {
+  if (k != 5 || njobs > 2) return GFLA_ERR_UNSUPPORTED;
+  if (B <= 0 || njobs <= 0) return GFLA_OK;
+  for (int j = 0; j < njobs; ++j)
+    if (!amax_x[j] || !amax_z[j]) return GFLA_ERR_UNSUPPORTED;
+  auto single = fc_wino16_wgrad_kernel<false>, multi = fc_wino16_wgrad_kernel<true>;
+#ifdef GFLA_PROBES
+  switch (tuning(20) >= 64 ? tuning(20) - 64 : 0) {
+    case 1: single = multi = fc_wino16_wgrad_kernel<true, 1>; break;
+    case 2: single = multi = fc_wino16_wgrad_kernel<true, 2>; break;
+    case 3: single = multi = fc_wino16_wgrad_kernel<true, 3>; break;
+    case 4: single = multi = fc_wino16_wgrad_kernel<true, 4>; break;
+    case 6: single = multi = fc_wino16_wgrad_kernel<true, 6>; break;
+    case 7: single = multi = fc_wino16_wgrad_kernel<true, 7>; break;
+    case 8: single = multi = fc_wino16_wgrad_kernel<true, 8>; break;
+    case 15: single = multi = fc_wino16_wgrad_kernel<true, 15>; break;
+    default: break;
+  }
+#endif
+  return ww_launch(jobs, njobs, cpad, B, k, kWw16Pitch, kWw16VBytes, single, multi, stream, amax_x[0], amax_x[njobs > 1 ? 1 : 0],
+                   amax_z[0], amax_z[njobs > 1 ? 1 : 0]);
 }
 
 }  // namespace gfla

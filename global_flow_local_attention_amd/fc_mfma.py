@@ -13,7 +13,7 @@ convolution.  `mode` picks the arithmetic of the contraction (include/gfla_hip.h
      from the tensor's max |x|) on the f16 matrix cores, f32 accumulation -- THE DEFAULT (round 6).  Which kernel runs what is
      decided per convolution by measurement (csrc/fc_block.hip: fc_plan): the k = 5 convolutions and every data gradient on the
      direct kernels (three cross products, mode 2's arithmetic) reading the float32 maps in place; the k = 3 forward and the
-     k = 5 weight gradient in the Winograd domain (all four cross products: csrc/fc_wino16.hip, fc_wino.hip); the k = 3 weight
+     k = 5 weight gradient in the Winograd domain (all four cross products: csrc/fc_wino16.hip); the k = 3 weight
      gradient is mode 4's kernel.  Same measured error as mode 4, same test bars;
   3 / 2  operands split into three / two f16 terms, f32 accumulation (labelled experiments);  1  one f16 term (bf16 path).
 """

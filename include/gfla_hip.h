@@ -94,7 +94,7 @@ const char *gfla_status_string(int status);
  *   key 25: be_fwd_pix_kernel: 1 = non-temporal output stores (A/B only: half the rate)
  *   key 27: (make PROBES=1 builds) timing ablations of the two round-4 block_extractor forward kernels
  *   key 29: Winograd-domain weight gradient: 1 = units of one tile row everywhere (round 3); 0 = whole tile rows per unit
- *           on maps whose tile rows fill at most half a unit (csrc/fc_wino.hip: MR)
+ *           on maps whose tile rows fill at most half a unit (csrc/fc_wino_wgrad.h: MR)
  *   key 30: big-plane kernels (few planes, each beyond the LDS budget: csrc/tile_map.h)   0 auto, 1 never (round 1's
  *           row-window kernels), 2 always (tests drive them at small shapes)
  *   key 31 / 32: rows / columns of a tile (0 auto: 16 x 32)   key 35 / 36: the same for block_extractor's forward (0 auto:

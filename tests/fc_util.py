@@ -588,7 +588,7 @@ def wn16_conv_lo(lin, w, Hv, Wv, k, x_max, w_max):
 
 
 def wn16_wgrad_lo(lin, dG, k, x_max, z_max):
-    """the same for the two-term f16 weight gradient (fc_wino.hip: fc_wino16_wgrad_kernel): dV as above, dZ = 2^(ez + 4 - 39) for
+    """the same for the two-term f16 weight gradient (fc_wino16.hip: fc_wino16_wgrad_kernel): dV as above, dZ = 2^(ez + 4 - 39) for
     the lifted gradient tiles A dY A^T; |d dW| <= |G^T| (sum_tiles dV |Zh| + |V| dZ) |G|"""
     Hv, Wv = dG.shape[2:]
     ext, TH, TW, m = wn_tiles(lin, Hv, Wv, k)
