@@ -14,6 +14,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kAggStreamWaves = 12;  // <= 12 waves per workgroup: the stream kernels hold ~170 VGPRs per lane
+constexpr int kAggChunk = 4;  // channels whose accumulators one lane of agg_fwd_lds_kernel keeps in registers at a time
 constexpr int kAggMaxChunk = 8;      // planes per chunk the stream kernels are instantiated for (2, 4, 6, 8)
 
 // ---------------------------------------------------------------------------------------------- plane layout in LDS
@@ -289,12 +290,7 @@ inline bool agg_stream_shape_ok(int64_t B, int64_t C, int64_t Hs, int64_t Ws, in
   return (k & 1) && Ws >= k + 1 && !(Ws & 1) && Ws < 32768 && Hs < 32000 && B * C * Hs * Ws < (1LL << 31) &&
          (!batch_in_grid_y || B <= 65535);
 }
-// Policy, not correctness.  Tuning keys 3 and 8 = 1 switch the stream kernels off (round 1's kernels: the tests' reference).
-inline bool agg_stream_enabled() { return tuning(3) != 1 && tuning(8) != 1; }
-// The aggregation takes them from k = 5: k = 3 has 16 patch words per output instead of 36, and there the per-group setup
-// of agg_fwd_lds_kernel costs less than the extra coefficient pass (23 us against 20 + 5 at the bench shape); key 8 = 2
-// forces them for every odd k.  (resample2d's d/d input2 has no such break-even: agg_stream_enabled() alone.)
-inline bool agg_stream_wanted(int k) { return agg_stream_enabled() && (k >= 5 || tuning(8) == 2); }
+// (Policy -- whether the default dispatch wants them -- is gs_route.h: agg_stream_enabled / agg_stream_wanted.)
 
 // Geometry + grid of a stream-kernel launch; false: no chunk fits LDS, or the padded grid overflows.
 struct AggStreamPlan { AggStreamGeo pg; int64_t total, padded; };  // workgroups with work / launched (multiple of kNumXCD)

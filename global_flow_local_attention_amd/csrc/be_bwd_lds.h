@@ -294,31 +294,14 @@ __global__ __launch_bounds__(kLdsThreads) void be_bwd_lds_kernel(
   }
 }
 
-// Launch geometry of be_bwd_lds_kernel (the launcher below and gfla_lds_plane_geometry use it).  The factored / unfold forms
-// are only produced for planes that fit; the tensor form may window.  16-bit storage (elem_size 2): whole planes, one owner per
-// plane (no atomics on the planes).
-inline PlaneGeo be_bwd_lds_geometry(int mode, int elem_size, int acc_size, bool need_src, bool need_flow, int64_t B, int64_t C,
-                                    int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int K) {
-  const int bytes = (need_src ? (int)sizeof(lds_acc_t) : 0) + (need_flow ? acc_size : 0);
-  const bool half = elem_size == 2;
-  return (mode == kGoutTensor && !half) ? lds_geometry(Hs, Ws, bytes, B, C, Hf, Wf, K + 3, 1)
-                                        : plane_geometry(Hs * Ws, bytes, B, C, Hf * Wf, !half, 1);
-}
-
-// Launch helper.  mode = kGoutTensor / kGoutAttn / kGoutUnfold (see GoutRow).  *done = false when the
-// planes do not fit in LDS.
+// Launch helper.  mode = kGoutTensor / kGoutAttn / kGoutUnfold / kGoutUnfoldAttn (see GoutRow); g = the geometry the route
+// holds for this call (gs_route.h: be_bwd_lds_geometry; G > 0 and a grid that fits are the route's business).
 template <typename T, int K>
-static int launch_be_bwd_lds(int mode, const T *src, const T *flow, const T *gout, const T *attn, T *gsrc,
+static int launch_be_bwd_lds(int mode, const PlaneGeo &g, const T *src, const T *flow, const T *gout, const T *attn, T *gsrc,
                              typename Num<T>::acc *gflow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf,
-                             hipStream_t stream, bool *done, int64_t u_cs = 0, int64_t u_bs = 0,
+                             hipStream_t stream, int64_t u_cs = 0, int64_t u_bs = 0,
                              const T *gout2 = nullptr, const unsigned *skip_stat = nullptr, unsigned skip_limit = 0) {
-  using A = typename Num<T>::acc;
-  *done = false;
-  PlaneGeo g = be_bwd_lds_geometry(mode, (int)sizeof(T), (int)sizeof(A), gsrc != nullptr, gflow != nullptr, B, C, Hs, Ws, Hf, Wf, K);
-  if (g.G == 0) return GFLA_OK;
-  const int64_t blocks = B * g.ngroups * g.split;
-  if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)blocks), blk(kLdsThreads);
+  const dim3 grid((unsigned)(B * g.ngroups * g.split)), blk(kLdsThreads);
 #define GFLA_BE_BWD_LAUNCH(S, F, AT)                                                                 \
   if (AT == kGoutTensor && g.margin >= 0)                                                            \
     launch_lds(be_bwd_lds_kernel<T, K, S, F, kGoutTensor, true>, grid, blk, g.lds_bytes, stream,             \
@@ -346,7 +329,6 @@ static int launch_be_bwd_lds(int mode, const T *src, const T *flow, const T *gou
     else GFLA_BE_BWD_LAUNCH(false, true, kGoutTensor);
   }
 #undef GFLA_BE_BWD_LAUNCH
-  *done = true;
   return launch_status();
 }
 

@@ -253,8 +253,8 @@ struct PixGeo {
 
 // G channel planes (padded) per workgroup, `split` workgroups per (b, group), `threads` per workgroup.
 // tuning: key 4 caps G, key 5 sets split, key 24 the threads.
-template <int CH>
-inline PixGeo pix_geometry(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int K, int acc_bytes) {
+// CH = channels a lane evaluates together (be_pix_chunk).
+inline PixGeo pix_geometry(int CH, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int K, int acc_bytes) {
   PixGeo g{0, 0, 1, 512, 0};
   const int64_t plane_bytes = Hs * (Ws + 2 * K) * acc_bytes;
   const int64_t budget = kLdsBudget;
@@ -283,17 +283,14 @@ inline PixGeo pix_geometry(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t
   return g;
 }
 
+// register budget: CH x (K+1) patch values + K x 4 weights
+constexpr int be_pix_chunk(int acc_bytes, int K) { return acc_bytes == 8 ? (K >= 4 ? 1 : 2) : 4; }
+
 template <typename T, int K>
-static int launch_fwd_pix(const T *src, const T *flow, T *out, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
-                          int64_t Wf, hipStream_t stream, bool *done) {
-  using A = typename Num<T>::acc;
-  constexpr int CH = sizeof(A) == 8 ? (K >= 4 ? 1 : 2) : 4;  // register budget: CH x (K+1) patch values + K x 4 weights
-  *done = false;
-  const PixGeo g = pix_geometry<CH>(B, C, Hs, Ws, Hf, Wf, K, (int)sizeof(A));
-  if (g.G <= 0) return GFLA_OK;
-  const int64_t blocks = B * g.ngroups * g.split;
-  if (blocks > 0x7fffffffLL) return GFLA_OK;
-  const dim3 grid((unsigned)blocks), block((unsigned)g.threads);
+static int launch_fwd_pix(const PixGeo &g, const T *src, const T *flow, T *out, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
+                          int64_t Hf, int64_t Wf, hipStream_t stream) {
+  constexpr int CH = be_pix_chunk((int)sizeof(typename Num<T>::acc), K);
+  const dim3 grid((unsigned)(B * g.ngroups * g.split)), block((unsigned)g.threads);
 #define GFLA_PIX_LAUNCH(NT_, ABL_)                                                                                      \
   launch_lds(be_fwd_pix_kernel<T, K, CH, NT_, ABL_>, grid, block, g.lds_bytes, stream, src, flow, out, (int)C, (int)Hs,   \
              (int)Ws, (int)Hf, (int)Wf, g.G, g.ngroups, g.split)
@@ -305,7 +302,6 @@ static int launch_fwd_pix(const T *src, const T *flow, T *out, int64_t B, int64_
 #endif
   else GFLA_PIX_LAUNCH(false, 0);
 #undef GFLA_PIX_LAUNCH
-  *done = true;
   return launch_status();
 }
 

@@ -277,14 +277,9 @@ inline WrowGeo wrow_geometry(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64
 }
 
 template <typename T, int K>
-static int launch_fwd_wrow(const T *src, const T *flow, T *out, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
-                           int64_t Wf, hipStream_t stream, bool *done) {
-  using A = typename Num<T>::acc;
-  *done = false;
-  const WrowGeo g = wrow_geometry(B, C, Hs, Ws, Hf, Wf, K, (int)sizeof(A), (int)sizeof(T));
-  if (g.G <= 0) return GFLA_OK;
+static int launch_fwd_wrow(const WrowGeo &g, const T *src, const T *flow, T *out, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
+                           int64_t Hf, int64_t Wf, hipStream_t stream) {
   const int64_t blocks = B * g.ngroups;
-  if (blocks > 0x7fffffffLL || (int64_t)K * K * Hf * Wf > 0x7fffffffLL) return GFLA_OK;
 #ifdef GFLA_PROBES   // timing ablations (results are garbage): key 27 bit 0 = no patch reads, bit 1 = no output stores
 #define GFLA_WROW_ABL(N_)                                                                                                 \
   launch_lds(be_fwd_wrow_kernel<T, K, N_>, dim3((unsigned)blocks), dim3((unsigned)g.threads), g.lds_bytes, stream, src,    \
@@ -297,7 +292,6 @@ static int launch_fwd_wrow(const T *src, const T *flow, T *out, int64_t B, int64
 #endif
   launch_lds(be_fwd_wrow_kernel<T, K>, dim3((unsigned)blocks), dim3((unsigned)g.threads), g.lds_bytes, stream, src, flow,
              out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.G, g.ngroups, g.rpw, g.tile_off, g.tile_stride);
-  *done = true;
   return launch_status();
 }
 

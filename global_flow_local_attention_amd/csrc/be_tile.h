@@ -311,32 +311,41 @@ __global__ __launch_bounds__(512) void be_fwd_tile_kernel(const T *__restrict__ 
   }
 }
 
+// channels a lane of the forward kernels evaluates together: the global-gather version / the window kernel
+// (K = 3: 4 -> 2 measured 28.4 -> 27.2 us; 2 -> 1 in the tile kernel 28.1 -> 26.7 on a smooth flow, k = 5 on a wild flow 143 ->
+// 120, the other flows within 3 % either way: session s32)
+constexpr int be_gpix_chunk(int acc_bytes, int K) { return acc_bytes == 8 ? (K >= 4 ? 1 : 2) : (K >= 3 ? 2 : 4); }
+constexpr int be_tile_chunk(int acc_bytes, int K) { return acc_bytes == 8 ? be_gpix_chunk(8, K) : (K >= 3 ? 1 : 4); }
+
+// first version of the forward (tuning key 38 = 1): global gathers, lane = pixel, four channel ranges per workgroup
+struct BeGpixGeo {
+  int cpw, ncs4, nblk;
+  int64_t nwg;
+};
+inline BeGpixGeo be_gpix_geometry(int64_t B, int64_t C, int64_t Hf, int64_t Wf, int K, int acc_bytes) {
+  const int64_t nblk = ceil_div(Hf * Wf, 64);
+  const int cpw = big_channels_per_wave(B, C, nblk, be_gpix_chunk(acc_bytes, K), 24 * kNumCU);
+  const int64_t ncs4 = ceil_div(ceil_div(C, cpw), 4);
+  return BeGpixGeo{cpw, (int)ncs4, (int)nblk, B * nblk * ncs4};
+}
 template <typename T, int K>
-static int launch_fwd_big(const T *src, const T *flow, T *out, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
-                          int64_t Wf, hipStream_t stream, bool *done) {
+static int launch_fwd_gpix(const BeGpixGeo &g, const T *src, const T *flow, T *out, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
+                           int64_t Wf, hipStream_t stream) {
+  constexpr int CH = be_gpix_chunk((int)sizeof(typename Num<T>::acc), K);
+  be_fwd_gpix_kernel<T, K, CH><<<dim3((unsigned)g.nwg), dim3(256), 0, stream>>>(src, flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf,
+                                                                               (int)Wf, g.cpw, g.ncs4, g.nblk, g.nwg);
+  return launch_status();
+}
+
+// the window kernel; bg = big_geometry(0, ...)
+template <typename T, int K>
+static int launch_fwd_tile(const BigGeo &bg, const T *src, const T *flow, T *out, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
+                           int64_t Wf, hipStream_t stream) {
   using A = typename Num<T>::acc;
-  // (K = 3: 4 -> 2 measured 28.4 -> 27.2 us; 2 -> 1 in the tile kernel 28.1 -> 26.7 on a smooth flow, k = 5 on a wild flow 143 ->
-  // 120, the other flows within 3 % either way: session s32)
-  constexpr int CH = sizeof(A) == 8 ? (K >= 4 ? 1 : 2) : (K >= 3 ? 2 : 4);
-  constexpr int CH_TILE = sizeof(A) == 8 ? CH : (K >= 3 ? 1 : 4);
-  *done = false;
-  if (Hs * Ws > 0x3fffffffLL) return GFLA_OK;
-  if (tuning(38) == 1) {   // first version: global gathers, lane = pixel, four channel ranges per workgroup
-    const int64_t nblk = ceil_div(Hf * Wf, 64);
-    const int cpw = big_channels_per_wave(B, C, nblk, CH, 24 * kNumCU);
-    const int64_t ncs = ceil_div(C, cpw), ncs4 = ceil_div(ncs, 4);
-    const int64_t nwg = B * nblk * ncs4;
-    if (nwg > 0x7fffffffLL) return GFLA_OK;
-    be_fwd_gpix_kernel<T, K, CH><<<dim3((unsigned)nwg), dim3(256), 0, stream>>>(src, flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf,
-                                                                               (int)Wf, cpw, (int)ncs4, (int)nblk, nwg);
-    *done = true;
-    return launch_status();
-  }
-  const BigGeo bg = big_geometry(0, B, C, Hf, Wf, K + 1, (int)sizeof(A));
+  constexpr int CH_TILE = be_tile_chunk((int)sizeof(A), K);
   const TileGeo tg = bg.tg;
   const int G = bg.G;
   const int64_t ngroups = bg.ngroups, nwg = bg.nwg;
-  if (nwg > 0x7fffffffLL) return GFLA_OK;
   const unsigned lds_bytes = bg.lds_bytes;
 #define GFLA_BE_FWD_TILE(CH_)                                                                                                       \
   launch_lds(be_fwd_tile_kernel<T, K, CH_>, dim3((unsigned)nwg), dim3((unsigned)tg.threads), lds_bytes, stream, src, flow, out, (int)C, \
@@ -350,7 +359,6 @@ static int launch_fwd_big(const T *src, const T *flow, T *out, int64_t B, int64_
     GFLA_BE_FWD_TILE(CH_TILE);
   }
 #undef GFLA_BE_FWD_TILE
-  *done = true;
   return launch_status();
 }
 
@@ -657,19 +665,16 @@ __global__ __launch_bounds__(512, (sizeof(T) == 4 ? 4 : 2)) void be_bwd_tile_ker
   }
 }
 
+// bg = big_geometry(1, ...); f32 / f64 only (16-bit storage has no atomics: the planes-in-LDS kernels only)
 template <typename T, int K>
-static int launch_be_bwd_tile(const T *src, const T *flow, const T *gout, T *gsrc, typename Num<T>::acc *gflow, int64_t B,
-                              int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, hipStream_t stream, bool *done) {
-  *done = false;
+static int launch_be_bwd_tile(const BigGeo &bg, const T *src, const T *flow, const T *gout, T *gsrc, typename Num<T>::acc *gflow,
+                              int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, hipStream_t stream) {
   if constexpr (sizeof(T) == 2) {
-    return GFLA_OK;  // bf16 storage has no atomics: the planes-in-LDS kernels only
+    return GFLA_ERR_UNSUPPORTED;
   } else {
-    if (Hs * Ws > 0x3fffffffLL || (int64_t)K * Hf * K * Wf > 0x7fffffffLL) return GFLA_OK;
-    const BigGeo bg = big_geometry(1, B, C, Hf, Wf, K + 1, (gsrc ? (int)sizeof(lds_acc_t) : 0) + (gflow ? (int)sizeof(typename Num<T>::acc) : 0));
     const TileGeo tg = bg.tg;
     const int G = bg.G;
     const int64_t ngroups = bg.ngroups, nwg = bg.nwg;
-    if (nwg > 0x7fffffffLL) return GFLA_OK;
     const unsigned lds_bytes = bg.lds_bytes;
     const dim3 grid((unsigned)nwg), blk((unsigned)tg.threads);
 #define GFLA_BE_TILE_LAUNCH(S, F)                                                                                          \
@@ -680,7 +685,6 @@ static int launch_be_bwd_tile(const T *src, const T *flow, const T *gout, T *gsr
     else if (gsrc) GFLA_BE_TILE_LAUNCH(true, false);
     else GFLA_BE_TILE_LAUNCH(false, true);
 #undef GFLA_BE_TILE_LAUNCH
-    *done = true;
     return launch_status();
   }
 }

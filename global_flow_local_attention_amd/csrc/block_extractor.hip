@@ -15,10 +15,7 @@
 //            instead of C*k^2 colliding atomics per address), grad_source is scattered with
 //            double-precision LDS planes (ds_add_f64) flushed once, or relaxed device-scope float atomics when the plane does not fit.
 #include "gfla_common.h"
-#include "be_bwd_lds.h"
-#include "be_fwd_pix.h"
-#include "be_fwd_wrow.h"
-#include "be_tile.h"
+#include "gs_route.h"
 
 namespace gfla {
 
@@ -94,23 +91,6 @@ __global__ __launch_bounds__(kBlock) void be_fwd_rows_kernel(
     plane += plane_sz;
     orow += oplane_sz;
   }
-}
-
-template <typename T, int V>
-static int launch_fwd_rows(const T *src, const T *flow, T *out, int64_t B, int64_t C, int64_t Hs,
-                           int64_t Ws, int64_t Hf, int64_t Wf, int k, hipStream_t stream) {
-  const int64_t Ho = k * Hf, Wo = k * Wf;
-  const int64_t sp = Ho * (Wo / V);
-  const int64_t sp_blocks = ceil_div(sp, kBlock);
-  int cpt = tuning(1) > 0 ? tuning(1) : pick_channels_per_thread(sp_blocks * kBlock, C, B, 16);
-  if (cpt > C) cpt = (int)C;
-  const int64_t ncg = ceil_div(C, cpt);
-  const int64_t blocks = sp_blocks * ncg * B;
-  if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((be_fwd_rows_kernel<T, V>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, src,
-                     flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k, cpt, (int)ncg,
-                     (int)sp_blocks);
-  return launch_status();
 }
 
 // ----------------------------------------------------------------------------------------
@@ -213,74 +193,36 @@ __global__ __launch_bounds__(kLdsThreads) void be_fwd_lds_kernel(
   }
 }
 
+// The route (gs_route.h: be_fwd_route) has decided; V = outputs per lane of round 1's kernels (kLds, kRows).
 template <typename T, int V>
-static int launch_fwd(const T *src, const T *flow, T *out, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
+static int launch_fwd(const BeFwdRoute &r, const T *src, const T *flow, T *out, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
                       int64_t Hf, int64_t Wf, int k, hipStream_t stream) {
-  using A = typename Num<T>::acc;
-  const int variant = tuning(0);
-  // key 0: 0 auto, 1 global-gather kernel, 2 round 1's planes-in-LDS kernel (lane = output quad), 3 the lane-per-pixel
-  // kernel with direct stores (be_fwd_pix.h), 4 the wave-per-flow-row kernel (be_fwd_wrow.h).
-  // auto: flow rows of up to 64 pixels go to the wave-per-flow-row kernel (contiguous pieces whatever the width: 4.6-5.6
-  // TB/s), wider ones to the lane-per-pixel kernel (5.2 TB/s when its output rows are whole 128-byte lines, 3.8-4.7
-  // otherwise), planes beyond the LDS budget to round 1's windowed kernel
-  if constexpr (sizeof(T) >= 4) {
-    // few planes, each far beyond the LDS budget (BASELINE configs[1]): parallelism from pixel blocks, not planes (be_tile.h)
-    if (variant == 0 && k >= 2 && k <= 5 && big_plane_regime(B, C, Hs * Ws * (int64_t)sizeof(A), lds_budget())) {
-      bool done = false;
-      int st = GFLA_OK;
-      switch (k) {
-        case 2: st = launch_fwd_big<T, 2>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-        case 3: st = launch_fwd_big<T, 3>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-        case 4: st = launch_fwd_big<T, 4>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-        default: st = launch_fwd_big<T, 5>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-      }
-      if (done) note_path(GFLA_PATH_BE_FWD_GPIX);
-      if (done || st != GFLA_OK) return st;
-    }
-    // small output planes (<= 32 KB: a whole plane is a few hundred lines that one workgroup writes within microseconds)
-    // stream slightly faster from the lane-per-pixel kernel: (32,256,32,22) k=3 40 us against 41-45
-    const bool small_plane = (int64_t)k * k * Hf * Wf * (int64_t)sizeof(T) <= 32 * 1024 && Wf <= 64;
-    if ((variant == 4 || (variant == 0 && !small_plane)) && k >= 2 && k <= 5) {
-      bool done = false;
-      int st = GFLA_OK;
-      switch (k) {
-        case 2: st = launch_fwd_wrow<T, 2>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-        case 3: st = launch_fwd_wrow<T, 3>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-        case 4: st = launch_fwd_wrow<T, 4>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-        default: st = launch_fwd_wrow<T, 5>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-      }
-      if (done) note_path(GFLA_PATH_BE_FWD_PIX);
-      if (done || st != GFLA_OK) return st;
-    }
-    if (variant != 1 && variant != 2 && variant != 4 && k >= 2 && k <= 5) {  // lane = flow pixel, direct stores (be_fwd_pix.h)
-      bool done = false;
-      int st = GFLA_OK;
-      switch (k) {
-        case 2: st = launch_fwd_pix<T, 2>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-        case 3: st = launch_fwd_pix<T, 3>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-        case 4: st = launch_fwd_pix<T, 4>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-        default: st = launch_fwd_pix<T, 5>(src, flow, out, B, C, Hs, Ws, Hf, Wf, stream, &done); break;
-      }
-      if (done) note_path(GFLA_PATH_BE_FWD_PIX);
-      if (done || st != GFLA_OK) return st;
-    }
-  }
-  if (variant != 1) {
-    // work items = output positions; one flow row = k output rows of (k*Wf)/V positions
-    PlaneGeo g = lds_geometry(Hs, Ws, sizeof(A), B, C, Hf, (int64_t)k * ((k * Wf) / V), k + 1, 1);
-    if (g.G > 0) {
-      const int64_t blocks = B * g.ngroups * g.split;
-      if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-      if (g.margin < 0)
-        launch_lds(be_fwd_lds_kernel<T, V, false>, dim3((unsigned)blocks), dim3(kLdsThreads), g.lds_bytes, stream, 
-            src, flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k, g.G, g.ngroups, g.split, g.per, g.margin);
-      else
-        launch_lds(be_fwd_lds_kernel<T, V, true>, dim3((unsigned)blocks), dim3(kLdsThreads), g.lds_bytes, stream, 
-            src, flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k, g.G, g.ngroups, g.split, g.per, g.margin);
+  int st = GFLA_OK;
+  switch (r.path) {
+    case BeFwdPath::kUnsupported: return GFLA_ERR_UNSUPPORTED;
+    case BeFwdPath::kRows:
+      hipLaunchKernelGGL((be_fwd_rows_kernel<T, V>), dim3((unsigned)r.rows.blocks), dim3(kBlock), 0, stream, src, flow, out, (int)C,
+                         (int)Hs, (int)Ws, (int)Hf, (int)Wf, k, r.rows.cpt, r.rows.ncg, r.rows.sp_blocks);
+      return launch_status();
+    case BeFwdPath::kLds: {
+      const PlaneGeo &g = r.lds;
+      GFLA_WIN_SWITCH(g.margin, launch_lds(be_fwd_lds_kernel<T, V, WIN>, dim3((unsigned)plane_blocks(B, g)), dim3(kLdsThreads),
+                                           g.lds_bytes, stream, src, flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k, g.G,
+                                           g.ngroups, g.split, g.per, g.margin));
       return launch_status();
     }
+    default: break;
   }
-  return launch_fwd_rows<T, V>(src, flow, out, B, C, Hs, Ws, Hf, Wf, k, stream);
+  if constexpr (sizeof(T) >= 4) {  // the kernels with a compile-time kernel size: f32 / f64, k = 2 .. 5
+    GFLA_K_SWITCH(K, 2, 5, k, {
+      if (r.path == BeFwdPath::kGpix) st = launch_fwd_gpix<T, K>(r.gpix, src, flow, out, C, Hs, Ws, Hf, Wf, stream);
+      else if (r.path == BeFwdPath::kTile) st = launch_fwd_tile<T, K>(r.big, src, flow, out, C, Hs, Ws, Hf, Wf, stream);
+      else if (r.path == BeFwdPath::kWrow) st = launch_fwd_wrow<T, K>(r.wrow, src, flow, out, B, C, Hs, Ws, Hf, Wf, stream);
+      else st = launch_fwd_pix<T, K>(r.pix, src, flow, out, B, C, Hs, Ws, Hf, Wf, stream);
+    });
+    note_path(r.path == BeFwdPath::kGpix || r.path == BeFwdPath::kTile ? GFLA_PATH_BE_FWD_GPIX : GFLA_PATH_BE_FWD_PIX);
+  }
+  return st;
 }
 
 template <typename T>
@@ -292,12 +234,12 @@ static int block_extractor_fwd(const T *src, const T *flow, T *out, int64_t B, i
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   constexpr int VMAX = 16 / sizeof(T) > 4 ? 4 : 16 / sizeof(T);  // f32:4  f64:2  bf16:4 (8-byte store)
   const int64_t Wo = k * Wf;
-  const bool aligned = (reinterpret_cast<uintptr_t>(out) % (VMAX * sizeof(T))) == 0;
-  if (aligned && Wo % VMAX == 0)
-    return launch_fwd<T, VMAX>(src, flow, out, B, C, Hs, Ws, Hf, Wf, k, stream);
-  if (VMAX == 4 && (reinterpret_cast<uintptr_t>(out) % (2 * sizeof(T))) == 0 && Wo % 2 == 0)
-    return launch_fwd<T, 2>(src, flow, out, B, C, Hs, Ws, Hf, Wf, k, stream);
-  return launch_fwd<T, 1>(src, flow, out, B, C, Hs, Ws, Hf, Wf, k, stream);
+  const auto fits = [&](int v) { return reinterpret_cast<uintptr_t>(out) % (v * sizeof(T)) == 0 && Wo % v == 0; };
+  const int V = fits(VMAX) ? VMAX : (VMAX == 4 && fits(2)) ? 2 : 1;
+  const BeFwdRoute r = be_fwd_route((int)sizeof(T), (int)sizeof(typename Num<T>::acc), V, B, C, Hs, Ws, Hf, Wf, k);
+  if (V == VMAX) return launch_fwd<T, VMAX>(r, src, flow, out, B, C, Hs, Ws, Hf, Wf, k, stream);
+  if (V == 2) return launch_fwd<T, 2>(r, src, flow, out, B, C, Hs, Ws, Hf, Wf, k, stream);
+  return launch_fwd<T, 1>(r, src, flow, out, B, C, Hs, Ws, Hf, Wf, k, stream);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -426,41 +368,6 @@ __global__ __launch_bounds__(kBlock) void be_bwd_elem_kernel(
   }
 }
 
-template <typename T, int K>
-static int launch_bwd_pix(const T *src, const T *flow, const T *gout, T *gsrc, typename Num<T>::acc *gflow,
-                          int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf,
-                          hipStream_t stream) {
-  constexpr bool kBf16 = sizeof(T) == 2;
-  if (tuning(2) != 1 && !kBf16 &&
-      big_plane_regime(B, C, Hs * Ws * (int64_t)(sizeof(lds_acc_t) + sizeof(typename Num<T>::acc)), lds_budget())) {
-    bool done = false;   // few planes far beyond the LDS budget: flow-pixel tiles with bounding-box windows (be_tile.h)
-    int st = launch_be_bwd_tile<T, K>(src, flow, gout, gsrc, gflow, B, C, Hs, Ws, Hf, Wf, stream, &done);
-    if (done) note_path(GFLA_PATH_BE_BWD_TILE);
-    if (done || st != GFLA_OK) return st;
-  }
-  if (tuning(2) != 1 || kBf16) {
-    bool done = false;
-    int st = launch_be_bwd_lds<T, K>(kGoutTensor, src, flow, gout, static_cast<const T *>(nullptr), gsrc, gflow, B, C, Hs, Ws, Hf, Wf, stream, &done);
-    if (done) note_path(GFLA_PATH_BE_BWD_LDS);
-    if (done || st != GFLA_OK) return st;
-  }
-  if constexpr (kBf16) {
-    return GFLA_ERR_UNSUPPORTED;  // bf16 storage: the planes-in-LDS kernel only (global atomics need f32 / f64)
-  } else {
-  const int64_t sp_blocks = ceil_div(Hf * Wf, kBlock);
-  int cpt = tuning(1) > 0 ? tuning(1) : pick_channels_per_thread(sp_blocks * kBlock, C, B, 16, 2 * kNumCU * kWavesPerCU);
-  if (cpt > C) cpt = (int)C;
-  const int64_t ncg = ceil_div(C, cpt);
-  const int64_t blocks = sp_blocks * ncg * B;
-  if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-  note_path(GFLA_PATH_BE_BWD_GLOBAL);
-  hipLaunchKernelGGL((be_bwd_pix_kernel<T, K>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, src,
-                     flow, gout, gsrc, gflow, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, cpt,
-                     (int)ncg, (int)sp_blocks);
-  return launch_status();
-  }
-}
-
 template <typename T>
 static int block_extractor_bwd(const T *src, const T *flow, const T *gout, T *gsrc, typename Num<T>::acc *gflow,
                                int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
@@ -470,23 +377,39 @@ static int block_extractor_bwd(const T *src, const T *flow, const T *gout, T *gs
   if (Hs * Ws > 0x7fffffffLL || (k * Hf) * (k * Wf) > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
   if (!gsrc && !gflow) return GFLA_OK;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  switch (k) {
-    case 2: return launch_bwd_pix<T, 2>(src, flow, gout, gsrc, gflow, B, C, Hs, Ws, Hf, Wf, stream);
-    case 3: return launch_bwd_pix<T, 3>(src, flow, gout, gsrc, gflow, B, C, Hs, Ws, Hf, Wf, stream);
-    case 4: return launch_bwd_pix<T, 4>(src, flow, gout, gsrc, gflow, B, C, Hs, Ws, Hf, Wf, stream);
-    case 5: return launch_bwd_pix<T, 5>(src, flow, gout, gsrc, gflow, B, C, Hs, Ws, Hf, Wf, stream);
-    default: break;
+  const BeBwdRoute r = be_bwd_route((int)sizeof(T), (int)sizeof(typename Num<T>::acc), gsrc != nullptr, gflow != nullptr, B, C,
+                                    Hs, Ws, Hf, Wf, k);
+  int st = GFLA_ERR_UNSUPPORTED;
+  switch (r.path) {
+    case BeBwdPath::kUnsupported: break;
+    case BeBwdPath::kTile:
+      GFLA_K_SWITCH(K, 2, 5, k, st = launch_be_bwd_tile<T, K>(r.big, src, flow, gout, gsrc, gflow, C, Hs, Ws, Hf, Wf, stream));
+      note_path(GFLA_PATH_BE_BWD_TILE);
+      break;
+    case BeBwdPath::kLds:
+      GFLA_K_SWITCH(K, 2, 5, k, st = launch_be_bwd_lds<T, K>(kGoutTensor, r.lds, src, flow, gout, static_cast<const T *>(nullptr),
+                                                             gsrc, gflow, B, C, Hs, Ws, Hf, Wf, stream));
+      note_path(GFLA_PATH_BE_BWD_LDS);
+      break;
+    case BeBwdPath::kGlobal:
+    case BeBwdPath::kElem:
+      if constexpr (sizeof(T) != 2) {  // (global atomics need f32 / f64: the route sends no 16-bit call here)
+        if (r.path == BeBwdPath::kGlobal) {
+          note_path(GFLA_PATH_BE_BWD_GLOBAL);
+          const Geo &g = r.global;
+          GFLA_K_SWITCH(K, 2, 5, k, hipLaunchKernelGGL((be_bwd_pix_kernel<T, K>), dim3((unsigned)g.blocks), dim3(kBlock), 0, stream,
+                                                       src, flow, gout, gsrc, gflow, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf,
+                                                       g.cpt, g.ncg, g.sp_blocks));
+        } else {
+          const int64_t n = B * C * (k * Hf) * (k * Wf);
+          hipLaunchKernelGGL((be_bwd_elem_kernel<T>), dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, stream, src, flow,
+                             gout, gsrc, gflow, n, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k);
+        }
+        st = launch_status();
+      }
+      break;
   }
-  if constexpr (sizeof(T) == 2) {
-    return GFLA_ERR_UNSUPPORTED;
-  } else {
-    const int64_t n = B * C * (k * Hf) * (k * Wf);
-    const int64_t blocks = ceil_div(n, kBlock);
-    if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((be_bwd_elem_kernel<T>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, src, flow,
-                       gout, gsrc, gflow, n, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, k);
-    return launch_status();
-  }
+  return st;
 }
 
 // ----------------------------------------------------------------------------------------
@@ -600,20 +523,10 @@ __global__ __launch_bounds__(kLdsThreads) void be_unfold_fwd_lds_kernel(
   }
 }
 
-#define GFLA_BE_K_SWITCH(KV, ...)                  \
-  switch (KV) {                                    \
-    case 1: { constexpr int K = 1; __VA_ARGS__; } break;  \
-    case 2: { constexpr int K = 2; __VA_ARGS__; } break;  \
-    case 3: { constexpr int K = 3; __VA_ARGS__; } break;  \
-    case 4: { constexpr int K = 4; __VA_ARGS__; } break;  \
-    default: { constexpr int K = 5; __VA_ARGS__; } break; \
-  }
-
-static int unfold_check(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
-                        int bytes_per_elem) {
+static int unfold_check(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k, bool planes_fit) {
   if (B <= 0 || C <= 0 || Hs <= 0 || Ws <= 0 || Hf <= 0 || Wf <= 0 || k < 1) return GFLA_ERR_BAD_SHAPE;
   if (k > 5) return GFLA_ERR_UNSUPPORTED;
-  if (Hs * Ws * bytes_per_elem > kLdsBudget || Hf * Wf > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
+  if (!planes_fit || Hf * Wf > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
   return GFLA_OK;
 }
 
@@ -633,16 +546,16 @@ static int block_extractor_unfold_fwd(const T *src, const T *flow, T *out, int64
                                       gfla_stream_t stream_) {
   using A = typename Num<T>::acc;
   if (!src || !flow || !out) return GFLA_ERR_NULL_POINTER;
-  int st = unfold_check(B, C, Hs, Ws, Hf, Wf, k, sizeof(A));
+  int st = unfold_check(B, C, Hs, Ws, Hf, Wf, k, Hs * Ws * (int64_t)sizeof(A) <= lds_budget());
   if (st != GFLA_OK) return st;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  PlaneGeo g = unfold_fwd_geometry(sizeof(A), B, C, Hs, Ws, Hf, Wf);
-  const int64_t blocks = B * g.ngroups * g.split;
-  if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
+  const PlaneGeo g = unfold_fwd_route(sizeof(A), B, C, Hs, Ws, Hf, Wf, k);
+  if (g.G == 0) return GFLA_ERR_UNSUPPORTED;
   int64_t cs, bs;
   unfold_strides(layout, B, C, (int64_t)(Hf * Wf), k, &cs, &bs);
-  GFLA_BE_K_SWITCH(k, launch_lds(be_unfold_fwd_lds_kernel<T, K>, dim3((unsigned)blocks), dim3(kLdsThreads), g.lds_bytes, stream, 
-                          src, flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.G, g.ngroups, g.split, cs, bs));
+  GFLA_K_SWITCH(K, 1, 5, k, launch_lds(be_unfold_fwd_lds_kernel<T, K>, dim3((unsigned)plane_blocks(B, g)), dim3(kLdsThreads),
+                                       g.lds_bytes, stream, src, flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.G,
+                                       g.ngroups, g.split, cs, bs));
   return launch_status();
 }
 
@@ -652,157 +565,64 @@ static int block_extractor_unfold_bwd(const T *src, const T *flow, const T *gout
                                       int64_t Hf, int64_t Wf, int k, int layout, gfla_stream_t stream_) {
   using A = typename Num<T>::acc;
   if (!src || !flow || !gout) return GFLA_ERR_NULL_POINTER;
-  int st = unfold_check(B, C, Hs, Ws, Hf, Wf, k, sizeof(lds_acc_t) + sizeof(A));
+  int st = unfold_check(B, C, Hs, Ws, Hf, Wf, k, scatter_gather_planes_fit(Hs, Ws, sizeof(A)));
   if (st != GFLA_OK) return st;
   if (!gsrc && !gflow) return GFLA_OK;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  bool done = false;
+  const PlaneGeo g = whole_plane_bwd_route(kGoutUnfold, sizeof(T), sizeof(A), gsrc != nullptr, gflow != nullptr, B, C, Hs, Ws,
+                                           Hf, Wf, k);
+  if (g.G == 0) return GFLA_ERR_UNSUPPORTED;
   int64_t cs, bs;
   unfold_strides(layout, B, C, (int64_t)(Hf * Wf), k, &cs, &bs);
-  GFLA_BE_K_SWITCH(k, st = launch_be_bwd_lds<T, K>(kGoutUnfold, src, flow, gout, static_cast<const T *>(nullptr), gsrc,
-                                                   gflow, B, C, Hs, Ws, Hf, Wf, stream, &done, cs, bs));
-  if (st == GFLA_OK && !done) st = GFLA_ERR_UNSUPPORTED;
+  GFLA_K_SWITCH(K, 1, 5, k, st = launch_be_bwd_lds<T, K>(kGoutUnfold, g, src, flow, gout, static_cast<const T *>(nullptr), gsrc,
+                                                         gflow, B, C, Hs, Ws, Hf, Wf, stream, cs, bs));
   return st;
 }
 
 }  // namespace gfla
 
-using gfla::bf16_t;
-using gfla::f16_t;
+// ---- extern "C": one definer per GFLA_DECL_* family of include/gfla_hip.h, instantiated per suffix --------------------
+#define GFLA_BE_SHAPE_PARAMS int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k
+#define GFLA_BE_SHAPE_ARGS B, C, Hs, Ws, Hf, Wf, k
+
+#define GFLA_DEF_BLOCK_EXTRACTOR(SFX, T)                                                                              \
+  int gfla_block_extractor_fwd_##SFX(const T *s, const T *f, T *o, GFLA_BE_SHAPE_PARAMS, gfla_stream_t st) {          \
+    using E = gfla::elem_##SFX;                                                                                       \
+    return gfla::block_extractor_fwd<E>(gfla::as<E>(s), gfla::as<E>(f), gfla::as<E>(o), GFLA_BE_SHAPE_ARGS, st);      \
+  }
+#define GFLA_DEF_UNFOLD_FWD(SFX, T)                                                                                   \
+  int gfla_block_extractor_unfold_fwd_##SFX(const T *s, const T *f, T *o, GFLA_BE_SHAPE_PARAMS, int layout,           \
+                                            gfla_stream_t st) {                                                       \
+    using E = gfla::elem_##SFX;                                                                                       \
+    return gfla::block_extractor_unfold_fwd<E>(gfla::as<E>(s), gfla::as<E>(f), gfla::as<E>(o), GFLA_BE_SHAPE_ARGS,    \
+                                               layout, st);                                                           \
+  }
+// R = type of grad_flow, a reduction over channels and taps accumulated across channel groups with atomics: T for f32 / f64
+// (BLOCK_EXTRACTOR_BWD, UNFOLD_BWD), float for 16-bit storage (this file's part of BWD16; grad_source stays in the storage
+// type: accumulated into, exclusive owner per plane)
+#define GFLA_DEF_BLOCK_EXTRACTOR_BWD(SFX, T, R)                                                                       \
+  int gfla_block_extractor_bwd_##SFX(const T *s, const T *f, const T *go, T *gs, R *gf, GFLA_BE_SHAPE_PARAMS,         \
+                                     gfla_stream_t st) {                                                              \
+    using E = gfla::elem_##SFX;                                                                                       \
+    return gfla::block_extractor_bwd<E>(gfla::as<E>(s), gfla::as<E>(f), gfla::as<E>(go), gfla::as<E>(gs), gf,         \
+                                        GFLA_BE_SHAPE_ARGS, st);                                                      \
+  }
+#define GFLA_DEF_UNFOLD_BWD(SFX, T, R)                                                                                \
+  int gfla_block_extractor_unfold_bwd_##SFX(const T *s, const T *f, const T *go, T *gs, R *gf, GFLA_BE_SHAPE_PARAMS,  \
+                                            int layout, gfla_stream_t st) {                                           \
+    using E = gfla::elem_##SFX;                                                                                       \
+    return gfla::block_extractor_unfold_bwd<E>(gfla::as<E>(s), gfla::as<E>(f), gfla::as<E>(go), gfla::as<E>(gs), gf,  \
+                                               GFLA_BE_SHAPE_ARGS, layout, st);                                       \
+  }
+#define GFLA_DEF_BE_ALL(SFX, T, R)        \
+  GFLA_DEF_BLOCK_EXTRACTOR(SFX, T)        \
+  GFLA_DEF_UNFOLD_FWD(SFX, T)             \
+  GFLA_DEF_BLOCK_EXTRACTOR_BWD(SFX, T, R) \
+  GFLA_DEF_UNFOLD_BWD(SFX, T, R)
 
 extern "C" {
-int gfla_block_extractor_fwd_f32(const float *s, const float *f, float *o, int64_t B, int64_t C,
-                                 int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
-                                 gfla_stream_t st) {
-  return gfla::block_extractor_fwd<float>(s, f, o, B, C, Hs, Ws, Hf, Wf, k, st);
-}
-int gfla_block_extractor_fwd_f64(const double *s, const double *f, double *o, int64_t B, int64_t C,
-                                 int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
-                                 gfla_stream_t st) {
-  return gfla::block_extractor_fwd<double>(s, f, o, B, C, Hs, Ws, Hf, Wf, k, st);
-}
-int gfla_block_extractor_fwd_bf16(const uint16_t *s, const uint16_t *f, uint16_t *o, int64_t B,
-                                  int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
-                                  gfla_stream_t st) {
-  return gfla::block_extractor_fwd<bf16_t>(reinterpret_cast<const bf16_t *>(s),
-                                           reinterpret_cast<const bf16_t *>(f),
-                                           reinterpret_cast<bf16_t *>(o), B, C, Hs, Ws, Hf, Wf, k, st);
-}
-int gfla_block_extractor_bwd_f32(const float *s, const float *f, const float *go, float *gs,
-                                 float *gf, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
-                                 int64_t Wf, int k, gfla_stream_t st) {
-  return gfla::block_extractor_bwd<float>(s, f, go, gs, gf, B, C, Hs, Ws, Hf, Wf, k, st);
-}
-/* bf16 storage: grad_source bf16 (accumulated into, exclusive owner per plane); grad_flow FLOAT32 -- a sum over all
- * channels and taps, accumulated across channel groups with atomics */
-int gfla_block_extractor_bwd_bf16(const uint16_t *s, const uint16_t *f, const uint16_t *go, uint16_t *gs, float *gf,
-                                  int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
-                                  gfla_stream_t st) {
-  return gfla::block_extractor_bwd<bf16_t>(reinterpret_cast<const bf16_t *>(s), reinterpret_cast<const bf16_t *>(f),
-                                           reinterpret_cast<const bf16_t *>(go), reinterpret_cast<bf16_t *>(gs), gf, B, C,
-                                           Hs, Ws, Hf, Wf, k, st);
-}
-int gfla_block_extractor_bwd_f64(const double *s, const double *f, const double *go, double *gs,
-                                 double *gf, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
-                                 int64_t Hf, int64_t Wf, int k, gfla_stream_t st) {
-  return gfla::block_extractor_bwd<double>(s, f, go, gs, gf, B, C, Hs, Ws, Hf, Wf, k, st);
-}
-/* Host-side launch geometry of the planes-in-LDS kernels (include/gfla_lds_plane.h; no GPU needed).  The geometry itself comes
- * from the functions the launchers call; what is written out here is only whether the dispatch in front of a launcher hands it
- * the call at all (big-plane regime, keys 2 / 6, whole-plane requirements). */
-int gfla_lds_plane_geometry(int op, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k, int dilation,
-                            int elem_size, int needs, int64_t *out) {
-  if (!out) return GFLA_ERR_NULL_POINTER;
-  if (op < 0 || op > 7 || B <= 0 || C <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || k < 1 || dilation < 1 ||
-      (elem_size != 2 && elem_size != 4 && elem_size != 8) || (op <= 3 && (needs & 3) == 0) || (op >= 5 && k < 2))
-    return GFLA_ERR_BAD_SHAPE;
-  const int acc = elem_size == 8 ? 8 : 4;
-  gfla::PlaneGeo g{0, 0, 1, 0, 0, -1};
-  if (op <= 3) {
-    const bool tile = op == 0 && elem_size != 2 && gfla::tuning(2) != 1 &&
-                      gfla::big_plane_regime(B, C, Hs * Ws * (int64_t)(8 + acc), gfla::lds_budget());
-    if (k <= 5 && !tile && (gfla::tuning(2) != 1 || elem_size == 2 || op != 0))
-      g = gfla::be_bwd_lds_geometry(op, elem_size, acc, (needs & 1) != 0, (needs & 2) != 0, B, C, Hs, Ws, H, W, k);
-  } else if (op == 4) {
-    if (k <= 5 && Hs * Ws * (int64_t)acc <= gfla::lds_budget()) g = gfla::unfold_fwd_geometry(acc, B, C, Hs, Ws, H, W);
-  } else if (op == 5) {
-    if (gfla::tuning(6) != 1 && !gfla::big_plane_regime(B, C, Hs * Ws * (int64_t)acc, gfla::lds_budget()))
-      g = gfla::rs_gather_geometry(acc, B, C, Hs, Ws, H, W, k, dilation, 1);
-  } else {
-    const bool big = elem_size != 2 && gfla::tuning(6) != 1 && gfla::big_plane_regime(B, C, Hs * Ws * (int64_t)8, gfla::lds_budget());
-    const gfla::PlaneGeo pg1 = gfla::rs_scatter_geometry(elem_size, B, C, Hs, Ws, H, W, k, dilation);
-    const gfla::PlaneGeo pg2 = gfla::rs_gather_geometry(acc, B, C, Hs, Ws, H, W, k, dilation, 0);
-    if (!big && (gfla::tuning(6) != 1 || elem_size == 2) && pg1.G > 0 && pg2.G > 0) g = op == 6 ? pg1 : pg2;
-  }
-  const int64_t v[6] = {g.G, g.ngroups, g.split, g.per, g.margin, g.lds_bytes};
-  for (int i = 0; i < 6; ++i) out[i] = g.G > 0 ? v[i] : 0;
-  return GFLA_OK;
-}
-int gfla_unfold_supported(int64_t Hs, int64_t Ws, int k, int elem_size) {
-  const int acc = elem_size == 8 ? 8 : 4;
-  return (k >= 1 && k <= 5 && Hs > 0 && Ws > 0 && Hs * Ws * (int64_t)(8 + acc) <= gfla::lds_budget()) ? 1 : 0;
-}
-int gfla_block_extractor_unfold_fwd_f32(const float *s, const float *f, float *o, int64_t B, int64_t C,
-                                        int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k, int layout,
-                                        gfla_stream_t st) {
-  return gfla::block_extractor_unfold_fwd<float>(s, f, o, B, C, Hs, Ws, Hf, Wf, k, layout, st);
-}
-int gfla_block_extractor_unfold_fwd_f64(const double *s, const double *f, double *o, int64_t B, int64_t C,
-                                        int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k, int layout,
-                                        gfla_stream_t st) {
-  return gfla::block_extractor_unfold_fwd<double>(s, f, o, B, C, Hs, Ws, Hf, Wf, k, layout, st);
-}
-int gfla_block_extractor_unfold_fwd_bf16(const uint16_t *s, const uint16_t *f, uint16_t *o, int64_t B,
-                                         int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k, int layout,
-                                         gfla_stream_t st) {
-  return gfla::block_extractor_unfold_fwd<bf16_t>(reinterpret_cast<const bf16_t *>(s),
-                                                  reinterpret_cast<const bf16_t *>(f),
-                                                  reinterpret_cast<bf16_t *>(o), B, C, Hs, Ws, Hf, Wf, k, layout, st);
-}
-int gfla_block_extractor_unfold_bwd_f32(const float *s, const float *f, const float *go, float *gs, float *gf,
-                                        int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf,
-                                        int k, int layout, gfla_stream_t st) {
-  return gfla::block_extractor_unfold_bwd<float>(s, f, go, gs, gf, B, C, Hs, Ws, Hf, Wf, k, layout, st);
-}
-int gfla_block_extractor_unfold_bwd_bf16(const uint16_t *s, const uint16_t *f, const uint16_t *go, uint16_t *gs,
-                                         float *gf, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
-                                         int64_t Wf, int k, int layout, gfla_stream_t st) {
-  return gfla::block_extractor_unfold_bwd<bf16_t>(reinterpret_cast<const bf16_t *>(s), reinterpret_cast<const bf16_t *>(f),
-                                                  reinterpret_cast<const bf16_t *>(go), reinterpret_cast<bf16_t *>(gs), gf,
-                                                  B, C, Hs, Ws, Hf, Wf, k, layout, st);
-}
-int gfla_block_extractor_unfold_bwd_f64(const double *s, const double *f, const double *go, double *gs,
-                                        double *gf, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
-                                        int64_t Wf, int k, int layout, gfla_stream_t st) {
-  return gfla::block_extractor_unfold_bwd<double>(s, f, go, gs, gf, B, C, Hs, Ws, Hf, Wf, k, layout, st);
-}
-/* f16 storage: the bf16 entry points' twins (same kernels, IEEE binary16 loads and stores) */
-int gfla_block_extractor_fwd_f16(const uint16_t *s, const uint16_t *f, uint16_t *o, int64_t B,
-                                 int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
-                                 gfla_stream_t st) {
-  return gfla::block_extractor_fwd<f16_t>(reinterpret_cast<const f16_t *>(s),
-                                          reinterpret_cast<const f16_t *>(f),
-                                          reinterpret_cast<f16_t *>(o), B, C, Hs, Ws, Hf, Wf, k, st);
-}
-int gfla_block_extractor_bwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *go, uint16_t *gs, float *gf,
-                                 int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k,
-                                 gfla_stream_t st) {
-  return gfla::block_extractor_bwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
-                                          reinterpret_cast<const f16_t *>(go), reinterpret_cast<f16_t *>(gs), gf, B, C,
-                                          Hs, Ws, Hf, Wf, k, st);
-}
-int gfla_block_extractor_unfold_fwd_f16(const uint16_t *s, const uint16_t *f, uint16_t *o, int64_t B,
-                                        int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k, int layout,
-                                        gfla_stream_t st) {
-  return gfla::block_extractor_unfold_fwd<f16_t>(reinterpret_cast<const f16_t *>(s),
-                                                 reinterpret_cast<const f16_t *>(f),
-                                                 reinterpret_cast<f16_t *>(o), B, C, Hs, Ws, Hf, Wf, k, layout, st);
-}
-int gfla_block_extractor_unfold_bwd_f16(const uint16_t *s, const uint16_t *f, const uint16_t *go, uint16_t *gs,
-                                        float *gf, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
-                                        int64_t Wf, int k, int layout, gfla_stream_t st) {
-  return gfla::block_extractor_unfold_bwd<f16_t>(reinterpret_cast<const f16_t *>(s), reinterpret_cast<const f16_t *>(f),
-                                                 reinterpret_cast<const f16_t *>(go), reinterpret_cast<f16_t *>(gs), gf,
-                                                 B, C, Hs, Ws, Hf, Wf, k, layout, st);
-}
+GFLA_DEF_BE_ALL(f32, float, float)
+GFLA_DEF_BE_ALL(f64, double, double)
+GFLA_DEF_BE_ALL(bf16, uint16_t, float)
+GFLA_DEF_BE_ALL(f16, uint16_t, float)
 }

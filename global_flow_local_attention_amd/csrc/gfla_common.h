@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/gfla_hip.h"
 
 namespace gfla {
@@ -81,6 +83,14 @@ struct Num<f16_t> {
   static __device__ __forceinline__ f16_t from(float v) { return f16_t::from_bits(pack(v)); }
 };
 __host__ __device__ inline f16_t::f16_t(float v) : bits(Num<f16_t>::pack(v)) {}
+
+// ---- extern "C" definers: element type behind an entry point's suffix (16-bit storage crosses the ABI as uint16_t) ----
+typedef float elem_f32;
+typedef double elem_f64;
+typedef bf16_t elem_bf16;
+typedef f16_t elem_f16;
+template <typename E, typename S>
+static inline auto as(S *p) { return reinterpret_cast<std::conditional_t<std::is_const<S>::value, const E, E> *>(p); }
 
 // Vector of V storage elements written with ONE store instruction (V*sizeof(T) in {4,8,16}).
 template <typename T, int V>

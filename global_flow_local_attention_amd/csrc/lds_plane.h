@@ -142,32 +142,7 @@ inline PlaneGeo band_geometry(int64_t H, int64_t W, int bytes_per_elem, int64_t 
   return g;
 }
 
-// Either the whole plane (plane_geometry) or a row window (band_geometry).
-inline PlaneGeo lds_geometry(int64_t H, int64_t W, int bytes_per_elem, int64_t B, int64_t C, int64_t Hf,
-                             int64_t items_per_row, int k_span, int chunk = 0) {
-  PlaneGeo g = plane_geometry(H * W, bytes_per_elem, B, C, Hf * items_per_row, true, chunk);
-  if (g.G > 0) return g;
-  if (tuning(7) == 1) return g;  // windows disabled
-  return band_geometry(H, W, bytes_per_elem, B, C, Hf, items_per_row, k_span);
-}
-
-// The geometry of each launcher of the family, in one place: the launchers call these and gfla_lds_plane_geometry
-// (include/gfla_lds_plane.h) hands the same answers to the tests.  acc_size = sizeof(Num<T>::acc), elem_size = sizeof(T).
-// Unfold forward: whole gather planes only.
-inline PlaneGeo unfold_fwd_geometry(int acc_size, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf) {
-  return plane_geometry(Hs * Ws, acc_size, B, C, Hf * Wf, true);
-}
-// resample2d: forward and d/d input2 gather from planes of the arithmetic type, d/d input1 scatters into double planes.
-// 16-bit storage: the scatter planes are whole and have one owner each (the flush is a plain read-modify-write).
-inline PlaneGeo rs_gather_geometry(int acc_size, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k,
-                                   int dil, int chunk) {
-  return lds_geometry(Hi, Wi, acc_size, B, C, H, W, (k - 1) * dil + 1, chunk);
-}
-inline PlaneGeo rs_scatter_geometry(int elem_size, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k,
-                                    int dil) {
-  return elem_size == 2 ? plane_geometry(Hi * Wi, sizeof(lds_acc_t), B, C, H * W, false)
-                        : lds_geometry(Hi, Wi, sizeof(lds_acc_t), B, C, H, W, (k - 1) * dil + 1);
-}
+// (Whole plane or row window -- lds_geometry -- and the geometry of each launcher of the family: gs_route.h.)
 
 // Launch a kernel with `lds` bytes of dynamic LDS; above 64 KB the per-kernel limit has to be raised first.
 template <typename... KArgs, typename... Args>

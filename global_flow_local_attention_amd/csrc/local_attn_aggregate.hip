@@ -16,10 +16,9 @@
 #include <type_traits>
 
 #include "gfla_common.h"
-#include "be_bwd_lds.h"
+#include "gs_route.h"
 #include "patch_mfma.h"
 #include "rs_taps.h"
-#include "agg_stream.h"
 
 namespace gfla {
 
@@ -263,7 +262,6 @@ __global__ __launch_bounds__(kBlock) void agg_bwd_kernel(
 // ds_read_b32 gathers ((K+1)^2 per output in the dense case).  Backward additionally keeps G gradient
 // planes in LDS (ds_add_f32) and flushes them once.
 // ----------------------------------------------------------------------------------------------
-constexpr int kAggChunk = 4;  // channels whose accumulators one lane keeps in registers at a time
 
 template <typename T, int K>
 __global__ __launch_bounds__(kLdsThreads) void agg_fwd_lds_kernel(
@@ -1014,17 +1012,10 @@ __global__ __launch_bounds__(kAggStreamWaves * 64) void agg_ga_stream_kernel(
 }
 
 // resample2d d/d input2 (kernel_size 4, dilation 1) on agg_ga_stream_kernel<T, 3, 1>; gin2 (B, 3, H, W) float32, accumulated
-// into.  GFLA_ERR_UNSUPPORTED where the shape does not fit (the caller falls back to rs_lds_kernel<MODE 2>).
+// into.  pl = the plan of the route that chose this kernel (gs_route.h: rs_bwd_route).
 template <typename T>
-int rs_bwd2_stream(const T *in1, const T *in2, const T *gout, float *gin2, int64_t B, int64_t C, int64_t Hi, int64_t Wi,
-                   int64_t H, int64_t W, hipStream_t stream) {
-  constexpr int k = 3;
-  // B <= 65535 and B C H W < 2^31: bounds this entry has always had.  The kernel needs neither (it decodes the sample
-  // from blockIdx.x and indexes the flow map in 64 bits); dropping them would move calls onto another kernel.
-  if (!agg_stream_enabled() || !agg_stream_shape_ok(B, C, Hi, Wi, k, true) || B * C * H * W >= (1LL << 31))
-    return GFLA_ERR_UNSUPPORTED;
-  AggStreamPlan pl;
-  if (!agg_stream_plan(B, C, Hi, Wi, H, W, k, pl)) return GFLA_ERR_UNSUPPORTED;
+int rs_bwd2_stream(const AggStreamPlan &pl, const T *in1, const T *in2, const T *gout, float *gin2, int64_t C, int64_t Hi,
+                   int64_t Wi, int64_t H, int64_t W, hipStream_t stream) {
   const AggStreamGeo &pg = pl.pg;
   GFLA_AGG_CHT_SWITCH(pg.CH, launch_lds(agg_ga_stream_kernel<T, 3, 1, CHT>, dim3((unsigned)pl.padded), dim3(pg.threads), pg.lds,
                                         stream, in1, in2, gout, (float *)nullptr, (const T *)nullptr, gin2, (int)C, (int)Hi,
@@ -1032,11 +1023,11 @@ int rs_bwd2_stream(const T *in1, const T *in2, const T *gout, float *gin2, int64
                                         (int)pl.total, pg.tw_log2, pg.ntile));
   return launch_status();
 }
-template int rs_bwd2_stream<float>(const float *, const float *, const float *, float *, int64_t, int64_t, int64_t, int64_t,
-                                   int64_t, int64_t, hipStream_t);
-template int rs_bwd2_stream<bf16_t>(const bf16_t *, const bf16_t *, const bf16_t *, float *, int64_t, int64_t, int64_t,
-                                    int64_t, int64_t, int64_t, hipStream_t);
-template int rs_bwd2_stream<f16_t>(const f16_t *, const f16_t *, const f16_t *, float *, int64_t, int64_t, int64_t,
+template int rs_bwd2_stream<float>(const AggStreamPlan &, const float *, const float *, const float *, float *, int64_t, int64_t,
+                                   int64_t, int64_t, int64_t, hipStream_t);
+template int rs_bwd2_stream<bf16_t>(const AggStreamPlan &, const bf16_t *, const bf16_t *, const bf16_t *, float *, int64_t,
+                                    int64_t, int64_t, int64_t, int64_t, hipStream_t);
+template int rs_bwd2_stream<f16_t>(const AggStreamPlan &, const f16_t *, const f16_t *, const f16_t *, float *, int64_t, int64_t,
                                    int64_t, int64_t, int64_t, hipStream_t);
 
 // In place: glogits holds ga (d/d a_ij); turn it into d/d logit_ij = a_ij * (ga_ij - sum_mn a_mn ga_mn).
@@ -1064,38 +1055,12 @@ __global__ __launch_bounds__(kBlock) void agg_softmax_bwd_kernel(const T *__rest
   for (int t = 0; t < KK; ++t) gl[(int64_t)t * HW] = a[t] * (ga[t] - dot);
 }
 
-struct AggGeo {
-  int cpt, ncg, sp_blocks;
-  int64_t blocks;
-};
-static AggGeo agg_geometry(int64_t B, int64_t C, int64_t H, int64_t W, int max_cpt, int64_t want_waves) {
-  AggGeo g;
-  g.sp_blocks = (int)ceil_div(H * W, kBlock);
-  int cpt = tuning(1) > 0 ? tuning(1)
-                          : pick_channels_per_thread((int64_t)g.sp_blocks * kBlock, C, B, max_cpt, want_waves);
-  if (cpt > C) cpt = (int)C;
-  g.cpt = cpt;
-  g.ncg = (int)ceil_div(C, cpt);
-  g.blocks = (int64_t)g.sp_blocks * g.ncg * B;
-  return g;
-}
-
 static int agg_check(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k) {
   if (B <= 0 || C <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || k < 1) return GFLA_ERR_BAD_SHAPE;
   if (k > 5) return GFLA_ERR_UNSUPPORTED;  // fused path is instantiated for k = 1..5
   if (Hs * Ws > 0x7fffffffLL || H * W > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
   return GFLA_OK;
 }
-
-#define GFLA_K_SWITCH(KV, ...)                     \
-  switch (KV) {                                    \
-    case 1: { constexpr int K = 1; __VA_ARGS__; } break;  \
-    case 2: { constexpr int K = 2; __VA_ARGS__; } break;  \
-    case 3: { constexpr int K = 3; __VA_ARGS__; } break;  \
-    case 4: { constexpr int K = 4; __VA_ARGS__; } break;  \
-    default: { constexpr int K = 5; __VA_ARGS__; } break; \
-  }
-
 
 template <typename T>
 static int aggregate_fwd(const T *src, const T *flow, const T *logits, T *out, T *attn_out, int64_t B,
@@ -1106,37 +1071,38 @@ static int aggregate_fwd(const T *src, const T *flow, const T *logits, T *out, T
   if (st != GFLA_OK) return st;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   using A = typename Num<T>::acc;
-  if constexpr (std::is_same<A, float>::value) {
-    // coefficient-table path: needs the caller's workspace (gfla_aggregate_fwd_workspace_bytes)
-    AggStreamPlan pl;
-    if (workspace && agg_stream_wanted(k) && agg_stream_shape_ok(B, C, Hs, Ws, k, true) &&
-        agg_stream_plan(B, C, Hs, Ws, H, W, k, pl)) {
-      const AggStreamGeo &pg = pl.pg;
-      float *table = static_cast<float *>(workspace);
-      const dim3 cgrid((unsigned)ceil_div(pg.ntile, kAggCoefThreads / 64), (unsigned)B);
-      GFLA_AGG_ODD_K_SWITCH(
-          k, agg_coef_kernel<T, K><<<cgrid, dim3(kAggCoefThreads), 0, stream>>>(flow, logits, attn_out, table, (int)Hs, (int)Ws,
-                                                                               (int)H, (int)W, sm, pg.tw_log2, pg.ntile);
-          GFLA_AGG_CHT_SWITCH(pg.CH, launch_lds(agg_fwd_stream_kernel<T, K, CHT>, dim3((unsigned)pl.padded), dim3(pg.threads),
-                                                pg.lds, stream, src, flow, logits, (const float *)table, out, (int)C, (int)Hs,
-                                                (int)Ws, (int)H, (int)W, sm, pg.CH, pg.CS, pg.nsuper, pg.tgroups, pg.pitch,
-                                                (int)pl.total, pg.tw_log2, pg.ntile)));
-      return launch_status();
+  const AggFwdRoute r = agg_fwd_route((int)sizeof(A), workspace != nullptr, B, C, Hs, Ws, H, W, k);
+  switch (r.path) {
+    case AggFwdPath::kUnsupported: return GFLA_ERR_UNSUPPORTED;
+    case AggFwdPath::kStream:  // coefficient-table path: the table lives in the caller's workspace (gfla_aggregate_fwd_workspace_bytes)
+      if constexpr (std::is_same<A, float>::value) {
+        const AggStreamGeo &pg = r.plan.pg;
+        float *table = static_cast<float *>(workspace);
+        const dim3 cgrid((unsigned)ceil_div(pg.ntile, kAggCoefThreads / 64), (unsigned)B);
+        GFLA_AGG_ODD_K_SWITCH(
+            k, agg_coef_kernel<T, K><<<cgrid, dim3(kAggCoefThreads), 0, stream>>>(flow, logits, attn_out, table, (int)Hs, (int)Ws,
+                                                                                 (int)H, (int)W, sm, pg.tw_log2, pg.ntile);
+            GFLA_AGG_CHT_SWITCH(pg.CH, launch_lds(agg_fwd_stream_kernel<T, K, CHT>, dim3((unsigned)r.plan.padded), dim3(pg.threads),
+                                                  pg.lds, stream, src, flow, logits, (const float *)table, out, (int)C, (int)Hs,
+                                                  (int)Ws, (int)H, (int)W, sm, pg.CH, pg.CS, pg.nsuper, pg.tgroups, pg.pitch,
+                                                  (int)r.plan.total, pg.tw_log2, pg.ntile)));
+      }
+      break;
+    case AggFwdPath::kLds: {
+      const PlaneGeo &pg = r.lds;
+      GFLA_K_SWITCH(K, 1, 5, k, launch_lds(agg_fwd_lds_kernel<T, K>, dim3((unsigned)plane_blocks(B, pg)), dim3(kLdsThreads),
+                                           pg.lds_bytes, stream, src, flow, logits, out, attn_out, (int)C, (int)Hs, (int)Ws, (int)H,
+                                           (int)W, sm, pg.G, pg.ngroups, pg.split));
+      break;
+    }
+    case AggFwdPath::kGlobal: {
+      const Geo &g = r.global;
+      GFLA_K_SWITCH(K, 1, 5, k, agg_fwd_kernel<T, K><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(
+                                    src, flow, logits, out, attn_out, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, sm, g.cpt, g.ncg,
+                                    g.sp_blocks));
+      break;
     }
   }
-  if (tuning(3) != 1) {
-    PlaneGeo pg = plane_geometry(Hs * Ws, sizeof(A), B, C, H * W, true, kAggChunk);
-    if (pg.G > 0) {
-      const int64_t blocks = B * pg.ngroups * pg.split;
-      if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-      GFLA_K_SWITCH(k, launch_lds(agg_fwd_lds_kernel<T, K>, dim3((unsigned)blocks), dim3(kLdsThreads), pg.lds_bytes, stream,
-                           src, flow, logits, out, attn_out, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, sm, pg.G, pg.ngroups, pg.split));
-      return launch_status();
-    }
-  }
-  AggGeo g = agg_geometry(B, C, H, W, 32, 4 * kNumCU * kWavesPerCU);
-  if (g.blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-  GFLA_K_SWITCH(k, agg_fwd_kernel<T, K><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(src, flow, logits, out, attn_out, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, sm, g.cpt, g.ncg, g.sp_blocks));
   return launch_status();
 }
 
@@ -1145,47 +1111,41 @@ template <typename T>
 static int launch_agg_ga(const T *src, const T *flow, const T *attn, const T *gout, typename Num<T>::acc *glogits,
                          typename Num<T>::acc *gflow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k, int sm, hipStream_t stream) {
   using A = typename Num<T>::acc;
-  bool launched = false;
-  if constexpr (std::is_same<A, float>::value) {
-    // streaming kernel (interleaved planes, paired reads); no coefficient pass here, so no bound on B
-    AggStreamPlan pl;
-    if (agg_stream_wanted(k) && agg_stream_shape_ok(B, C, Hs, Ws, k, false) && agg_stream_plan(B, C, Hs, Ws, H, W, k, pl)) {
-      const AggStreamGeo &pg = pl.pg;
+  const AggGaRoute r = agg_ga_route((int)sizeof(A), B, C, Hs, Ws, H, W, k);
+  if (r.path == AggGaPath::kUnsupported) return GFLA_ERR_UNSUPPORTED;
+  if (r.path == AggGaPath::kStream) {  // streaming kernel (interleaved planes, paired reads)
+    if constexpr (std::is_same<A, float>::value) {
+      const AggStreamGeo &pg = r.plan.pg;
       GFLA_AGG_ODD_K_SWITCH(
-          k, GFLA_AGG_CHT_SWITCH(pg.CH, launch_lds(agg_ga_stream_kernel<T, K, 0, CHT>, dim3((unsigned)pl.padded), dim3(pg.threads),
+          k, GFLA_AGG_CHT_SWITCH(pg.CH, launch_lds(agg_ga_stream_kernel<T, K, 0, CHT>, dim3((unsigned)r.plan.padded), dim3(pg.threads),
                                                    pg.lds, stream, src, flow, gout, (float *)glogits,
                                                    gflow ? attn : (const T *)nullptr, (float *)gflow, (int)C, (int)Hs, (int)Ws,
-                                                   (int)H, (int)W, pg.CH, pg.CS, pg.nsuper, pg.tgroups, pg.pitch, (int)pl.total,
+                                                   (int)H, (int)W, pg.CH, pg.CS, pg.nsuper, pg.tgroups, pg.pitch, (int)r.plan.total,
                                                    pg.tw_log2, pg.ntile)));
-      launched = true;
     }
-  }
-  if (!launched) {
-    const int threads = 512;
-    const int64_t ntiles = ceil_div(H * W, threads);
-    int64_t G = kLdsBudget / (Hs * Ws * (int64_t)sizeof(A));
-    if (G < 1) return GFLA_ERR_UNSUPPORTED;
-    if (G > C) G = C;
-    int64_t nsuper = 1;  // split the channels until the launch has >= 4 workgroups per CU
-    while (B * ntiles * nsuper < 4 * kNumCU && nsuper * 2 * G <= C) nsuper *= 2;
-    const int64_t CS = ceil_div(C, nsuper);
-    nsuper = ceil_div(C, CS);
-    if (G > CS) G = CS;
-    const int64_t blocks = B * nsuper * ntiles;
-    if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-    const unsigned lds = (unsigned)(G * Hs * Ws * sizeof(A));
-    const int64_t padded = ceil_div(blocks, kNumXCD) * kNumXCD;  // the XCD remap needs a multiple of 8
-    GFLA_K_SWITCH(k, agg_ga_lds_kernel<T, K><<<dim3((unsigned)padded), dim3(threads), lds, stream>>>(
-                         src, flow, gout, glogits, gflow ? attn : nullptr, gflow, (int)C, (int)Hs, (int)Ws, (int)H, (int)W,
-                         (int)G, (int)nsuper, (int)CS, (int)ntiles, (int)blocks));
+  } else {
+    GFLA_K_SWITCH(K, 1, 5, k, agg_ga_lds_kernel<T, K><<<dim3((unsigned)r.padded), dim3(512), r.lds_bytes, stream>>>(
+                                  src, flow, gout, glogits, gflow ? attn : nullptr, gflow, (int)C, (int)Hs, (int)Ws, (int)H, (int)W,
+                                  r.G, r.nsuper, r.CS, r.ntiles, (int)r.blocks));
   }
   int st = launch_status();
   if (st == GFLA_OK && sm && glogits) {
     const int64_t n = B * H * W;
-    GFLA_K_SWITCH(k, agg_softmax_bwd_kernel<T, K><<<dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, stream>>>(
-                         attn, glogits, n, (int)(H * W)));
+    GFLA_K_SWITCH(K, 1, 5, k, agg_softmax_bwd_kernel<T, K><<<dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, stream>>>(
+                                  attn, glogits, n, (int)(H * W)));
     st = launch_status();
   }
+  return st;
+}
+
+// be_bwd_lds_kernel in the attention-factored form on the planes of `g`: grad_source [+ grad_flow]
+template <typename T>
+static int launch_agg_scatter(const PlaneGeo &g, const T *src, const T *flow, const T *attn, const T *gout, T *gsrc,
+                              typename Num<T>::acc *gflow, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k,
+                              hipStream_t stream, const unsigned *skip_stat = nullptr, unsigned skip_limit = 0) {
+  int st = GFLA_OK;
+  GFLA_K_SWITCH(K, 1, 5, k, st = launch_be_bwd_lds<T, K>(kGoutAttn, g, src, flow, gout, attn, gsrc, gflow, B, C, Hs, Ws, H, W, stream,
+                                                         0, 0, (const T *)nullptr, skip_stat, skip_limit));
   return st;
 }
 
@@ -1201,51 +1161,45 @@ static int aggregate_bwd(const T *src, const T *flow, const T *attn, const T *go
   if (!gsrc && !gflow && !glogits) return GFLA_OK;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   using A = typename Num<T>::acc;
-  const bool planes_fit = Hs * Ws * (int64_t)sizeof(A) <= kLdsBudget;
+  const AggBwdRoute r = agg_bwd_route((int)sizeof(T), (int)sizeof(A), gsrc != nullptr, gflow != nullptr, glogits != nullptr,
+                                      workspace != nullptr, B, C, Hs, Ws, H, W, k);
   if constexpr (std::is_same<T, float>::value) {
-    // d/d source as a block-sparse product on the matrix cores (patch_mfma.hip); d/d flow then comes out of the
-    // d/d a_ij pass, which holds the patch sums it needs
-    if (gsrc && workspace && tuning(3) != 1 && (planes_fit || (!gflow && !glogits))) {
-      // the LDS-atomic kernel is the device-side fallback for flows that spread the patches too far
-      const bool lds_fallback = Hs * Ws * (int64_t)(sizeof(lds_acc_t) + sizeof(A)) <= kLdsBudget;
+    if (r.product) {
+      if (r.lds_fallback && r.fallback.G == 0) return GFLA_ERR_UNSUPPORTED;
       const unsigned *skip_stat = nullptr;
       unsigned skip_limit = 0;
-      st = agg_source_bwd_mfma(flow, attn, gout, gsrc, workspace, B, C, Hs, Ws, H, W, k, 1, lds_fallback ? 1 : 0, &skip_stat,
+      st = agg_source_bwd_mfma(flow, attn, gout, gsrc, workspace, B, C, Hs, Ws, H, W, k, 1, r.lds_fallback ? 1 : 0, &skip_stat,
                                &skip_limit, stream);
       if (st == GFLA_OK) {
-        if (lds_fallback && skip_limit != 0xffffffffu) {
-          bool done = false;
-          GFLA_K_SWITCH(k, st = launch_be_bwd_lds<T, K>(kGoutAttn, src, flow, gout, attn, gsrc, (A *)nullptr, B, C, Hs, Ws, H, W,
-                                                        stream, &done, 0, 0, (const T *)nullptr, skip_stat, skip_limit));
+        if (r.lds_fallback && skip_limit != 0xffffffffu) {
+          st = launch_agg_scatter<T>(r.fallback, src, flow, attn, gout, gsrc, (A *)nullptr, B, C, Hs, Ws, H, W, k, stream, skip_stat,
+                                     skip_limit);
           if (st != GFLA_OK) return st;
-          if (!done) return GFLA_ERR_UNSUPPORTED;
         }
         if (gflow || glogits) st = launch_agg_ga<T>(src, flow, attn, gout, glogits, gflow, B, C, Hs, Ws, H, W, k, sm, stream);
         return st;
       }
-      if (st != GFLA_ERR_UNSUPPORTED) return st;
+      if (st != GFLA_ERR_UNSUPPORTED) return st;  // (the product declined: the route's kernels)
     }
   }
-  // bf16 storage exists for the planes-in-LDS kernels only: the forced-global test knob (key 3) does not apply to it
-  if ((tuning(3) != 1 || sizeof(T) == 2) && Hs * Ws * (int64_t)(sizeof(lds_acc_t) + sizeof(A)) <= kLdsBudget) {
-    // (1) grad_source + grad_flow: block_extractor backward of the factored gradient a_ij*g_c/k^2
-    if (gsrc || gflow) {
-      bool done = false;
-      GFLA_K_SWITCH(k, st = launch_be_bwd_lds<T, K>(kGoutAttn, src, flow, gout, attn, gsrc, gflow, B, C, Hs, Ws, H, W, stream, &done));
-      if (st != GFLA_OK) return st;
-      if (!done) return GFLA_ERR_UNSUPPORTED;
-    }
-    if (glogits) st = launch_agg_ga<T>(src, flow, attn, gout, glogits, (A *)nullptr, B, C, Hs, Ws, H, W, k, sm, stream);
-    return st;
+  switch (r.path) {
+    case AggBwdPath::kUnsupported: return GFLA_ERR_UNSUPPORTED;
+    case AggBwdPath::kLds:
+      st = GFLA_OK;
+      if (gsrc || gflow) st = launch_agg_scatter<T>(r.scatter, src, flow, attn, gout, gsrc, gflow, B, C, Hs, Ws, H, W, k, stream);
+      if (st == GFLA_OK && glogits)
+        st = launch_agg_ga<T>(src, flow, attn, gout, glogits, (A *)nullptr, B, C, Hs, Ws, H, W, k, sm, stream);
+      return st;
+    case AggBwdPath::kGlobal:
+      if constexpr (sizeof(T) != 2) {  // (16-bit storage: the planes-in-LDS kernels only; the route sends none here)
+        const Geo &g = r.global;
+        GFLA_K_SWITCH(K, 1, 5, k, agg_bwd_kernel<T, K><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(
+                                      src, flow, attn, gout, gsrc, gflow, glogits, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, sm, g.cpt,
+                                      g.ncg, g.sp_blocks));
+      }
+      return launch_status();
   }
-  if constexpr (sizeof(T) == 2) {
-    return GFLA_ERR_UNSUPPORTED;  // bf16 / f16 storage: the planes-in-LDS kernels only
-  } else {
-    AggGeo g = agg_geometry(B, C, H, W, 32, 2 * kNumCU * kWavesPerCU);
-    if (g.blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-    GFLA_K_SWITCH(k, agg_bwd_kernel<T, K><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(src, flow, attn, gout, gsrc, gflow, glogits, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, sm, g.cpt, g.ncg, g.sp_blocks));
-    return launch_status();
-  }
+  return st;
 }
 
 // Backward of everything in ExtractorAttn that flows into block_source(source, flow): the gradient of
@@ -1259,33 +1213,23 @@ static int local_attn_source_bwd(const T *src, const T *flow, const T *gunf, con
   if (!src || !flow || (!gunf && !(attn && gout)) || ((attn == nullptr) != (gout == nullptr))) return GFLA_ERR_NULL_POINTER;
   int st = agg_check(B, C, Hs, Ws, H, W, k);
   if (st != GFLA_OK) return st;
-  if (Hs * Ws * (int64_t)(sizeof(lds_acc_t) + sizeof(A)) > kLdsBudget) return GFLA_ERR_UNSUPPORTED;
+  if (!scatter_gather_planes_fit(Hs, Ws, sizeof(A))) return GFLA_ERR_UNSUPPORTED;
   if (!gsrc && !gflow) return GFLA_OK;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const int64_t HW = H * W;
   const int64_t cs = layout == 1 ? B * HW : HW;
   const int64_t bs = layout == 1 ? HW : C * k * k * HW;
   const int mode = gunf ? (attn ? kGoutUnfoldAttn : kGoutUnfold) : kGoutAttn;
-  bool done = false;
-  GFLA_K_SWITCH(k, st = launch_be_bwd_lds<T, K>(mode, src, flow, gunf ? gunf : gout, attn, gsrc, gflow, B, C, Hs, Ws, H, W,
-                                                stream, &done, cs, bs, gout));
-  if (st == GFLA_OK && !done) st = GFLA_ERR_UNSUPPORTED;
+  const PlaneGeo g = whole_plane_bwd_route(mode, sizeof(T), sizeof(A), gsrc != nullptr, gflow != nullptr, B, C, Hs, Ws, H, W, k);
+  if (g.G == 0) return GFLA_ERR_UNSUPPORTED;
+  GFLA_K_SWITCH(K, 1, 5, k, st = launch_be_bwd_lds<T, K>(mode, g, src, flow, gunf ? gunf : gout, attn, gsrc, gflow, B, C, Hs, Ws, H, W,
+                                                         stream, cs, bs, gout));
   return st;
 }
 
 }  // namespace gfla
 
 // ---- extern "C": one definer per GFLA_DECL_* family of include/gfla_hip.h, instantiated per suffix --------------------
-namespace gfla {
-// element type behind an entry point's suffix (16-bit storage crosses the ABI as uint16_t)
-typedef float elem_f32;
-typedef double elem_f64;
-typedef bf16_t elem_bf16;
-typedef f16_t elem_f16;
-template <typename E, typename S>
-static inline auto as(S *p) { return reinterpret_cast<std::conditional_t<std::is_const<S>::value, const E, E> *>(p); }
-}  // namespace gfla
-
 #define GFLA_SHAPE_PARAMS int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W
 #define GFLA_SHAPE_ARGS B, C, Hs, Ws, H, W
 
@@ -1362,14 +1306,5 @@ int gfla_aggregate_fwd_geometry(int64_t B, int64_t C, int64_t Hs, int64_t Ws, in
   const int64_t v[9] = {g.CH, g.CS, g.nsuper, g.tgroups, g.threads, g.pitch, 1 << g.tw_log2, g.ntile, g.lds};
   for (int i = 0; i < 9; ++i) out[i] = v[i];
   return GFLA_OK;
-}
-/* 1 when gfla_local_attn_aggregate_bwd_<storage> takes source planes of Hs x Ws (elem_size 2 = bf16, 4 = f32, 8 = f64).
- * f32 / f64 always do (global-memory kernels behind the planes-in-LDS ones); bf16 storage exists for the planes-in-LDS
- * kernels only: a double accumulator plane + an arithmetic-type source plane per position within the LDS budget (tuning
- * key 10).  The host side asks here instead of duplicating the budget. */
-int gfla_aggregate_bwd_supported(int64_t Hs, int64_t Ws, int elem_size) {
-  if (Hs <= 0 || Ws <= 0 || (elem_size != 2 && elem_size != 4 && elem_size != 8)) return 0;
-  if (elem_size != 2) return 1;
-  return Hs * Ws * (int64_t)(sizeof(gfla::lds_acc_t) + sizeof(float)) <= gfla::lds_budget() ? 1 : 0;
 }
 }

@@ -13,10 +13,9 @@
 #include "gfla_common.h"
 #include <type_traits>
 
-#include "lds_plane.h"
+#include "gs_route.h"
 #include "rs_taps.h"
 #include "patch_mfma.h"
-#include "tile_map.h"
 
 namespace gfla {
 
@@ -866,29 +865,6 @@ __global__ __launch_bounds__(512) void rs_bwd1_tile_kernel(const T *__restrict__
   }
 }
 
-struct Geo {
-  int cpt, ncg, sp_blocks;
-  int64_t blocks;
-};
-static Geo geometry(int64_t B, int64_t C, int64_t H, int64_t W, int max_cpt, int64_t want_waves) {
-  Geo g;
-  g.sp_blocks = (int)ceil_div(H * W, kBlock);
-  int cpt = tuning(1) > 0 ? tuning(1) : pick_channels_per_thread((int64_t)g.sp_blocks * kBlock, C, B, max_cpt, want_waves);
-  if (cpt > C) cpt = (int)C;
-  g.cpt = cpt;
-  g.ncg = (int)ceil_div(C, cpt);
-  g.blocks = (int64_t)g.sp_blocks * g.ncg * B;
-  return g;
-}
-
-// big-plane gathers: channels per thread -- all of them unless that leaves fewer than `want` waves (tuning key 33)
-static int big_cpt(int64_t B, int64_t C, int64_t nsp, int64_t want) {
-  if (tuning(33) > 0) return tuning(33) < C ? tuning(33) : (int)C;
-  int64_t cpt = C;
-  while (cpt > 1 && B * nsp * (kBlock / 64) * ceil_div(C, cpt) < want) cpt = ceil_div(cpt, 2);
-  return (int)cpt;
-}
-
 template <typename T>
 static int check(const void *a, const void *b, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H,
                  int64_t W, int k, int dil) {
@@ -899,13 +875,17 @@ static int check(const void *a, const void *b, int64_t B, int64_t C, int64_t Hi,
   return GFLA_OK;
 }
 
-#define GFLA_KH_SWITCH(KHV, ...) \
-  switch (KHV) {                  \
-    case 1: { constexpr int KH = 1; __VA_ARGS__; } break; \
-    case 2: { constexpr int KH = 2; __VA_ARGS__; } break; \
-    case 3: { constexpr int KH = 3; __VA_ARGS__; } break; \
-    default: { constexpr int KH = 4; __VA_ARGS__; } break; \
-  }
+// rs_lds_kernel<T, KH, MODE, WIN = g.margin >= 0, FIX, TAB> on the planes of `g`
+#define GFLA_RS_LDS(KH_, MODE_, FIX_, TAB_, g, in2_, gout_, outp_, trunc_, skip_stat_, skip_limit_)                                \
+  GFLA_WIN_SWITCH((g).margin, launch_lds(rs_lds_kernel<T, KH_, MODE_, WIN, FIX_, TAB_>, dim3((unsigned)plane_blocks(B, g)),         \
+                                         dim3(kLdsThreads), (g).lds_bytes, stream, in1, in2_, gout_, outp_, (int)C, (int)Hi, (int)Wi, \
+                                         (int)H, (int)W, dil, trunc_, (g).G, (g).ngroups, (g).split, (g).per, (g).margin,          \
+                                         skip_stat_, skip_limit_))
+// rs_gather_tile_kernel<T, KH, MODE> on the tiles of `bg`
+#define GFLA_RS_GATHER_TILES(KH_, MODE_, bg, gout_, outp_)                                                                         \
+  launch_lds(rs_gather_tile_kernel<T, KH_, MODE_>, dim3((unsigned)(bg).nwg), dim3((unsigned)(bg).tg.threads), (bg).lds_bytes,       \
+             stream, in1, in2, gout_, outp_, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, (bg).tg.th, (bg).tg.tw, (bg).tg.ntx,    \
+             (bg).tg.nty, (bg).G, (bg).ngroups, (int)((bg).lds_bytes / sizeof(A)), (bg).nwg, tile_probe_bits())
 
 template <typename T>
 static int resample2d_fwd(const T *in1, const T *in2, T *out, int64_t B, int64_t C, int64_t Hi,
@@ -915,293 +895,185 @@ static int resample2d_fwd(const T *in1, const T *in2, T *out, int64_t B, int64_t
   if (!out) return GFLA_ERR_NULL_POINTER;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   using A = typename Num<T>::acc;
-  if (tuning(6) != 1 && big_plane_regime(B, C, Hi * Wi * (int64_t)sizeof(A), lds_budget())) {
-    // few planes far beyond the LDS budget (BASELINE configs[1]): one tap setup per pixel and chunk of channels, global gathers
-    if (tuning(38) != 1 && sizeof(T) >= 4 && Hi * Wi <= 0x3fffffffLL) {   // planes staged into bounding-box windows
-      const BigGeo bg = big_geometry(2, B, C, H, W, (k - 1) * dil + 1, (int)sizeof(A));
-      const TileGeo tg = bg.tg;
-      const int G = bg.G;
-      const int64_t ngroups = bg.ngroups, nwg = bg.nwg;
-      if (nwg <= 0x7fffffffLL) {
-        const unsigned lds_bytes = bg.lds_bytes;
-        GFLA_KH_SWITCH(k / 2, launch_lds(rs_gather_tile_kernel<T, KH, 0>, dim3((unsigned)nwg), dim3((unsigned)tg.threads), lds_bytes, stream, in1, in2, static_cast<const T *>(nullptr), out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, tg.th, tg.tw, tg.ntx, tg.nty, G, (int)ngroups, (int)(lds_bytes / sizeof(A)), nwg, tile_probe_bits()));
-        note_path(GFLA_PATH_RS_FWD_BIG);
-        return launch_status();
-      }
-    }
-    const int64_t nsp = ceil_div(H * W, kBlock);
-    const int cpt = big_cpt(B, C, nsp, 20 * kNumCU);
-    const int64_t ncg = ceil_div(C, cpt), nwg = B * nsp * ncg;
-    if (nwg <= 0x7fffffffLL) {
-      GFLA_KH_SWITCH(k / 2, rs_fwd_big_kernel<T, KH><<<dim3((unsigned)nwg), dim3(kBlock), 0, stream>>>(in1, in2, out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, cpt, (int)ncg, (int)nsp, nwg));
+  const RsFwdRoute r = rs_fwd_route((int)sizeof(T), (int)sizeof(A), B, C, Hi, Wi, H, W, k, dil);
+  switch (r.path) {
+    case RsFwdPath::kUnsupported: return GFLA_ERR_UNSUPPORTED;
+    case RsFwdPath::kBigTile:
+      GFLA_K_SWITCH(KH, 1, 4, k / 2, GFLA_RS_GATHER_TILES(KH, 0, r.big, static_cast<const T *>(nullptr), out));
       note_path(GFLA_PATH_RS_FWD_BIG);
-      return launch_status();
+      break;
+    case RsFwdPath::kBigGather: {
+      const BigGatherGeo &g = r.gather;
+      GFLA_K_SWITCH(KH, 1, 4, k / 2, rs_fwd_big_kernel<T, KH><<<dim3((unsigned)g.nwg), dim3(kBlock), 0, stream>>>(
+                                         in1, in2, out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, g.cpt, g.ncg, g.nsp, g.nwg));
+      note_path(GFLA_PATH_RS_FWD_BIG);
+      break;
+    }
+    case RsFwdPath::kLds:
+      GFLA_K_SWITCH(KH, 1, 4, k / 2, GFLA_RS_LDS(KH, 0, false, false, r.lds, in2, nullptr, out, 0, nullptr, 0u));
+      break;
+    case RsFwdPath::kGlobal: {
+      const Geo &g = r.global;
+      GFLA_K_SWITCH(KH, 1, 4, k / 2, rs_fwd_kernel<T, KH><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(
+                                         in1, in2, out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, g.cpt, g.ncg, g.sp_blocks));
+      break;
     }
   }
-  if (tuning(6) != 1) {
-    PlaneGeo pg = rs_gather_geometry(sizeof(A), B, C, Hi, Wi, H, W, k, dil, 1);
-    if (pg.G > 0) {
-      const int64_t blocks = B * pg.ngroups * pg.split;
-      if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-      GFLA_KH_SWITCH(k / 2, if (pg.margin < 0) launch_lds(rs_lds_kernel<T, KH, 0, false>, dim3((unsigned)blocks), dim3(kLdsThreads), pg.lds_bytes, stream, in1, in2, nullptr, out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, 0, pg.G, pg.ngroups, pg.split, pg.per, pg.margin, nullptr, 0u);
-                                else launch_lds(rs_lds_kernel<T, KH, 0, true>, dim3((unsigned)blocks), dim3(kLdsThreads), pg.lds_bytes, stream, in1, in2, nullptr, out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, 0, pg.G, pg.ngroups, pg.split, pg.per, pg.margin, nullptr, 0u));
-      return launch_status();
-    }
-  }
-  Geo g = geometry(B, C, H, W, 16, 4 * kNumCU * kWavesPerCU);
-  if (g.blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-  GFLA_KH_SWITCH(k / 2, rs_fwd_kernel<T, KH><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(in1, in2, out, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, g.cpt, g.ncg, g.sp_blocks));
   return launch_status();
 }
 
+// workspace (gfla_scatter_workspace_bytes(B, H, W, k*k), may be NULL; f32 only): d/d input1 runs as a block-sparse product on
+// the matrix cores (patch_mfma.hip) where the route offers it, and the scatter kernel reads its per-pixel setup from tap
+// records.  The route (gs_route.h: rs_bwd_route) holds every decision, the zero-fill rule included.
 template <typename T>
 static int resample2d_bwd(const T *in1, const T *in2, const T *gout, T *gin1, typename Num<T>::acc *gin2, int64_t B,
                           int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int dil,
-                          int trunc, gfla_stream_t stream_, const unsigned *skip_stat = nullptr,
-                          unsigned skip_limit = 0, void *tap_records = nullptr) {
+                          int trunc, gfla_stream_t stream_, void *workspace = nullptr) {
   int st = check<T>(in1, in2, B, C, Hi, Wi, H, W, k, dil);
   if (st != GFLA_OK) return st;
   if (!gout) return GFLA_ERR_NULL_POINTER;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   using A = typename Num<T>::acc;
-  constexpr bool kBf16 = sizeof(T) == 2;
-  if constexpr (!kBf16) {
-    // few planes far beyond the LDS budget (BASELINE configs[1]; tile_map.h).  Not behind the matrix-core product's
-    // device-side switch (skip_stat): the _ws entry point does not try the product in this regime.
-    if (tuning(6) != 1 && !skip_stat && Hi * Wi <= 0x3fffffffLL &&
-        big_plane_regime(B, C, Hi * Wi * (int64_t)sizeof(lds_acc_t), lds_budget())) {
-      if (gin1) {
-        if (trunc & 2) {  // the tiles accumulate with atomics: zero-fill here
-          if (hipMemsetAsync(gin1, 0, (size_t)(B * C * Hi * Wi) * sizeof(T), stream) != hipSuccess) return GFLA_ERR_LAUNCH;
-          trunc &= ~2;
+  const auto route = [&](bool product_allowed) {
+    return rs_bwd_route((int)sizeof(T), (int)sizeof(A), B, C, Hi, Wi, H, W, k, dil, trunc, gin1 != nullptr, gin2 != nullptr,
+                        workspace != nullptr, product_allowed);
+  };
+  // flag word `trunc`: bit 0 = the reference's int() truncation quirk; bit 1 = grad_in1 arrives UNINITIALISED and is to be
+  // overwritten
+  const auto zero_fill = [&]() {
+    trunc &= ~2;
+    return hipMemsetAsync(gin1, 0, (size_t)(B * C * Hi * Wi) * sizeof(T), stream) == hipSuccess;
+  };
+  RsBwdRoute r = route(true);
+  if (r.path == RsBwdPath::kUnsupported && !r.product) return GFLA_ERR_UNSUPPORTED;
+  if (r.zero_fill && !zero_fill()) return GFLA_ERR_LAUNCH;
+  void *tap_records = nullptr;
+  const unsigned *skip_stat = nullptr;  // the product's device-side switch: the scatter kernel behind it returns at once
+  unsigned skip_limit = 0;              // where the product did the work
+  if constexpr (std::is_same<T, float>::value) {
+    if (workspace && gin1) tap_records = static_cast<unsigned char *>(workspace) + pm_table_bytes(B, H, W, k * k);
+    if (r.product) {
+      st = rs_input1_bwd_mfma(in2, gout, gin1, workspace, B, C, Hi, Wi, H, W, k, trunc & 1, (trunc & 2) ? 0 : 1,
+                              r.lds_fallback ? 1 : 0, &skip_stat, &skip_limit, stream);
+      if (st == GFLA_OK) {
+        if (!r.lds_fallback || skip_limit == 0xffffffffu) {  // done unconditionally: what is left is d/d input2 alone
+          gin1 = nullptr, skip_stat = nullptr;
+          if (!gin2) return GFLA_OK;
+          r = route(false);
         }
-        const BigGeo bg = big_geometry(3, B, C, H, W, (k - 1) * dil + 1, 8);
-        const TileGeo tg = bg.tg;
-        const int G = bg.G;
-        const int64_t ngroups = bg.ngroups, nwg = bg.nwg;
-        if (nwg > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-        const unsigned lds_bytes = bg.lds_bytes;
-        constexpr bool FIX = std::is_same<A, float>::value;
-        GFLA_KH_SWITCH(k / 2, launch_lds(rs_bwd1_tile_kernel<T, KH, FIX>, dim3((unsigned)nwg), dim3((unsigned)tg.threads), lds_bytes, stream, in2, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, tg.th, tg.tw, tg.ntx, tg.nty, G, (int)ngroups, (int)(lds_bytes / 8), nwg, tile_probe_bits()));
-        note_path(GFLA_PATH_RS_BWD1_TILE);
+      } else if (st != GFLA_ERR_UNSUPPORTED) {
+        return st;
+      } else {  // the product declined
+        skip_stat = nullptr;
+        r = route(false);
+        if (r.path == RsBwdPath::kUnsupported) return GFLA_ERR_UNSUPPORTED;
+        if (r.zero_fill && !zero_fill()) return GFLA_ERR_LAUNCH;
+      }
+    }
+  }
+  st = GFLA_OK;
+  switch (r.path) {
+    case RsBwdPath::kUnsupported: return GFLA_ERR_UNSUPPORTED;
+    case RsBwdPath::kBig:
+      if constexpr (sizeof(T) >= 4) {
+        if (gin1) {
+          constexpr bool FIX = std::is_same<A, float>::value;
+          const BigGeo &bg = r.big1;
+          GFLA_K_SWITCH(KH, 1, 4, k / 2, launch_lds(rs_bwd1_tile_kernel<T, KH, FIX>, dim3((unsigned)bg.nwg), dim3((unsigned)bg.tg.threads), bg.lds_bytes, stream, in2, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, bg.tg.th, bg.tg.tw, bg.tg.ntx, bg.tg.nty, bg.G, bg.ngroups, (int)(bg.lds_bytes / 8), bg.nwg, tile_probe_bits()));
+          note_path(GFLA_PATH_RS_BWD1_TILE);
+          st = launch_status();
+          if (st != GFLA_OK) return st;
+        }
+        if (gin2) {
+          const BigGatherGeo &g = r.gather;
+          if (r.gather_tiles) GFLA_K_SWITCH(KH, 1, 4, k / 2, GFLA_RS_GATHER_TILES(KH, 2, r.big2, gout, gin2));
+          else GFLA_K_SWITCH(KH, 1, 4, k / 2, rs_bwd2_big_kernel<T, KH><<<dim3((unsigned)g.nwg), dim3(kBlock), 0, stream>>>(in1, in2, gout, gin2, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, g.cpt, g.ncg, g.nsp, g.nwg));
+          note_path(GFLA_PATH_RS_BWD2_BIG);
+          st = launch_status();
+        }
+      }
+      return st;
+    case RsBwdPath::kLds:
+      if (gin1) {
+        if constexpr (std::is_same<T, float>::value) {
+          if (r.tab) {  // the per-pixel setup runs once (rs_tap_table_kernel)
+            RsTapRec *tab = static_cast<RsTapRec *>(tap_records);
+            rs_tap_table_kernel<<<dim3((unsigned)ceil_div(H * W, 256), (unsigned)B), 256, 0, stream>>>(
+                in2, tab, (int)(H * W), (int)W, (int)Hi, (int)Wi, dil, trunc, skip_stat, skip_limit);
+            GFLA_RS_LDS(2, 1, true, true, r.lds1, reinterpret_cast<const float *>(tab), gout, gin1, trunc, skip_stat, skip_limit);
+          } else if (r.fix) {
+            GFLA_K_SWITCH(KH, 1, 4, k / 2, GFLA_RS_LDS(KH, 1, true, false, r.lds1, in2, gout, gin1, trunc, skip_stat, skip_limit));
+          } else {
+            GFLA_K_SWITCH(KH, 1, 4, k / 2, GFLA_RS_LDS(KH, 1, false, false, r.lds1, in2, gout, gin1, trunc, skip_stat, skip_limit));
+          }
+        } else {  // fixed-point planes for float arithmetic, double planes for f64
+          GFLA_K_SWITCH(KH, 1, 4, k / 2, GFLA_RS_LDS(KH, 1, (std::is_same<A, float>::value), false, r.lds1, in2, gout, gin1, trunc, skip_stat, skip_limit));
+        }
         st = launch_status();
         if (st != GFLA_OK) return st;
       }
-      if (gin2 && tuning(38) != 1) {
-        const BigGeo bg = big_geometry(4, B, C, H, W, (k - 1) * dil + 1, (int)sizeof(A));
-        const TileGeo tg = bg.tg;
-        const int G = bg.G;
-        const int64_t ngroups = bg.ngroups, nwg = bg.nwg;
-        if (nwg > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-        const unsigned lds_bytes = bg.lds_bytes;
-        GFLA_KH_SWITCH(k / 2, launch_lds(rs_gather_tile_kernel<T, KH, 2>, dim3((unsigned)nwg), dim3((unsigned)tg.threads), lds_bytes, stream, in1, in2, gout, gin2, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, tg.th, tg.tw, tg.ntx, tg.nty, G, (int)ngroups, (int)(lds_bytes / sizeof(A)), nwg, tile_probe_bits()));
-        note_path(GFLA_PATH_RS_BWD2_BIG);
-        st = launch_status();
-      } else if (gin2) {
-        const int64_t nsp = ceil_div(H * W, kBlock);
-        const int cpt = big_cpt(B, C, nsp, 20 * kNumCU);
-        const int64_t ncg = ceil_div(C, cpt), nwg = B * nsp * ncg;
-        if (nwg > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-        GFLA_KH_SWITCH(k / 2, rs_bwd2_big_kernel<T, KH><<<dim3((unsigned)nwg), dim3(kBlock), 0, stream>>>(in1, in2, gout, gin2, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, cpt, (int)ncg, (int)nsp, nwg));
-        note_path(GFLA_PATH_RS_BWD2_BIG);
+      if (gin2) {
+        if constexpr (std::is_same<A, float>::value) {
+          if (r.stream) return rs_bwd2_stream<T>(r.plan, in1, in2, gout, gin2, C, Hi, Wi, H, W, stream);
+        }
+        GFLA_K_SWITCH(KH, 1, 4, k / 2, GFLA_RS_LDS(KH, 2, false, false, r.lds2, in2, gout, gin2, trunc, nullptr, 0u));
         st = launch_status();
       }
       return st;
-    }
-  }
-  // double scatter planes.  bf16 storage: whole planes, one owner each (the flush is a plain read-modify-write)
-  PlaneGeo pg1 = rs_scatter_geometry((int)sizeof(T), B, C, Hi, Wi, H, W, k, dil);
-  PlaneGeo pg2 = rs_gather_geometry(sizeof(A), B, C, Hi, Wi, H, W, k, dil, 0);            // gather planes
-  // flag word `trunc`: bit 0 = the reference's int() truncation quirk; bit 1 = grad_in1 arrives UNINITIALISED and is to be
-  // overwritten -- honoured by the kernels where every element has exactly one writer, zero-filled here otherwise
-  const bool lds_path = (tuning(6) != 1 || kBf16) && pg1.G > 0 && pg2.G > 0;
-  if (gin1 && (trunc & 2) && !(lds_path && pg1.split == 1 && pg1.margin < 0) && !skip_stat) {
-    if (hipMemsetAsync(gin1, 0, (size_t)(B * C * Hi * Wi) * sizeof(T), stream) != hipSuccess) return GFLA_ERR_LAUNCH;
-    trunc &= ~2;
-  }
-  if (lds_path) {
-    if (gin1) {
-      const int64_t blocks = B * pg1.ngroups * pg1.split;
-      if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-#define GFLA_RS_SCATTER(FIX_)                                                                                                                                       \
-      GFLA_KH_SWITCH(k / 2, if (pg1.margin < 0) launch_lds(rs_lds_kernel<T, KH, 1, false, FIX_>, dim3((unsigned)blocks), dim3(kLdsThreads), pg1.lds_bytes, stream, in1, in2, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, pg1.G, pg1.ngroups, pg1.split, pg1.per, pg1.margin, skip_stat, skip_limit); \
-                                else launch_lds(rs_lds_kernel<T, KH, 1, true, FIX_>, dim3((unsigned)blocks), dim3(kLdsThreads), pg1.lds_bytes, stream, in1, in2, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, pg1.G, pg1.ngroups, pg1.split, pg1.per, pg1.margin, skip_stat, skip_limit))
-      // fixed-point planes (lds_plane.h); tuning key 23 = 1: round 1's double planes
-      if constexpr (std::is_same<T, float>::value) {
-        // scratch given, kernel_size 4 / 5: the per-pixel setup runs once (rs_tap_table_kernel); tuning key 23 = 2: never
-        if (tap_records && k / 2 == 2 && Hi <= 65535 && Wi <= 65535 && tuning(23) == 0) {
-          RsTapRec *tab = static_cast<RsTapRec *>(tap_records);
-          rs_tap_table_kernel<<<dim3((unsigned)ceil_div(H * W, 256), (unsigned)B), 256, 0, stream>>>(
-              in2, tab, (int)(H * W), (int)W, (int)Hi, (int)Wi, dil, trunc, skip_stat, skip_limit);
-          const float *recs = reinterpret_cast<const float *>(tab);
-          if (pg1.margin < 0)
-            launch_lds(rs_lds_kernel<T, 2, 1, false, true, true>, dim3((unsigned)blocks), dim3(kLdsThreads), pg1.lds_bytes, stream, in1, recs, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, pg1.G, pg1.ngroups, pg1.split, pg1.per, pg1.margin, skip_stat, skip_limit);
-          else
-            launch_lds(rs_lds_kernel<T, 2, 1, true, true, true>, dim3((unsigned)blocks), dim3(kLdsThreads), pg1.lds_bytes, stream, in1, recs, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, pg1.G, pg1.ngroups, pg1.split, pg1.per, pg1.margin, skip_stat, skip_limit);
-        } else if (tuning(23) == 1) {
-          GFLA_RS_SCATTER(false);
-        } else {
-          GFLA_RS_SCATTER(true);
+    case RsBwdPath::kGlobal:
+      if constexpr (sizeof(T) != 2) {  // (16-bit storage: the planes-in-LDS kernels only; the route sends none here)
+        if (gin1) {
+          const Geo &g = r.global1;
+          GFLA_K_SWITCH(KH, 1, 4, k / 2, rs_bwd1_kernel<T, KH><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(in2, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, g.cpt, g.ncg, g.sp_blocks));
+          st = launch_status();
+          if (st != GFLA_OK) return st;
         }
-      } else if constexpr (std::is_same<A, float>::value) {
-        GFLA_RS_SCATTER(true);
-      } else {
-        GFLA_RS_SCATTER(false);
-      }
-#undef GFLA_RS_SCATTER
-      st = launch_status();
-      if (st != GFLA_OK) return st;
-    }
-    if (gin2) {
-      if constexpr (std::is_same<A, float>::value) {
-        // kernel_size 4, dilation 1: the aggregation's streaming d/d logits kernel with resample2d's epilogue
-        // (rs_taps.h); tuning key 22 = 1: rs_lds_kernel<MODE 2>
-        if (k == 4 && dil == 1 && tuning(22) != 1) {
-          st = rs_bwd2_stream<T>(in1, in2, gout, gin2, B, C, Hi, Wi, H, W, stream);
-          if (st != GFLA_ERR_UNSUPPORTED) return st;
+        if (gin2) {
+          const Geo &g = r.global2;
+          GFLA_K_SWITCH(KH, 1, 4, k / 2, rs_bwd2_kernel<T, KH><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(in1, in2, gout, gin2, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, g.cpt, g.ncg, g.sp_blocks));
+          st = launch_status();
         }
       }
-      const int64_t blocks = B * pg2.ngroups * pg2.split;
-      if (blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-      GFLA_KH_SWITCH(k / 2, if (pg2.margin < 0) launch_lds(rs_lds_kernel<T, KH, 2, false>, dim3((unsigned)blocks), dim3(kLdsThreads), pg2.lds_bytes, stream, in1, in2, gout, gin2, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, pg2.G, pg2.ngroups, pg2.split, pg2.per, pg2.margin, nullptr, 0u);
-                                else launch_lds(rs_lds_kernel<T, KH, 2, true>, dim3((unsigned)blocks), dim3(kLdsThreads), pg2.lds_bytes, stream, in1, in2, gout, gin2, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, pg2.G, pg2.ngroups, pg2.split, pg2.per, pg2.margin, nullptr, 0u));
-      st = launch_status();
-    }
-    return st;
-  }
-  if constexpr (kBf16) {
-    return GFLA_ERR_UNSUPPORTED;  // bf16 storage: the planes-in-LDS kernels only
-  } else {
-  if (gin1) {
-    Geo g = geometry(B, C, H, W, 16, 4 * kNumCU * kWavesPerCU);
-    if (g.blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-    GFLA_KH_SWITCH(k / 2, rs_bwd1_kernel<T, KH><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(in2, gout, gin1, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, trunc, g.cpt, g.ncg, g.sp_blocks));
-    st = launch_status();
-    if (st != GFLA_OK) return st;
-  }
-  if (gin2) {
-    Geo g = geometry(B, C, H, W, 512, 2 * kNumCU * kWavesPerCU);
-    if (g.blocks > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-    GFLA_KH_SWITCH(k / 2, rs_bwd2_kernel<T, KH><<<dim3((unsigned)g.blocks), dim3(kBlock), 0, stream>>>(in1, in2, gout, gin2, (int)C, (int)Hi, (int)Wi, (int)H, (int)W, dil, g.cpt, g.ncg, g.sp_blocks));
-    st = launch_status();
+      return st;
   }
   return st;
-  }
 }
+#undef GFLA_RS_LDS
+#undef GFLA_RS_GATHER_TILES
 
 }  // namespace gfla
 
-using gfla::bf16_t;
-using gfla::f16_t;
+// ---- extern "C": one definer per GFLA_DECL_* family of include/gfla_hip.h, instantiated per suffix --------------------
+#define GFLA_RS_SHAPE_PARAMS int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int d
+#define GFLA_RS_SHAPE_ARGS B, C, Hi, Wi, H, W, k, d
+
+#define GFLA_DEF_RESAMPLE_FWD(SFX, T)                                                                              \
+  int gfla_resample2d_fwd_##SFX(const T *a, const T *b, T *o, GFLA_RS_SHAPE_PARAMS, gfla_stream_t st) {            \
+    using E = gfla::elem_##SFX;                                                                                    \
+    return gfla::resample2d_fwd<E>(gfla::as<E>(a), gfla::as<E>(b), gfla::as<E>(o), GFLA_RS_SHAPE_ARGS, st);        \
+  }
+// R = type of grad_in2 (B,3,H,W), a reduction over the channels: T for f32 / f64 (RESAMPLE_BWD), float for 16-bit storage
+// (this file's part of BWD16)
+#define GFLA_DEF_RESAMPLE_BWD(SFX, T, R)                                                                           \
+  int gfla_resample2d_bwd_##SFX(const T *a, const T *b, const T *go, T *g1, R *g2, GFLA_RS_SHAPE_PARAMS, int trunc, \
+                                gfla_stream_t st) {                                                                \
+    using E = gfla::elem_##SFX;                                                                                    \
+    return gfla::resample2d_bwd<E>(gfla::as<E>(a), gfla::as<E>(b), gfla::as<E>(go), gfla::as<E>(g1), g2,           \
+                                   GFLA_RS_SHAPE_ARGS, trunc, st);                                                 \
+  }
 
 extern "C" {
-int gfla_resample2d_fwd_f32(const float *a, const float *b, float *o, int64_t B, int64_t C, int64_t Hi,
-                            int64_t Wi, int64_t H, int64_t W, int k, int d, gfla_stream_t st) {
-  return gfla::resample2d_fwd<float>(a, b, o, B, C, Hi, Wi, H, W, k, d, st);
-}
-int gfla_resample2d_fwd_f64(const double *a, const double *b, double *o, int64_t B, int64_t C,
-                            int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int d,
-                            gfla_stream_t st) {
-  return gfla::resample2d_fwd<double>(a, b, o, B, C, Hi, Wi, H, W, k, d, st);
-}
-int gfla_resample2d_fwd_bf16(const uint16_t *a, const uint16_t *b, uint16_t *o, int64_t B, int64_t C,
-                             int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int d,
-                             gfla_stream_t st) {
-  return gfla::resample2d_fwd<bf16_t>(reinterpret_cast<const bf16_t *>(a),
-                                      reinterpret_cast<const bf16_t *>(b), reinterpret_cast<bf16_t *>(o),
-                                      B, C, Hi, Wi, H, W, k, d, st);
-}
-int gfla_resample2d_bwd_f32(const float *a, const float *b, const float *go, float *g1, float *g2,
-                            int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k,
-                            int d, int trunc, gfla_stream_t st) {
-  return gfla::resample2d_bwd<float>(a, b, go, g1, g2, B, C, Hi, Wi, H, W, k, d, trunc, st);
-}
-/* As gfla_resample2d_bwd_f32 with scratch (gfla_scatter_workspace_bytes(B, H, W, k*k), may be NULL): d/d input1 runs as
- * a block-sparse product on the matrix cores (patch_mfma.hip) when dilation == 1 and the shape allows, else as before. */
+GFLA_DEF_RESAMPLE_FWD(f32, float)
+GFLA_DEF_RESAMPLE_FWD(f64, double)
+GFLA_DEF_RESAMPLE_FWD(bf16, uint16_t)
+GFLA_DEF_RESAMPLE_FWD(f16, uint16_t)
+GFLA_DEF_RESAMPLE_BWD(f32, float, float)
+GFLA_DEF_RESAMPLE_BWD(f64, double, double)
+GFLA_DEF_RESAMPLE_BWD(bf16, uint16_t, float)
+GFLA_DEF_RESAMPLE_BWD(f16, uint16_t, float)
+/* the _ws twin of RESAMPLE_BWD exists for f32 only: workspace = gfla_scatter_workspace_bytes(B, H, W, k*k), may be NULL */
 int gfla_resample2d_bwd_ws_f32(const float *a, const float *b, const float *go, float *g1, float *g2, void *workspace,
-                               int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int d,
-                               int trunc, gfla_stream_t st) {
-  const unsigned *skip_stat = nullptr;
-  unsigned skip_limit = 0;
-  const bool big = gfla::tuning(6) != 1 && gfla::big_plane_regime(B, C, Hi * Wi * (int64_t)sizeof(gfla::lds_acc_t), gfla::lds_budget());
-  if (g1 && workspace && d == 1 && gfla::tuning(6) != 1 && !big) {
-    int rc = gfla::check<float>(a, b, B, C, Hi, Wi, H, W, k, d);
-    if (rc != GFLA_OK) return rc;
-    if (!go) return GFLA_ERR_NULL_POINTER;
-    // adaptive only where the LDS-atomic kernel exists as the device-side fallback
-    const bool lds_fallback = gfla::lds_geometry(Hi, Wi, sizeof(gfla::lds_acc_t), B, C, H, W, (k - 1) * d + 1).G > 0 &&
-                              gfla::lds_geometry(Hi, Wi, sizeof(float), B, C, H, W, (k - 1) * d + 1).G > 0;
-    if (trunc & 2) {  // overwrite requested: both the product and its device-side fallback must be sole writers
-      const gfla::PlaneGeo pg1 = gfla::lds_geometry(Hi, Wi, sizeof(gfla::lds_acc_t), B, C, H, W, (k - 1) * d + 1);
-      if (lds_fallback && !(pg1.split == 1 && pg1.margin < 0)) {
-        if (hipMemsetAsync(g1, 0, (size_t)(B * C * Hi * Wi) * 4, static_cast<hipStream_t>(st)) != hipSuccess) return GFLA_ERR_LAUNCH;
-        trunc &= ~2;
-      }
-    }
-    rc = gfla::rs_input1_bwd_mfma(b, go, g1, workspace, B, C, Hi, Wi, H, W, k, trunc & 1, (trunc & 2) ? 0 : 1,
-                                  lds_fallback ? 1 : 0, &skip_stat, &skip_limit, static_cast<hipStream_t>(st));
-    if (rc == GFLA_OK) {
-      if (!lds_fallback || skip_limit == 0xffffffffu) g1 = nullptr, skip_stat = nullptr;  // done unconditionally
-    } else if (rc != GFLA_ERR_UNSUPPORTED) {
-      return rc;
-    } else {
-      skip_stat = nullptr;
-    }
-    if (!g1 && !g2) return GFLA_OK;
-  }
-  void *taps = (workspace && g1) ? static_cast<unsigned char *>(workspace) + gfla::pm_table_bytes(B, H, W, k * k) : nullptr;
-  return gfla::resample2d_bwd<float>(a, b, go, g1, g2, B, C, Hi, Wi, H, W, k, d, trunc, st, skip_stat, skip_limit, taps);
-}
-/* bf16 storage: grad_in1 bf16; grad_in2 (B,3,H,W) FLOAT32 (a reduction over the channels) */
-int gfla_resample2d_bwd_bf16(const uint16_t *a, const uint16_t *b, const uint16_t *go, uint16_t *g1, float *g2, int64_t B,
-                             int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int d, int trunc,
-                             gfla_stream_t st) {
-  return gfla::resample2d_bwd<bf16_t>(reinterpret_cast<const bf16_t *>(a), reinterpret_cast<const bf16_t *>(b),
-                                      reinterpret_cast<const bf16_t *>(go), reinterpret_cast<bf16_t *>(g1), g2, B, C, Hi,
-                                      Wi, H, W, k, d, trunc, st);
-}
-/* Host-side launch geometry of the big-plane tile kernels (csrc/tile_map.h; no GPU needed: the CPU tests sweep it).
- * op: 0 block_extractor forward, 1 block_extractor backward (both gradients), 2 resample2d forward / d/d input2,
- * 3 resample2d d/d input1.  (H, W) = the flow / output grid, (Hs, Ws) = the source plane, span = taps per axis (kernel_size
- * + 1 for block_extractor, (kernel_size - 1) * dilation + 1 for resample2d), elem_size 4 / 8.
- * out[10] = in the regime by default (0 / 1), tile rows, tile columns, tiles along x, tiles along y, threads per workgroup,
- * channels per workgroup, channel groups, dynamic LDS bytes requested, workgroups. */
-int gfla_big_plane_geometry(int op, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int span,
-                            int elem_size, int64_t *out) {
-  if (!out) return GFLA_ERR_NULL_POINTER;
-  if (op < 0 || op > 4 || B <= 0 || C <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || span < 1 || (elem_size != 4 && elem_size != 8))
-    return GFLA_ERR_BAD_SHAPE;
-  const int per = op == 0 || op == 2 || op == 4 ? elem_size : op == 3 ? 8 : 8 + elem_size;
-  const int64_t plane_bytes = Hs * Ws * (int64_t)(op == 1 ? 8 + elem_size : op == 3 ? 8 : elem_size);
-  const gfla::BigGeo g = gfla::big_geometry(op, B, C, H, W, span, per);
-  const int64_t v[10] = {gfla::big_plane_regime(B, C, plane_bytes, gfla::lds_budget()) ? 1 : 0, g.tg.th, g.tg.tw, g.tg.ntx, g.tg.nty,
-                         g.tg.threads, g.G, g.ngroups, g.lds_bytes, g.nwg};
-  for (int i = 0; i < 10; ++i) out[i] = v[i];
-  return GFLA_OK;
-}
-/* The workgroup -> work-item remap of those kernels (a bijection of [0, nwg) that hands the blocks of each of the 8 XCDs a
- * contiguous range); -1 outside [0, nwg). */
-int64_t gfla_xcd_swizzle(int64_t block, int64_t nwg) {
-  return (block < 0 || block >= nwg) ? -1 : gfla::xcd_swizzle(block, nwg);
-}
-int gfla_resample2d_bwd_f64(const double *a, const double *b, const double *go, double *g1, double *g2,
-                            int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k,
-                            int d, int trunc, gfla_stream_t st) {
-  return gfla::resample2d_bwd<double>(a, b, go, g1, g2, B, C, Hi, Wi, H, W, k, d, trunc, st);
-}
-/* f16 storage: the bf16 entry points' twins (same kernels, IEEE binary16 loads and stores) */
-int gfla_resample2d_fwd_f16(const uint16_t *a, const uint16_t *b, uint16_t *o, int64_t B, int64_t C,
-                            int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int d,
-                            gfla_stream_t st) {
-  return gfla::resample2d_fwd<f16_t>(reinterpret_cast<const f16_t *>(a),
-                                     reinterpret_cast<const f16_t *>(b), reinterpret_cast<f16_t *>(o),
-                                     B, C, Hi, Wi, H, W, k, d, st);
-}
-int gfla_resample2d_bwd_f16(const uint16_t *a, const uint16_t *b, const uint16_t *go, uint16_t *g1, float *g2, int64_t B,
-                            int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int k, int d, int trunc,
-                            gfla_stream_t st) {
-  return gfla::resample2d_bwd<f16_t>(reinterpret_cast<const f16_t *>(a), reinterpret_cast<const f16_t *>(b),
-                                     reinterpret_cast<const f16_t *>(go), reinterpret_cast<f16_t *>(g1), g2, B, C, Hi,
-                                     Wi, H, W, k, d, trunc, st);
+                               GFLA_RS_SHAPE_PARAMS, int trunc, gfla_stream_t st) {
+  return gfla::resample2d_bwd<float>(a, b, go, g1, g2, GFLA_RS_SHAPE_ARGS, trunc, st, workspace);
 }
 }

@@ -138,11 +138,12 @@ __device__ __forceinline__ void pin_taps(A (&v)[N][N]) {
   }
 }
 
-// resample2d d/d input2 (kernel_size 4, dilation 1, f32 / bf16 storage) on the aggregation's streaming machinery
-// (local_attn_aggregate.hip); GFLA_ERR_UNSUPPORTED where the shape does not fit it
+// resample2d d/d input2 (kernel_size 4, dilation 1, float arithmetic) on the aggregation's streaming machinery
+// (local_attn_aggregate.hip), launched from the plan the route holds (gs_route.h: rs_bwd_route)
+struct AggStreamPlan;
 template <typename T>
-int rs_bwd2_stream(const T *in1, const T *in2, const T *gout, float *gin2, int64_t B, int64_t C, int64_t Hi, int64_t Wi,
-                   int64_t H, int64_t W, hipStream_t stream);
+int rs_bwd2_stream(const AggStreamPlan &pl, const T *in1, const T *in2, const T *gout, float *gin2, int64_t C, int64_t Hi,
+                   int64_t Wi, int64_t H, int64_t W, hipStream_t stream);
 
 // d/d (dx, dy, sigma) of one pixel from the channel sums of its taps (resample2d_kernel.cu:273-328):
 //   Racc[r] = sum_c g_c sum_q w_x[q] v_c[r][q],   Cacc[q] = sum_c g_c sum_r w_y[r] v_c[r][q]

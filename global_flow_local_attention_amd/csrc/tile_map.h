@@ -194,16 +194,6 @@ inline int tile_probe_bits() {
 #endif
 }
 
-// Host side: is this the regime of the big-plane kernels?  Few planes (the planes-in-LDS / windowed kernels get fewer
-// than ~4 workgroups per CU out of batch x channel groups) AND planes beyond the LDS budget.  tuning key 30: 1 = never
-// (round 1's windowed kernels), 2 = always (tests drive the kernels at small shapes).
-inline bool big_plane_regime(int64_t B, int64_t C, int64_t plane_bytes, int64_t lds_budget) {
-  const int t = tuning(30);
-  if (t == 1) return false;
-  if (t == 2) return true;
-  return plane_bytes > lds_budget && B * C < 4 * kNumCU;
-}
-
 // Scatter tiles: th x tw flow pixels per workgroup, one pixel per thread (th * tw <= 512).  tuning keys 31 / 32.
 struct TileGeo {
   int th, tw, nty, ntx, threads;

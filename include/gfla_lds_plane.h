@@ -2,8 +2,10 @@
  * ctypes binding reads both.
  *
  * ---- launch geometry of the planes-in-LDS kernels (csrc/lds_plane.h: PlaneGeo), for tests -- host only, no GPU needed ----
- * gfla_lds_plane_geometry answers with the geometry a launch of the family would use right now (the launchers and this query
- * call the same functions; the tuning keys 4 = cap on G, 5 = split, 10 = LDS budget in KB are honoured as a launch honours them):
+ * gfla_lds_plane_geometry answers with the geometry a launch of the family would use right now.  The launchers and this query
+ * call the same functions for the GATE (does the family take the call at all: csrc/gs_route.h, one route function per
+ * entry-point family) as well as for the geometry; the tuning keys 4 = cap on G, 5 = split, 10 = LDS budget in KB are honoured
+ * as a launch honours them:
  *   op 0 block_extractor backward, gradient of a (B,C,kH,kW) tensor     1 the attention-factored form (aggregation backward)
  *      2 the unfold form (gradient in unfold layout)                    3 unfold + attention in one pass
  *      4 block_extractor unfold forward
