@@ -10,8 +10,9 @@ from .local_attn_reshape import LocalAttnReshape, LocalAttnReshapeFunction  # no
 from .resample2d import Resample2d, Resample2dFunction  # noqa: F401
 from .extractor_attn import (BlockExtractorUnfoldFunction, ExtractorAttn, FcTailFunction, GraphedCall,  # noqa: F401
                              LocalAttnAggregateFunction, graphed_inference, patch_reference_extractor_attn)
-from .losses import (AffineRegFunction, AffineRegularizationLoss, GramL1Function, MultiAffineRegularizationLoss,  # noqa: F401
-                     PerceptualLoss, StyleContentLoss, StyleLoss, VGGLoss, gram_l1)
+from .losses import (AdversarialLoss, AffineRegFunction, AffineRegularizationLoss, GramL1Function,  # noqa: F401
+                     MultiAffineRegularizationLoss, PerceptualLoss, StyleContentLoss, StyleLoss, VGGLoss, gan_generator_term,
+                     gram_l1)
 from .correctness import CorrectnessMapFunction, MaxCosineFunction, PerceptualCorrectness, max_cosine_similarity  # noqa: F401
 from .flow_warp import BilinearSamplingBlock, FlowWarp, FlowWarpFunction, flow_warp  # noqa: F401
 from .vgg import Conv3x3ReluFunction, MaxPool2x2Function, VGG19Features, conv3x3_relu, maxpool2x2  # noqa: F401
@@ -21,6 +22,8 @@ from .head_conv import (HeadConv3x3, HeadConv3x3Function, flow_mask_heads, fuse_
                         patch_reference_flow_heads, torch_head_conv3x3)
 from .gen_conv import (GenConvFunction, InferenceConv, conv3x3, conv4x4_down, conv_transpose3x3_up, fuse_inference_convs,  # noqa: F401
                        patch_reference_convs, torch_gen_conv)
+from .spectral_norm import (SpectralConv, SpectralNormFunction, fuse_spectral_norm, patch_reference_discriminators,  # noqa: F401
+                            spectral_normalize, torch_spectral_normalize)
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401
 from .face_step import (DualStreamAttn, MaskBlendFunction, face_target_forward, generate_frames,  # noqa: F401

@@ -257,10 +257,10 @@ def conv3x3(x, weight, bias=None, padding="zeros", pre_slope=None, add=None, imp
     return _gen_conv(x, weight, bias, S1K3, padding, pre_slope, add, impl, grad)
 
 
-def conv4x4_down(x, weight, bias=None, pre_slope=None, impl="auto", grad="torch"):
-    """conv2d(leaky_relu(x, pre_slope), weight (Cout,Cin,4,4), bias, stride=2, padding=1): H, W >= 2, odd sizes as torch
-    (output (H-2)//2+1 x (W-2)//2+1).  Dispatch as conv3x3."""
-    return _gen_conv(x, weight, bias, S2K4, "zeros", pre_slope, None, impl, grad)
+def conv4x4_down(x, weight, bias=None, pre_slope=None, impl="auto", grad="torch", add=None):
+    """conv2d(leaky_relu(x, pre_slope), weight (Cout,Cin,4,4), bias, stride=2, padding=1) (+ add): H, W >= 2, odd sizes as
+    torch (output (H-2)//2+1 x (W-2)//2+1).  Dispatch as conv3x3."""
+    return _gen_conv(x, weight, bias, S2K4, "zeros", pre_slope, add, impl, grad)
 
 
 def conv_transpose3x3_up(x, weight, bias=None, add=None, impl="auto", pre_slope=None, grad="torch"):

@@ -44,7 +44,7 @@ def _bind_vgg(cls, vgg):
 
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
             dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False, fuse_instance_norm=False,
-            fuse_heads=False, inference_convs=False, train_convs=False):
+            fuse_heads=False, inference_convs=False, train_convs=False, discriminator_convs=False):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -96,10 +96,19 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     train_convs: with inference_convs, True makes those InferenceConv run the library's own gradient kernels as well
     (gen_conv.GenConvFunction, grad="kernels": csrc/gen_conv_bwd.hip and csrc/gen_conv_wgrad.hip) whenever a gradient is
     needed on a GPU map of float32 / float16 / bfloat16, so a training step of the generators' bodies calls no vendor
-    convolution.  False (the default) keeps the torch composition for training.  Without inference_convs it raises
-    ValueError."""
-    if train_convs and not inference_convs:
-        raise ValueError("install: train_convs=True needs inference_convs")
+    convolution.  False (the default) keeps the torch composition for training.  Without inference_convs or
+    discriminator_convs it raises ValueError.
+
+    discriminator_convs: True (or "auto" / "torch", the `impl` of spectral_norm.py) wraps the constructors of the reference's
+    ResDiscriminator, PatchDiscriminator and TemporalDiscriminator (discriminator.py) so that one built AFTER install() has
+    every Conv2d under torch's spectral_norm hook as a SpectralConv: all normalisations of a forward are one batched call on
+    csrc/spectral_norm.hip, and the 3x3 and 4x4 stride-2 convolutions run through gen_conv.py (with train_convs on its
+    gradient kernels as well; the 1x1 and the k 4, s 1 convolutions keep F.conv2d on the normalised weight).
+    ResBlockEncoder.forward hands shortcut(x) to the last convolution's epilogue.  Indices, state-dict keys, Parameter and
+    buffer objects are unchanged.  Imports the reference's discriminator module.  False (the default) changes nothing."""
+    if train_convs and not (inference_convs or discriminator_convs):
+        raise ValueError("install: train_convs=True needs inference_convs%s"
+                         % ("" if not discriminator_convs else " or discriminator_convs"))
     from . import extractor_attn as _ea
     if strict_mfma is None and allow_vendor_fallback is not None:
         strict_mfma = not allow_vendor_fallback
@@ -158,6 +167,11 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
         from .gen_conv import patch_reference_convs
         patch_reference_convs(base_function, inference_convs if isinstance(inference_convs, str) else "auto",
                               "kernels" if train_convs else "torch")
+    if base_function is not None and discriminator_convs:
+        from .spectral_norm import patch_reference_discriminators
+        patch_reference_discriminators(importlib.import_module("model.networks.discriminator"), base_function,
+                                       discriminator_convs if isinstance(discriminator_convs, str) else "auto",
+                                       "kernels" if train_convs else "torch")
     if vgg is not None:
         from . import losses
         external_function = importlib.import_module("model.networks.external_function")

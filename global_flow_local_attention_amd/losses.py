@@ -306,3 +306,48 @@ class StyleContentLoss(nn.Module):
     def forward(self, generated, target):
         content, style = self.vgg_loss(generated, target)
         return style * self.lambda_style + content * self.lambda_content
+
+
+class AdversarialLoss(nn.Module):
+    """The adversarial term of the reference's models (external_function.py AdversarialLoss), from the formulas:
+    nsgan  binary cross entropy of D, a probability, against the label (nn.BCELoss, as the reference: a discriminator
+           that ends in a sigmoid)                                 lsgan  mean squared error against the label
+    hinge  for the discriminator mean(relu(1 - D)) on real and mean(relu(1 + D)) on fake samples, for the generator
+           -mean(D)
+    Call: (outputs, is_real, for_dis=None); the label is target_real_label / target_fake_label, constant over outputs."""
+
+    TYPES = ("nsgan", "lsgan", "hinge")
+
+    def __init__(self, type="nsgan", target_real_label=1.0, target_fake_label=0.0):
+        super(AdversarialLoss, self).__init__()
+        if type not in self.TYPES:
+            raise ValueError("AdversarialLoss: type is one of %s (got %r)" % (self.TYPES, type))
+        self.type = type
+        self.real_label, self.fake_label = float(target_real_label), float(target_fake_label)
+
+    def forward(self, outputs, is_real, for_dis=None):
+        if self.type == "hinge":
+            if for_dis:
+                return F.relu(1.0 - outputs if is_real else 1.0 + outputs).mean()
+            return -outputs.mean()
+        labels = torch.full_like(outputs, self.real_label if is_real else self.fake_label)
+        if self.type == "nsgan":
+            return F.binary_cross_entropy(outputs, labels)
+        return F.mse_loss(outputs, labels)
+
+
+def gan_generator_term(net_D, loss, weight=1.0):
+    """(generated, target) -> weight * loss(net_D(generated), True, False): the callable TrainerShell(gan_loss=...)
+    expects (pose_model.py:150-153).  D runs with its parameters' requires_grad off, as the reference's _freeze does, so the
+    generator's step leaves no gradient on D; the flags are restored as they were found."""
+    def term(generated, target):
+        params = list(net_D.parameters())
+        flags = [p.requires_grad for p in params]
+        for p in params:
+            p.requires_grad_(False)
+        try:
+            return loss(net_D(generated), True, False) * weight
+        finally:
+            for p, flag in zip(params, flags):
+                p.requires_grad_(flag)
+    return term

@@ -853,6 +853,10 @@ int gfla_head_conv3x3_bwd_bf16(const uint16_t *x, const float *w, const uint16_t
  * documented in gfla_lds_plane.h ---- */
 #include "gfla_lds_plane.h"
 
+/* ---- spectral normalisation of a batch of weight matrices (csrc/spectral_norm.hip): gfla_spectral_norm_*, declared and
+ * documented in gfla_spectral_norm.h ---- */
+#include "gfla_spectral_norm.h"
+
 #ifdef __cplusplus
 }
 #endif
