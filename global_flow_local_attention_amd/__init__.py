@@ -20,8 +20,8 @@ from .instance_norm import (InstanceNormAct, InstanceNormActFunction, fuse_insta
                             instance_norm_act)
 from .head_conv import (HeadConv3x3, HeadConv3x3Function, flow_mask_heads, fuse_output_heads, head_conv3x3,  # noqa: F401
                         patch_reference_flow_heads, torch_head_conv3x3)
-from .gen_conv import (GenConvFunction, InferenceConv, conv3x3, conv4x4_down, conv_transpose3x3_up, fuse_inference_convs,  # noqa: F401
-                       patch_reference_convs, torch_gen_conv)
+from .gen_conv import (Conv1x1Function, GenConvFunction, InferenceConv, conv1x1, conv3x3, conv4x4_down,  # noqa: F401
+                       conv_transpose3x3_up, fuse_inference_convs, patch_reference_convs, torch_conv1x1, torch_gen_conv)
 from .spectral_norm import (SpectralConv, SpectralNormFunction, fuse_spectral_norm, patch_reference_discriminators,  # noqa: F401
                             spectral_normalize, torch_spectral_normalize)
 from .install import install  # noqa: F401

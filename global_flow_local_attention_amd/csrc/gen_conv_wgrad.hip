@@ -1,4 +1,5 @@
-// The weight and bias gradients of the generators' convolutions (gen_conv.hip) on the gfx950 matrix cores.
+// The weight and bias gradients of the generators' convolutions (gen_conv.hip) and of the 1x1 convolutions (conv1x1.hip) on
+// the gfx950 matrix cores.
 //
 //   grad_w[cp][cq][tap] = sum over (b, pixel p) of P[b][cp][p] Q[b][cq][S p - 1 + tap]        float32, torch's layout
 //
@@ -6,7 +7,10 @@
 //   S1K3      g  (H x W)                      a, zero / reflect padded         1   B H W                 (Cout,Cin,3,3)
 //   S2K4      g  (Hout x Wout)                a, zero padded                   2   B Hout Wout           (Cout,Cin,4,4)
 //   T2K3      a  (H x W)                      g  (2H x 2W), zero outside       2   B H W                 (Cin,Cout,3,3)
+//   1x1       g  (Hout x Wout)                a, or the 2 x 2 mean of x        1|2 B Hout Wout           (Cout,Cin,1,1)
 //
+// The 1x1 convolution of conv1x1.hip is the KW = 1 instantiation: one tap at offset 0 (Q[S p], not S p - 1 + tap), and with
+// S = 2 the operand is pooled while it is staged, with the forward's expression and the forward's one rounding.
 // a = act(x) is recomputed from x while it is staged, with the forward's expression (LeakyReLU rounded to T once, the
 // reflect mirror): the forward saves nothing but x and the weight.
 //
@@ -22,19 +26,29 @@
 // uninitialised workspace and a second kernel sums the splits in ascending order.  The bias gradient is one workgroup per
 // channel: every thread sums its strided share of g in ascending order, then a fixed tree over the workgroup.  No atomics:
 // bit-identical from call to call.
-#include "conv_igemm.h"
+#include "conv1x1.h"
 
 namespace gfla {
 
 constexpr int kWgTile = 64;        // rows and columns of grad_w per workgroup
 constexpr int kWgPix = 64;         // pixels per step
 constexpr int kWgTarget = 1024;    // workgroups a launch aims for when it chooses the number of splits
+// the same for the 1x1 convolution: grad_w is one or two tiles there, so the splits are the workgroups, and the second
+// kernel walks them one after the other (measured: 229 us for 1,024 splits of a 32 x 3 gradient, 0.22 us per split)
+constexpr int kWgTarget1x1 = 128;
 
 template <typename T>
 __device__ __forceinline__ T wg_act(const T *p, int pre_act, float slope) {
   if (!pre_act) return *p;
   const float v = Num<T>::ld(p);
   return (T)(v > 0.f ? v : v * slope);                  // rounded to T once, as the forward stages it
+}
+
+// the mean of the 2 x 2 block at p, as conv1x1.hip's forward stages it: the float32 sum in torch's order, rounded to T once
+template <typename T>
+__device__ __forceinline__ T wg_pool(const T *p, int W) {
+  const float s = Num<T>::ld(p) + Num<T>::ld(p + 1) + Num<T>::ld(p + W) + Num<T>::ld(p + W + 1);
+  return (T)(s * 0.25f);
 }
 
 template <typename T, int KW>
@@ -67,14 +81,19 @@ __global__ __launch_bounds__(kBlock) void gen_conv_wgrad_kernel(const T *__restr
       T pv = (T)0.f, qv = (T)0.f;
       if (live && cp < CP) pv = wg_act<T>(P + (b * CP + cp) * planeP + rem, act_p, slope);
       if (live && n < N) {
-        const int cq = n / TAPS, tap = n - cq * TAPS, ky = tap / KW, kx = tap - ky * KW;
-        int qy = S * py - 1 + ky, qx = S * px - 1 + kx;
-        if (reflect) {                                  // -1 -> 1, HQ -> HQ - 2 (HQ, WQ >= 2)
-          qy = qy == -1 ? 1 : qy == HQ ? HQ - 2 : qy;
-          qx = qx == -1 ? 1 : qx == WQ ? WQ - 2 : qx;
+        if constexpr (KW == 1) {                        // the pixel itself (S 1) or the mean of its 2 x 2 block (S 2)
+          const T *q = Q + (b * CQ + n) * planeQ + (int64_t)(S * py) * WQ + S * px;
+          qv = S == 2 ? wg_pool<T>(q, WQ) : wg_act<T>(q, act_q, slope);
+        } else {
+          const int cq = n / TAPS, tap = n - cq * TAPS, ky = tap / KW, kx = tap - ky * KW;
+          int qy = S * py - 1 + ky, qx = S * px - 1 + kx;
+          if (reflect) {                                // -1 -> 1, HQ -> HQ - 2 (HQ, WQ >= 2)
+            qy = qy == -1 ? 1 : qy == HQ ? HQ - 2 : qy;
+            qx = qx == -1 ? 1 : qx == WQ ? WQ - 2 : qx;
+          }
+          if (qy >= 0 && qy < HQ && qx >= 0 && qx < WQ)
+            qv = wg_act<T>(Q + (b * CQ + cq) * planeQ + (int64_t)qy * WQ + qx, act_q, slope);
         }
-        if (qy >= 0 && qy < HQ && qx >= 0 && qx < WQ)
-          qv = wg_act<T>(Q + (b * CQ + cq) * planeQ + (int64_t)qy * WQ + qx, act_q, slope);
       }
       *reinterpret_cast<T *>(Ps + r * RSB + col * (int)sizeof(T)) = pv;
       *reinterpret_cast<T *>(Qs + r * RSB + col * (int)sizeof(T)) = qv;
@@ -136,6 +155,22 @@ struct WgPlan {
   int S, KW, act_p;
 };
 
+// the GEMM's sizes are filled in: the reduction length and how it is split
+static int wg_split(WgPlan *p, int64_t target) {
+  p->N = p->CQ * p->KW * p->KW;
+  if (p->L > 0x7fffffffLL || p->N > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
+  p->tilesM = ceil_div(p->CP, kWgTile);
+  p->tilesN = ceil_div(p->N, kWgTile);
+  const int64_t steps = ceil_div(p->L, kWgPix), tiles = p->tilesM * p->tilesN;
+  int64_t splits = target / tiles;
+  splits = splits < 1 ? 1 : splits > steps ? steps : splits;
+  p->max_splits = splits;                           // what the workspace is sized for: monotone in B, H and W
+  p->per_split = ceil_div(steps, splits) * kWgPix;
+  p->splits = ceil_div(p->L, p->per_split);
+  if (p->tilesM > 65535 || p->splits > 65535) return GFLA_ERR_UNSUPPORTED;
+  return GFLA_OK;
+}
+
 static int wg_plan(int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int geometry, int pad_mode, WgPlan *p) {
   CvTile fwd;
   int64_t cblocks = 0;
@@ -149,29 +184,25 @@ static int wg_plan(int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, i
   } else {
     p->CP = Cout, p->CQ = Cin, p->HP = fwd.Hout, p->WP = fwd.Wout, p->HQ = H, p->WQ = W;
   }
-  p->N = p->CQ * p->KW * p->KW;
   p->L = B * p->HP * p->WP;
-  if (p->L > 0x7fffffffLL || p->N > 0x7fffffffLL) return GFLA_ERR_UNSUPPORTED;
-  p->tilesM = ceil_div(p->CP, kWgTile);
-  p->tilesN = ceil_div(p->N, kWgTile);
-  const int64_t steps = ceil_div(p->L, kWgPix), tiles = p->tilesM * p->tilesN;
-  int64_t splits = kWgTarget / tiles;
-  splits = splits < 1 ? 1 : splits > steps ? steps : splits;
-  p->max_splits = splits;                           // what the workspace is sized for: monotone in B, H and W
-  p->per_split = ceil_div(steps, splits) * kWgPix;
-  p->splits = ceil_div(p->L, p->per_split);
-  if (p->tilesM > 65535 || p->splits > 65535) return GFLA_ERR_UNSUPPORTED;
-  return GFLA_OK;
+  return wg_split(p, kWgTarget);
 }
 
-template <typename T>
-static int gen_conv_bwd_weight(const T *gy, const T *x, float *grad_w, float *grad_b, void *ws, int64_t B, int64_t Cin,
-                               int64_t Cout, int64_t H, int64_t W, int geometry, int pad_mode, int pre_act, double pre_slope,
-                               gfla_stream_t stream) {
-  if (!gy || (!grad_w && !grad_b) || (grad_w && (!x || !ws))) return GFLA_ERR_NULL_POINTER;
-  WgPlan p;
-  const int rc = wg_plan(B, Cin, Cout, H, W, geometry, pad_mode, &p);
+// the 1x1 convolution (conv1x1.hip): P = g at the output's pixels, Q = x at pixel `pool` p, pooled while staged (pool 2)
+static int wg_plan_1x1(int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int pool, int pre_act, WgPlan *p) {
+  PwShape s;
+  const int rc = pw_check(B, Cin, Cout, H, W, pool, pre_act, &s);                      // the forward's own limits
   if (rc != GFLA_OK) return rc;
+  p->KW = 1, p->S = pool, p->act_p = 0;
+  p->CP = Cout, p->CQ = Cin, p->HP = s.Hout, p->WP = s.Wout, p->HQ = H, p->WQ = W;
+  p->L = B * s.OP;
+  return wg_split(p, kWgTarget1x1);
+}
+
+// the launches of a plan: the split reduction and its sum, then the bias gradient over g's planes of `plane` pixels
+template <typename T>
+static int wg_run(const WgPlan &p, const T *gy, const T *x, float *grad_w, float *grad_b, void *ws, int64_t B, int64_t Cout,
+                  int64_t plane, int pad_mode, int pre_act, double pre_slope, gfla_stream_t stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (grad_w) {
     const T *P = p.act_p ? x : gy, *Q = p.act_p ? gy : x;
@@ -183,7 +214,8 @@ static int gen_conv_bwd_weight(const T *gy, const T *x, float *grad_w, float *gr
           p.act_p ? act : 0, p.act_p ? 0 : act, (float)pre_slope, p.L, p.per_split);
     };
     if (p.KW == 4) launch(std::integral_constant<int, 4>());
-    else launch(std::integral_constant<int, 3>());
+    else if (p.KW == 3) launch(std::integral_constant<int, 3>());
+    else launch(std::integral_constant<int, 1>());
     int st = launch_status();
     if (st != GFLA_OK) return st;
     const int64_t total = p.CP * p.N;
@@ -192,12 +224,31 @@ static int gen_conv_bwd_weight(const T *gy, const T *x, float *grad_w, float *gr
     st = launch_status();
     if (st != GFLA_OK) return st;
   }
-  if (grad_b) {
-    CvTile fwd = cv_tile(geometry, Cout, H, W);
-    const int64_t plane = fwd.Hout * fwd.Wout;
-    gen_conv_bgrad_kernel<T><<<dim3((unsigned)Cout), kBlock, 0, s>>>(gy, grad_b, (int)Cout, plane, B * plane);
-  }
+  if (grad_b) gen_conv_bgrad_kernel<T><<<dim3((unsigned)Cout), kBlock, 0, s>>>(gy, grad_b, (int)Cout, plane, B * plane);
   return launch_status();
+}
+
+template <typename T>
+static int gen_conv_bwd_weight(const T *gy, const T *x, float *grad_w, float *grad_b, void *ws, int64_t B, int64_t Cin,
+                               int64_t Cout, int64_t H, int64_t W, int geometry, int pad_mode, int pre_act, double pre_slope,
+                               gfla_stream_t stream) {
+  if (!gy || (!grad_w && !grad_b) || (grad_w && (!x || !ws))) return GFLA_ERR_NULL_POINTER;
+  WgPlan p;
+  const int rc = wg_plan(B, Cin, Cout, H, W, geometry, pad_mode, &p);
+  if (rc != GFLA_OK) return rc;
+  const CvTile fwd = cv_tile(geometry, Cout, H, W);
+  return wg_run<T>(p, gy, x, grad_w, grad_b, ws, B, Cout, fwd.Hout * fwd.Wout, pad_mode, pre_act, pre_slope, stream);
+}
+
+template <typename T>
+static int conv1x1_bwd_weight(const T *gy, const T *x, float *grad_w, float *grad_b, void *ws, int64_t B, int64_t Cin,
+                              int64_t Cout, int64_t H, int64_t W, int pool, int pre_act, double pre_slope,
+                              gfla_stream_t stream) {
+  if (!gy || (!grad_w && !grad_b) || (grad_w && (!x || !ws))) return GFLA_ERR_NULL_POINTER;
+  WgPlan p;
+  const int rc = wg_plan_1x1(B, Cin, Cout, H, W, pool, pre_act, &p);
+  if (rc != GFLA_OK) return rc;
+  return wg_run<T>(p, gy, x, grad_w, grad_b, ws, B, Cout, p.HP * p.WP, 0, pre_act, pre_slope, stream);
 }
 
 }  // namespace gfla
@@ -218,6 +269,15 @@ int64_t gfla_gen_conv_bwd_workspace_bytes(int64_t B, int64_t Cin, int64_t Cout, 
   return (weight > data ? weight : data) + 16;
 }
 
+int64_t gfla_conv1x1_bwd_workspace_bytes(int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int pool,
+                                         int elem_size) {
+  if (elem_size != 2 && elem_size != 4) return GFLA_ERR_BAD_SHAPE;
+  gfla::WgPlan p;
+  const int rc = gfla::wg_plan_1x1(B, Cin, Cout, H, W, pool, 0, &p);
+  if (rc != GFLA_OK) return rc;
+  return p.max_splits * p.CP * p.N * 4 + 16;                                             // the float32 partial sums
+}
+
 #define GFLA_DEF_GEN_CONV_WGRAD(SFX, T, CT)                                                                               \
   int gfla_gen_conv_bwd_weight_##SFX(const T *grad_y, const T *x, float *grad_w, float *grad_b, void *workspace,          \
                                      int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int geometry,            \
@@ -225,6 +285,12 @@ int64_t gfla_gen_conv_bwd_workspace_bytes(int64_t B, int64_t Cin, int64_t Cout, 
     return gfla::gen_conv_bwd_weight<CT>(reinterpret_cast<const CT *>(grad_y), reinterpret_cast<const CT *>(x), grad_w,   \
                                          grad_b, workspace, B, Cin, Cout, H, W, geometry, pad_mode, pre_act, pre_slope,   \
                                          stream);                                                                         \
+  }                                                                                                                       \
+  int gfla_conv1x1_bwd_weight_##SFX(const T *grad_y, const T *x, float *grad_w, float *grad_b, void *workspace,           \
+                                    int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int pool, int pre_act,    \
+                                    double pre_slope, gfla_stream_t stream) {                                             \
+    return gfla::conv1x1_bwd_weight<CT>(reinterpret_cast<const CT *>(grad_y), reinterpret_cast<const CT *>(x), grad_w,    \
+                                        grad_b, workspace, B, Cin, Cout, H, W, pool, pre_act, pre_slope, stream);         \
   }
 GFLA_DEF_GEN_CONV_WGRAD(f32, float, float)
 GFLA_DEF_GEN_CONV_WGRAD(f16, uint16_t, f16_t)

@@ -44,7 +44,7 @@ def _bind_vgg(cls, vgg):
 
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
             dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False, fuse_instance_norm=False,
-            fuse_heads=False, inference_convs=False, train_convs=False, discriminator_convs=False):
+            fuse_heads=False, inference_convs=False, train_convs=False, discriminator_convs=False, pointwise_convs=False):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -103,9 +103,19 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     ResDiscriminator, PatchDiscriminator and TemporalDiscriminator (discriminator.py) so that one built AFTER install() has
     every Conv2d under torch's spectral_norm hook as a SpectralConv: all normalisations of a forward are one batched call on
     csrc/spectral_norm.hip, and the 3x3 and 4x4 stride-2 convolutions run through gen_conv.py (with train_convs on its
-    gradient kernels as well; the 1x1 and the k 4, s 1 convolutions keep F.conv2d on the normalised weight).
+    gradient kernels as well; the 1x1 convolutions keep F.conv2d on the normalised weight unless pointwise_convs is set,
+    the k 4, s 1 ones always).
     ResBlockEncoder.forward hands shortcut(x) to the last convolution's epilogue.  Indices, state-dict keys, Parameter and
-    buffer objects are unchanged.  Imports the reference's discriminator module.  False (the default) changes nothing."""
+    buffer objects are unchanged.  Imports the reference's discriminator module.  False (the default) changes nothing.
+
+    pointwise_convs: with inference_convs and / or discriminator_convs, True puts the 1x1 convolutions on gen_conv.conv1x1
+    (csrc/conv1x1.hip) as well: the learnable shortcut of a generator's ResBlock (fuse_inference_convs(pointwise=True)),
+    and in the discriminators the pooled shortcut of every ResBlockEncoder -- its AvgPool2d(2) folded into the convolution
+    -- and the final Conv2d(C, 1, 1) (fuse_spectral_norm(pointwise="kernels")).  Together with train_convs a ResDiscriminator
+    then trains with no vendor convolution at all.  False (the default) changes nothing; without inference_convs or
+    discriminator_convs it raises ValueError."""
+    if pointwise_convs and not (inference_convs or discriminator_convs):
+        raise ValueError("install: pointwise_convs=True needs inference_convs or discriminator_convs")
     if train_convs and not (inference_convs or discriminator_convs):
         raise ValueError("install: train_convs=True needs inference_convs%s"
                          % ("" if not discriminator_convs else " or discriminator_convs"))
@@ -166,12 +176,13 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     if base_function is not None and inference_convs:
         from .gen_conv import patch_reference_convs
         patch_reference_convs(base_function, inference_convs if isinstance(inference_convs, str) else "auto",
-                              "kernels" if train_convs else "torch")
+                              "kernels" if train_convs else "torch", bool(pointwise_convs))
     if base_function is not None and discriminator_convs:
         from .spectral_norm import patch_reference_discriminators
         patch_reference_discriminators(importlib.import_module("model.networks.discriminator"), base_function,
                                        discriminator_convs if isinstance(discriminator_convs, str) else "auto",
-                                       "kernels" if train_convs else "torch")
+                                       "kernels" if train_convs else "torch",
+                                       "kernels" if pointwise_convs else "torch")
     if vgg is not None:
         from . import losses
         external_function = importlib.import_module("model.networks.external_function")

@@ -4,7 +4,8 @@ own kernels.
 torch.nn.utils.spectral_norm is a forward pre-hook: per convolution and per forward it runs three gemv, two
 normalisations, a dot and a division.  Here all normalised convolutions of a network are one call of a fixed number of
 launches, and what they convolve with is an ordinary tensor, so their 3x3 and 4x4 stride-2 convolutions run through
-gen_conv.py, forward and backward.
+gen_conv.py, forward and backward -- and with pointwise="kernels" the 1x1 ones as well, the AvgPool2d(2) in front of a
+shortcut folded into the convolution (gen_conv.conv1x1).
 
     spectral_normalize      the functional form over a batch of (weight, u, v)
     SpectralNormFunction    the autograd Function on the kernels
@@ -28,6 +29,7 @@ from torch.nn.utils.spectral_norm import SpectralNorm as _TorchSpectralNorm
 from . import _lib
 from . import gen_conv as _gc
 
+POINTWISE = ("torch", "kernels")
 _TABLE_CACHE = {}
 _TABLE_CACHE_MAX = 64
 
@@ -183,21 +185,43 @@ def _geometry_of(conv):
     return None
 
 
+def _check_pointwise(pointwise):
+    if pointwise not in POINTWISE:
+        raise ValueError("pointwise: one of %s (got %r)" % (POINTWISE, pointwise))
+
+
+def _is_pointwise(conv):
+    """Conv2d(k 1, s 1, p 0), groups 1, dilation 1: what gen_conv.conv1x1 computes"""
+    return conv.groups == 1 and tuple(conv.dilation) == (1, 1) and tuple(conv.kernel_size) == (1, 1) and \
+        tuple(conv.stride) == (1, 1) and conv.padding in ((0, 0), 0)
+
+
+def _is_pool2(module):
+    """nn.AvgPool2d(2, 2): what conv1x1's pool=2 computes"""
+    def pair(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    return type(module) is nn.AvgPool2d and pair(module.kernel_size) == (2, 2) and pair(module.stride) == (2, 2) and \
+        pair(module.padding) == (0, 0) and not module.ceil_mode and module.divisor_override is None
+
+
 class SpectralConv(nn.Module):
     """[LeakyReLU(pre_slope)] -> the convolution `conv` under torch's spectral_norm hook (+ add), with the normalisation
     on the batched op.  `weight_orig`, `bias`, `weight_u` and `weight_v` are conv's own Parameter and buffer objects under
     conv's names and in conv's order, so state dicts interchange with the hooked form in both directions;
     n_power_iterations and eps are the hook's.  Training mode iterates, eval mode does not.
     Conv2d(k 3, s 1, p 1) and Conv2d(k 4, s 2, p 1) run through gen_conv.conv3x3 / conv4x4_down (grad="kernels": the
-    library's gradient kernels; the normalised weight's gradient comes back through SpectralNormFunction); every other
-    geometry -- 1x1, groups, dilation -- runs F.conv2d on the normalised weight.
+    library's gradient kernels; the normalised weight's gradient comes back through SpectralNormFunction).  Conv2d(k 1,
+    s 1, p 0) runs through gen_conv.conv1x1 with pointwise="kernels" -- `pool` 2: behind the AvgPool2d(2) that
+    fuse_spectral_norm folded in, which needs that route --, and with the default pointwise="torch" through F.conv2d on the
+    normalised weight, as every other geometry does (groups, dilation, k 4 with s 1).
     Inside a forward of a network rewritten by fuse_spectral_norm the weight was normalised with all the others in one
     call; called on its own, the module normalises itself, a batch of one."""
 
-    def __init__(self, conv, pre_slope=None, impl="auto", grad="torch"):
+    def __init__(self, conv, pre_slope=None, impl="auto", grad="torch", pointwise="torch", pool=1):
         super(SpectralConv, self).__init__()
         _lib.check_impl(impl)
         _gc._check_grad(grad)
+        _check_pointwise(pointwise)
         hook = _torch_hook(conv)
         if type(conv) is not nn.Conv2d or hook is None:
             raise ValueError("SpectralConv: an nn.Conv2d under torch.nn.utils.spectral_norm (name 'weight', dim 0) and no "
@@ -206,6 +230,11 @@ class SpectralConv(nn.Module):
         self.pre_slope = None if pre_slope is None else float(pre_slope)
         self.n_power_iterations, self.eps = int(hook.n_power_iterations), float(hook.eps)
         self.geometry = _geometry_of(conv)
+        self.pointwise = pointwise == "kernels" and _is_pointwise(conv)
+        if pool not in _gc.POOLS or (pool == 2 and (not self.pointwise or pre_slope is not None)):
+            raise ValueError("SpectralConv: pool is 1, or 2 on a 1x1 convolution with pointwise='kernels' and no pre_slope "
+                             "(got %r)" % (pool,))
+        self.pool = pool
         for name, p in conv._parameters.items():
             self.register_parameter(name, p)
         for name, b in conv._buffers.items():
@@ -234,15 +263,18 @@ class SpectralConv(nn.Module):
             return _gc.conv3x3(x, weight, self.bias, "zeros", self.pre_slope, add, self.impl, self.grad)
         if self.geometry == _gc.S2K4:
             return _gc.conv4x4_down(x, weight, self.bias, self.pre_slope, self.impl, self.grad, add=add)
+        if self.pointwise:
+            y = _gc.conv1x1(x, weight, self.bias, self.pre_slope, self.pool, self.impl, self.grad)
+            return y if add is None else y + add
         a = x if self.pre_slope is None else F.leaky_relu(x, self.pre_slope)
         y = self.original._conv_forward(a, weight, self.bias)
         return y if add is None else y + add
 
     def extra_repr(self):
         c = self.original
-        return "%d -> %d, kernel_size=%s, stride=%s, n_power_iterations=%d, pre_slope=%s, impl=%r, grad=%r" % (
+        return "%d -> %d, kernel_size=%s, stride=%s, n_power_iterations=%d, pre_slope=%s, impl=%r, grad=%r%s" % (
             c.in_channels, c.out_channels, tuple(c.kernel_size), tuple(c.stride), self.n_power_iterations, self.pre_slope,
-            self.impl, self.grad)
+            self.impl, self.grad, ", pointwise='kernels', pool=%d" % self.pool if self.pointwise else "")
 
 
 def _normalize_all(convs, impl):
@@ -257,7 +289,7 @@ def _normalize_all(convs, impl):
             c.hand(w)
 
 
-def fuse_spectral_norm(net, impl="auto", grad="torch"):
+def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch"):
     """Rewrite, in place and recursively, every nn.Conv2d of `net` that carries torch.nn.utils.spectral_norm's hook (name
     "weight", dim 0) and no other: its slot becomes a SpectralConv with the same Parameter and buffer objects.  Indices
     and state-dict keys do not change.  Inside an nn.Sequential an nn.LeakyReLU directly in front is folded into the
@@ -266,9 +298,14 @@ def fuse_spectral_norm(net, impl="auto", grad="torch"):
     its weight; a forward hook drops what a forward did not use.
     Left alone, uncounted: ConvTranspose2d under spectral norm (dim 1), the convolution inside a CoordConv, modules with
     any other hook.  grad: the `grad` of every SpectralConv ("kernels": the convolutions train on GenConvFunction).
+    pointwise "kernels": every rewritten Conv2d(k 1, s 1, p 0) runs gen_conv.conv1x1, and inside an nn.Sequential an
+    nn.AvgPool2d(kernel 2, stride 2, padding 0, ceil_mode False, divisor_override None) directly in front of one is folded
+    into it (the pool's slot becomes nn.Identity(), the convolution gets pool=2); a pool of any other geometry stays.  The
+    default "torch" leaves the 1x1 convolutions on F.conv2d and every pool in place.
     Returns the number of convolutions rewritten."""
     _lib.check_impl(impl)
     _gc._check_grad(grad)
+    _check_pointwise(pointwise)
     replaced = {}
     for parent in list(net.modules()):
         if hasattr(parent, "addcoords"):                     # CoordConv: its convolution sees two more channels
@@ -278,11 +315,15 @@ def fuse_spectral_norm(net, impl="auto", grad="torch"):
             conv = parent._modules[name]
             if type(conv) is not nn.Conv2d or id(conv) in replaced or _torch_hook(conv) is None:
                 continue
-            slope = None
-            if isinstance(parent, nn.Sequential) and i >= 1 and type(parent._modules[names[i - 1]]) is nn.LeakyReLU:
-                slope = float(parent._modules[names[i - 1]].negative_slope)
+            slope, pool = None, 1
+            before = parent._modules[names[i - 1]] if isinstance(parent, nn.Sequential) and i >= 1 else None
+            if type(before) is nn.LeakyReLU:
+                slope = float(before.negative_slope)
                 parent._modules[names[i - 1]] = nn.Identity()
-            replaced[id(conv)] = (conv, SpectralConv(conv, slope, impl, grad))
+            elif pointwise == "kernels" and _is_pointwise(conv) and _is_pool2(before):
+                pool = 2
+                parent._modules[names[i - 1]] = nn.Identity()
+            replaced[id(conv)] = (conv, SpectralConv(conv, slope, impl, grad, pointwise, pool))
             parent._modules[name] = replaced[id(conv)][1]
     for m in net.modules():                                  # the same convolution under another name
         for name, sub in m._modules.items():
@@ -313,15 +354,16 @@ def _run_with_add(seq, x, add):
 _REFERENCE_DISCRIMINATORS = ("ResDiscriminator", "PatchDiscriminator", "TemporalDiscriminator")
 
 
-def patch_reference_discriminators(discriminator, base_function=None, impl="auto", grad="torch"):
+def patch_reference_discriminators(discriminator, base_function=None, impl="auto", grad="torch", pointwise="torch"):
     """Wrap the constructors of the reference's ResDiscriminator, PatchDiscriminator and TemporalDiscriminator
     (discriminator.py) so that every one built from now on comes out rewritten (fuse_spectral_norm on the finished
     network), and, given base_function, replace ResBlockEncoder.forward (base_function.py:533-556: model(x) + shortcut(x))
     by a version that hands shortcut(x) as `add` to the last convolution of `self.model` when that slot is a SpectralConv
-    on the 4x4 stride-2 kernels; otherwise it calls the original forward.  Idempotent.  Returns the names of the classes
-    wrapped."""
+    on the 4x4 stride-2 kernels; otherwise it calls the original forward.  pointwise: fuse_spectral_norm's.  Idempotent.
+    Returns the names of the classes wrapped."""
     _lib.check_impl(impl)
     _gc._check_grad(grad)
+    _check_pointwise(pointwise)
     wrapped = []
     for name in _REFERENCE_DISCRIMINATORS:
         cls = getattr(discriminator, name, None)
@@ -335,7 +377,7 @@ def patch_reference_discriminators(discriminator, base_function=None, impl="auto
         def make(orig):
             def __init__(self, *args, **kwargs):
                 orig(self, *args, **kwargs)
-                fuse_spectral_norm(self, impl, grad)
+                fuse_spectral_norm(self, impl, grad, pointwise)
             __init__._gfla_fuses_spectral_norm = True
             __init__.__wrapped__ = orig
             __init__.__doc__ = orig.__doc__

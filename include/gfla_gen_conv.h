@@ -45,7 +45,26 @@
  * gfla_gen_conv_bwd_weight: grad_w or grad_b may be NULL (not computed); both NULL -> -1; x and workspace may be NULL
  *           when grad_w is.
  * No atomics: bit-identical from call to call.  Status codes as above: NULL -> -1, the forward's bad shapes -> -2, the
- * forward's limits or B x (pixels of the reduction) beyond 2^31 - 1 -> GFLA_ERR_UNSUPPORTED, nothing is launched. */
+ * forward's limits or B x (pixels of the reduction) beyond 2^31 - 1 -> GFLA_ERR_UNSUPPORTED, nothing is launched.
+ *
+ * ---- 1x1 convolutions (discriminator.py: ResBlockEncoder's pooled shortcut, the final Conv2d(C, 1, 1); base_function.py:
+ * ResBlock's learnable shortcut; csrc/conv1x1.hip, csrc/gen_conv_wgrad.hip) ---------------------------------------------
+ * Functions of their own; the entry points above are untouched and keep refusing any geometry but 0 .. 2.
+ *   p = pool == 2 ? avg_pool2d(x, 2, 2) : pre_act ? leaky_relu(x, pre_slope) : x       rounded to T once
+ *   y = bias + conv1x1(p, w), w (Cout,Cin,1,1); y (B,Cout,H/pool,W/pool), torch's floor: an odd trailing row or column is
+ *       dropped.  The pooled value is the float32 sum ((x00 + x01) + x10) + x11 times 0.25.  No addend.
+ *   grad_x: pool 1: act'(x) sum_co w g; pool 2: 0.25 sum_co w g at the four elements of the block, and ZERO in the trailing
+ *           row / column of an odd H / W, written by the same launch: grad_x may be uninitialised, every element is written.
+ *   grad_w[co][ci] = sum over (b, pixel) of grad_y p, grad_b[co] = sum of grad_y: float32, the split reduction and the
+ *           bias kernel of the gradients above.
+ * `packed`: gfla_conv1x1_packed_bytes bytes, [chunk of 32 / sizeof(T) input channels][Cout padded to 32][chunk];
+ * `packed_grad`: gfla_conv1x1_grad_packed_bytes bytes, the transposed weight, [chunk of OUTPUT channels][Cin padded to
+ * 32][chunk]; `workspace` (bwd_weight only): gfla_conv1x1_bwd_workspace_bytes bytes, uninitialised, 16-byte aligned.
+ * bias may be NULL; bwd_data reads x only with pre_act (NULL is accepted otherwise); bwd_weight: as above.
+ * No atomics: bit-identical from call to call.  NULL -> -1; non-positive sizes, pool other than 1 / 2, pool 2 with H or W
+ * < 2 or with pre_act, src_type or elem_size out of range -> -2; a plane of x beyond 2^31 - 257, B > 65535, more than
+ * 65536 channels or B x (output pixels) beyond 2^31 - 1 -> GFLA_ERR_UNSUPPORTED, nothing is launched.  Additive:
+ * GFLA_ABI_VERSION stays 8. */
 #ifndef GFLA_GEN_CONV_H_
 #define GFLA_GEN_CONV_H_
 
@@ -78,5 +97,28 @@ GFLA_DECL_GEN_CONV_BWD(f32, float)
 GFLA_DECL_GEN_CONV_BWD(f16, uint16_t)
 GFLA_DECL_GEN_CONV_BWD(bf16, uint16_t)
 #undef GFLA_DECL_GEN_CONV_BWD
+
+int64_t gfla_conv1x1_packed_bytes(int64_t Cout, int64_t Cin, int elem_size);
+int64_t gfla_conv1x1_grad_packed_bytes(int64_t Cout, int64_t Cin, int elem_size);
+int64_t gfla_conv1x1_bwd_workspace_bytes(int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int pool,
+                                         int elem_size);
+#define GFLA_DECL_CONV1X1(SFX, T)                                                                                        \
+  int gfla_conv1x1_pack_weights_##SFX(const void *w, int src_type, void *packed, int64_t Cout, int64_t Cin,              \
+                                      gfla_stream_t stream);                                                             \
+  int gfla_conv1x1_pack_grad_weights_##SFX(const void *w, int src_type, void *packed, int64_t Cout, int64_t Cin,         \
+                                           gfla_stream_t stream);                                                        \
+  int gfla_conv1x1_fwd_##SFX(const T *x, const void *packed, const float *bias, T *y, int64_t B, int64_t Cin,            \
+                             int64_t Cout, int64_t H, int64_t W, int pool, int pre_act, double pre_slope,                \
+                             gfla_stream_t stream);                                                                      \
+  int gfla_conv1x1_bwd_data_##SFX(const T *grad_y, const T *x, const void *packed_grad, T *grad_x, int64_t B,            \
+                                  int64_t Cin, int64_t Cout, int64_t H, int64_t W, int pool, int pre_act,                \
+                                  double pre_slope, gfla_stream_t stream);                                               \
+  int gfla_conv1x1_bwd_weight_##SFX(const T *grad_y, const T *x, float *grad_w, float *grad_b, void *workspace,          \
+                                    int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int pool, int pre_act,   \
+                                    double pre_slope, gfla_stream_t stream);
+GFLA_DECL_CONV1X1(f32, float)
+GFLA_DECL_CONV1X1(f16, uint16_t)
+GFLA_DECL_CONV1X1(bf16, uint16_t)
+#undef GFLA_DECL_CONV1X1
 
 #endif /* GFLA_GEN_CONV_H_ */
