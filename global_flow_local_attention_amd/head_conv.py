@@ -26,9 +26,10 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from . import _rewrite
+from ._conv_common import PADDINGS, S1K3, check_conv_args, conv_geometry, param_grad
 
 IMPLS = _lib.IMPLS
-PADDINGS = ("zeros", "reflect")
 POSTS = (None, "tanh", "sigmoid")
 MAX_COUT = 8
 _KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
@@ -49,19 +50,7 @@ def _posts(post, cout):
 
 def _validate(x, weight, bias, padding, pre_slope, post, split):
     """Everything that can be wrong with a call, before anything is launched.  Returns (posts, split or None)."""
-    if x.dim() != 4 or x.numel() == 0:
-        raise ValueError("head_conv3x3: a non-empty (B,Cin,H,W) map (got %s)" % (tuple(x.shape),))
-    if padding not in PADDINGS:
-        raise ValueError("head_conv3x3: padding is one of %s (got %r)" % (PADDINGS, padding))
-    if weight.dim() != 4 or tuple(weight.shape[1:]) != (x.size(1), 3, 3) or weight.size(0) < 1:
-        raise ValueError("head_conv3x3: weight (Cout,Cin,3,3) with Cin = %d (got %s)" % (x.size(1), tuple(weight.shape)))
-    cout = weight.size(0)
-    if bias is not None and tuple(bias.shape) != (cout,):
-        raise ValueError("head_conv3x3: bias (Cout,) = (%d,) (got %s)" % (cout, tuple(bias.shape)))
-    if padding == "reflect" and (x.size(2) < 2 or x.size(3) < 2):
-        raise ValueError("head_conv3x3: reflect padding of one pixel needs H, W >= 2 (got %s)" % (tuple(x.shape),))
-    if pre_slope is not None and not float(pre_slope) >= 0:
-        raise ValueError("head_conv3x3: pre_slope is None or a slope >= 0 (got %r)" % (pre_slope,))
+    cout = check_conv_args("head_conv3x3", x, weight, bias, 3, padding, pre_slope)
     posts = _posts(post, cout)
     if split is not None:
         split = int(split)
@@ -150,11 +139,7 @@ class HeadConv3x3Function(Function):
         _lib.call("gfla_head_conv3x3_bwd_" + _lib.suffix(x, "head_conv3x3"), x, _lib.ptr(x), _lib.ptr(w32), _lib.ptr(y0),
                   _lib.ptr(y1), _lib.ptr(g0), _lib.ptr(g1), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws),
                   B, Cin, cout, c0, H, W, *ctx.conf[1:])
-        if dw is not None and dw.dtype != weight.dtype:
-            dw = dw.to(weight.dtype)
-        if db is not None and db.dtype != ctx.bias_dtype:
-            db = db.to(ctx.bias_dtype)
-        return (dx, dw, db) + none[3:]
+        return (dx, param_grad(dw, weight.dtype), param_grad(db, ctx.bias_dtype)) + none[3:]
 
 
 def _apply_post(s, posts):
@@ -251,29 +236,11 @@ class HeadConv3x3(nn.Module):
             self.in_channels, self.out_channels, self.padding, self.pre_slope, self.post, self.split, self.impl)
 
 
-def _slope_of(module):
-    if type(module) is nn.LeakyReLU:
-        return float(module.negative_slope)
-    if type(module) is nn.ReLU:
-        return 0.0
-    return None
-
-
-def _is_reflect_pad(module):
-    return type(module) is nn.ReflectionPad2d and tuple(module.padding) == (1, 1, 1, 1)
-
-
 def _narrow_conv(module, pad):
-    """a plain nn.Conv2d the op can stand in for: its own Parameters and no hook of any kind (spectral norm recomputes the
-    weight in one; any other would silently stop firing),
-    3x3, stride 1, groups 1, dilation 1, at most MAX_COUT output channels, zero padding `pad`"""
-    if type(module) is not nn.Conv2d or "weight" not in module._parameters:
-        return False
-    if module._forward_pre_hooks or module._forward_hooks or module._backward_hooks or module._backward_pre_hooks:
-        return False            # a hook on the convolution would stop firing once its slot is replaced
-    return (tuple(module.kernel_size) == (3, 3) and tuple(module.stride) == (1, 1) and tuple(module.dilation) == (1, 1)
-            and module.groups == 1 and module.out_channels <= MAX_COUT and tuple(module.padding) == (pad, pad)
-            and (pad == 0 or module.padding_mode == "zeros"))
+    """a plain nn.Conv2d the op can stand in for: its own Parameters and no hook of any kind, 3x3, stride 1, groups 1,
+    dilation 1, at most MAX_COUT output channels, zero padding `pad` (0: behind an nn.ReflectionPad2d(1))"""
+    return conv_geometry(module, pad == 0) == (S1K3, "zeros" if pad else "reflect") and \
+        module.out_channels <= MAX_COUT and _rewrite.plain(module)
 
 
 def _from_conv(conv, padding, pre_slope, post, impl):
@@ -302,12 +269,12 @@ def fuse_output_heads(module, impl="auto"):
         names = list(seq._modules.keys())
         for i, name in enumerate(names):
             prev = seq._modules[names[i - 1]] if i >= 1 else None
-            has_pad = prev is not None and _is_reflect_pad(prev)
+            has_pad = prev is not None and _rewrite.is_reflect_pad(prev)
             if not _narrow_conv(seq._modules[name], 0 if has_pad else 1):
                 continue
             at = i - 1 if has_pad else i
             before = seq._modules[names[at - 1]] if at >= 1 else None
-            slope = _slope_of(before) if before is not None else None
+            slope = _rewrite.slope_of(before, relu=True)
             after = seq._modules[names[i + 1]] if i + 1 < len(names) else None
             post = "tanh" if type(after) is nn.Tanh else "sigmoid" if type(after) is nn.Sigmoid else None
             seq._modules[name] = _from_conv(seq._modules[name], "reflect" if has_pad else "zeros", slope, post, impl)
@@ -367,36 +334,16 @@ def patch_reference_flow_heads(generator_module, impl="auto"):
     """Replace `attn_output` of the reference's PoseFlowNet, FaceFlowNet and ShapeNetFlowNet (generator.py:237-242,
     578-585, 743-749: `output{i}` and `mask{i}` applied to the same tensor) with flow_mask_heads.  Idempotent.  Returns
     the names of the classes patched."""
-    patched = []
-    for name in _REFERENCE_FLOW_NETS:
-        cls = getattr(generator_module, name, None)
-        if cls is None or "attn_output" not in cls.__dict__:
-            continue
-        if not getattr(cls.attn_output, "_gfla_fused_heads", False):
-            def attn_output(self, out, i):
-                return flow_mask_heads(out, getattr(self, "output" + str(i)), getattr(self, "mask" + str(i)), impl)
-            attn_output._gfla_fused_heads = True
-            attn_output.__wrapped__ = cls.attn_output
-            cls.attn_output = attn_output
-        patched.append(name)
-    return patched
+    def make(orig):
+        def attn_output(self, out, i):
+            return flow_mask_heads(out, getattr(self, "output" + str(i)), getattr(self, "mask" + str(i)), impl)
+        return attn_output
+    return [name for name in _REFERENCE_FLOW_NETS
+            if _rewrite.wrap_method(getattr(generator_module, name, None), "attn_output", "_gfla_fused_heads", make)]
 
 
 def patch_reference_outputs(base_function, impl="auto"):
     """Wrap the constructor of the reference's `Output` so that every image head built from now on comes out fused
     (fuse_output_heads on the finished module).  Idempotent.  Returns True when the class was found."""
-    cls = getattr(base_function, "Output", None)
-    if cls is None:
-        return False
-    init = cls.__dict__.get("__init__")
-    if init is None or getattr(init, "_gfla_fuses_heads", False):
-        return init is not None
-
-    def __init__(self, *args, **kwargs):
-        init(self, *args, **kwargs)
-        fuse_output_heads(self, impl)
-    __init__._gfla_fuses_heads = True
-    __init__.__wrapped__ = init
-    __init__.__doc__ = init.__doc__
-    cls.__init__ = __init__
-    return True
+    return _rewrite.wrap_init(getattr(base_function, "Output", None), "_gfla_fuses_heads",
+                              lambda self: fuse_output_heads(self, impl))

@@ -18,6 +18,8 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from . import _rewrite
+from ._conv_common import param_grad
 
 IMPLS = _lib.IMPLS
 
@@ -110,11 +112,8 @@ class InstanceNormActFunction(Function):
         _lib.call("gfla_instance_norm_bwd_" + _lib.suffix(x, "instance_norm_act"), x, _lib.ptr(x), _lib.ptr(grad_y),
                   _lib.ptr(w), _lib.ptr(b), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
                   _lib.ptr(ws), B, C, H, W, ctx.slope, ctx.act)
-        if dw is not None and dw.dtype != weight.dtype:
-            dw = dw.to(weight.dtype)
-        if db is not None and db.dtype != bias.dtype:
-            db = db.to(bias.dtype)
-        return dx, dw, db, None, None
+        return (dx, param_grad(dw, weight.dtype if need_w else None), param_grad(db, bias.dtype if need_b else None),
+                None, None)
 
 
 def torch_instance_norm_act(x, weight=None, bias=None, eps=1e-5, negative_slope=None):
@@ -190,15 +189,6 @@ class InstanceNormAct(nn.Module):
                                                                     self.negative_slope, self.impl)
 
 
-def _slope_of(module):
-    """negative slope of an activation the op can absorb, else None (so: (True, slope) / (False, None))"""
-    if type(module) is nn.LeakyReLU:
-        return True, float(module.negative_slope)
-    if type(module) is nn.ReLU:
-        return True, 0.0
-    return False, None
-
-
 def _fusable_norm(module):
     return type(module) is nn.InstanceNorm2d and not module.track_running_stats
 
@@ -227,9 +217,9 @@ def fuse_instance_norm_act(module, impl="auto"):
             if not _fusable_norm(norm):
                 continue
             nxt = names[i + 1] if i + 1 < len(names) else None
-            is_act, slope = _slope_of(seq._modules[nxt]) if nxt is not None else (False, None)
+            slope = _rewrite.slope_of(seq._modules[nxt], relu=True) if nxt is not None else None
             seq._modules[name] = _from_norm(norm, slope, impl)
-            if is_act:
+            if slope is not None:
                 seq._modules[nxt] = nn.Identity()
                 pairs += 1
     return pairs
@@ -251,24 +241,13 @@ def patch_reference_blocks(base_function, impl="auto"):
         init = cls.__dict__.get("__init__")
         if init is None:
             continue
-        if getattr(init, "_gfla_fuses_instance_norm", False):
-            wrapped.append(name)
-            continue
-        try:
-            takes_norm = "norm_layer" in inspect.signature(init).parameters
-        except (TypeError, ValueError):
-            takes_norm = False
-        if not (takes_norm or name in _REFERENCE_BLOCKS):
-            continue
-
-        def make(orig):
-            def __init__(self, *args, **kwargs):
-                orig(self, *args, **kwargs)
-                fuse_instance_norm_act(self, impl)
-            __init__._gfla_fuses_instance_norm = True
-            __init__.__wrapped__ = orig
-            __init__.__doc__ = orig.__doc__
-            return __init__
-        cls.__init__ = make(init)
+        if not getattr(init, "_gfla_fuses_instance_norm", False):
+            try:
+                takes_norm = "norm_layer" in inspect.signature(init).parameters
+            except (TypeError, ValueError):
+                takes_norm = False
+            if not (takes_norm or name in _REFERENCE_BLOCKS):
+                continue
+        _rewrite.wrap_init(cls, "_gfla_fuses_instance_norm", lambda self: fuse_instance_norm_act(self, impl))
         wrapped.append(name)
     return wrapped

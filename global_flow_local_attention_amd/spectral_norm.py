@@ -24,10 +24,11 @@ import torch.nn.functional as F
 from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
-from torch.nn.utils.spectral_norm import SpectralNorm as _TorchSpectralNorm
 
 from . import _lib
+from . import _rewrite
 from . import gen_conv as _gc
+from ._conv_common import P1K1, S1K3, S2K4, check_grad, conv_geometry
 
 POINTWISE = ("torch", "kernels")
 _TABLE_CACHE = {}
@@ -161,39 +162,9 @@ def spectral_normalize(weights, us, vs, power_iterations=1, eps=1e-12, impl="aut
     return [torch_spectral_normalize(w, u, v, int(power_iterations), float(eps)) for w, u, v in zip(weights, us, vs)]
 
 
-def _torch_hook(module):
-    """the SpectralNorm hook object of a convolution that carries exactly that one hook, or None"""
-    hooks = list(module._forward_pre_hooks.values())
-    if len(hooks) != 1 or type(hooks[0]) is not _TorchSpectralNorm:
-        return None
-    if module._forward_hooks or module._backward_hooks or module._backward_pre_hooks:
-        return None
-    hook = hooks[0]
-    if hook.name != "weight" or hook.dim != 0 or "weight_orig" not in module._parameters:
-        return None
-    return hook
-
-
-def _geometry_of(conv):
-    if conv.groups != 1 or tuple(conv.dilation) != (1, 1) or conv.padding_mode != "zeros":
-        return None
-    k, s, p = tuple(conv.kernel_size), tuple(conv.stride), conv.padding
-    if k == (3, 3) and s == (1, 1) and p == (1, 1):
-        return _gc.S1K3
-    if k == (4, 4) and s == (2, 2) and p == (1, 1):
-        return _gc.S2K4
-    return None
-
-
 def _check_pointwise(pointwise):
     if pointwise not in POINTWISE:
         raise ValueError("pointwise: one of %s (got %r)" % (POINTWISE, pointwise))
-
-
-def _is_pointwise(conv):
-    """Conv2d(k 1, s 1, p 0), groups 1, dilation 1: what gen_conv.conv1x1 computes"""
-    return conv.groups == 1 and tuple(conv.dilation) == (1, 1) and tuple(conv.kernel_size) == (1, 1) and \
-        tuple(conv.stride) == (1, 1) and conv.padding in ((0, 0), 0)
 
 
 def _is_pool2(module):
@@ -220,17 +191,18 @@ class SpectralConv(nn.Module):
     def __init__(self, conv, pre_slope=None, impl="auto", grad="torch", pointwise="torch", pool=1):
         super(SpectralConv, self).__init__()
         _lib.check_impl(impl)
-        _gc._check_grad(grad)
+        check_grad(grad)
         _check_pointwise(pointwise)
-        hook = _torch_hook(conv)
+        hook = _rewrite.spectral_norm_hook(conv)
         if type(conv) is not nn.Conv2d or hook is None:
             raise ValueError("SpectralConv: an nn.Conv2d under torch.nn.utils.spectral_norm (name 'weight', dim 0) and no "
                              "other hook")
         self.impl, self.grad = impl, grad
         self.pre_slope = None if pre_slope is None else float(pre_slope)
         self.n_power_iterations, self.eps = int(hook.n_power_iterations), float(hook.eps)
-        self.geometry = _geometry_of(conv)
-        self.pointwise = pointwise == "kernels" and _is_pointwise(conv)
+        geometry = (conv_geometry(conv) or (None,))[0]
+        self.geometry = geometry if geometry in (S1K3, S2K4) else None
+        self.pointwise = pointwise == "kernels" and geometry == P1K1
         if pool not in _gc.POOLS or (pool == 2 and (not self.pointwise or pre_slope is not None)):
             raise ValueError("SpectralConv: pool is 1, or 2 on a 1x1 convolution with pointwise='kernels' and no pre_slope "
                              "(got %r)" % (pool,))
@@ -259,16 +231,14 @@ class SpectralConv(nn.Module):
 
     def forward(self, x, add=None):
         weight = self.normalized_weight()
-        if self.geometry == _gc.S1K3:
-            return _gc.conv3x3(x, weight, self.bias, "zeros", self.pre_slope, add, self.impl, self.grad)
-        if self.geometry == _gc.S2K4:
-            return _gc.conv4x4_down(x, weight, self.bias, self.pre_slope, self.impl, self.grad, add=add)
-        if self.pointwise:
-            y = _gc.conv1x1(x, weight, self.bias, self.pre_slope, self.pool, self.impl, self.grad)
-            return y if add is None else y + add
-        a = x if self.pre_slope is None else F.leaky_relu(x, self.pre_slope)
-        y = self.original._conv_forward(a, weight, self.bias)
-        return y if add is None else y + add
+        geometry = P1K1 if self.pointwise else self.geometry
+
+        def own(x):                      # the convolution's own arithmetic on the normalised weight
+            a = x if self.pre_slope is None else F.leaky_relu(x, self.pre_slope)
+            return self.original._conv_forward(a, weight, self.bias)
+        # a geometry of the kernels runs as its functional form does; only the others need the convolution's own
+        return _gc.run(geometry, x, weight, self.bias, "zeros", self.pre_slope, add, self.pool, self.impl, self.grad,
+                       own if geometry is None else None)
 
     def extra_repr(self):
         c = self.original
@@ -304,7 +274,7 @@ def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch"):
     default "torch" leaves the 1x1 convolutions on F.conv2d and every pool in place.
     Returns the number of convolutions rewritten."""
     _lib.check_impl(impl)
-    _gc._check_grad(grad)
+    check_grad(grad)
     _check_pointwise(pointwise)
     replaced = {}
     for parent in list(net.modules()):
@@ -313,22 +283,17 @@ def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch"):
         names = list(parent._modules.keys())
         for i, name in enumerate(names):
             conv = parent._modules[name]
-            if type(conv) is not nn.Conv2d or id(conv) in replaced or _torch_hook(conv) is None:
+            if type(conv) is not nn.Conv2d or id(conv) in replaced or _rewrite.spectral_norm_hook(conv) is None:
                 continue
-            slope, pool = None, 1
             before = parent._modules[names[i - 1]] if isinstance(parent, nn.Sequential) and i >= 1 else None
-            if type(before) is nn.LeakyReLU:
-                slope = float(before.negative_slope)
-                parent._modules[names[i - 1]] = nn.Identity()
-            elif pointwise == "kernels" and _is_pointwise(conv) and _is_pool2(before):
-                pool = 2
+            slope = _rewrite.slope_of(before, relu=False)
+            pool = 2 if slope is None and pointwise == "kernels" and conv_geometry(conv) == (P1K1, "zeros") and \
+                _is_pool2(before) else 1
+            if slope is not None or pool == 2:
                 parent._modules[names[i - 1]] = nn.Identity()
             replaced[id(conv)] = (conv, SpectralConv(conv, slope, impl, grad, pointwise, pool))
             parent._modules[name] = replaced[id(conv)][1]
-    for m in net.modules():                                  # the same convolution under another name
-        for name, sub in m._modules.items():
-            if sub is not None and id(sub) in replaced and replaced[id(sub)][0] is sub:
-                m._modules[name] = replaced[id(sub)][1]
+    _rewrite.replace_aliases(net, replaced)
     if replaced and not getattr(net, "_gfla_spectral_norm_hooks", None):
         def before(module, inputs):
             convs = [m for m in module.modules() if type(m) is SpectralConv]
@@ -344,13 +309,6 @@ def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch"):
     return len(replaced)
 
 
-def _run_with_add(seq, x, add):
-    mods = list(seq)
-    for m in mods[:-1]:
-        x = m(x)
-    return mods[-1](x, add)
-
-
 _REFERENCE_DISCRIMINATORS = ("ResDiscriminator", "PatchDiscriminator", "TemporalDiscriminator")
 
 
@@ -362,41 +320,21 @@ def patch_reference_discriminators(discriminator, base_function=None, impl="auto
     on the 4x4 stride-2 kernels; otherwise it calls the original forward.  pointwise: fuse_spectral_norm's.  Idempotent.
     Returns the names of the classes wrapped."""
     _lib.check_impl(impl)
-    _gc._check_grad(grad)
+    check_grad(grad)
     _check_pointwise(pointwise)
-    wrapped = []
-    for name in _REFERENCE_DISCRIMINATORS:
-        cls = getattr(discriminator, name, None)
-        init = None if cls is None else cls.__dict__.get("__init__")
-        if init is None:
-            continue
-        wrapped.append(name)
-        if getattr(init, "_gfla_fuses_spectral_norm", False):
-            continue
+    wrapped = [name for name in _REFERENCE_DISCRIMINATORS
+               if _rewrite.wrap_init(getattr(discriminator, name, None), "_gfla_fuses_spectral_norm",
+                                     lambda self: fuse_spectral_norm(self, impl, grad, pointwise))]
 
-        def make(orig):
-            def __init__(self, *args, **kwargs):
-                orig(self, *args, **kwargs)
-                fuse_spectral_norm(self, impl, grad, pointwise)
-            __init__._gfla_fuses_spectral_norm = True
-            __init__.__wrapped__ = orig
-            __init__.__doc__ = orig.__doc__
-            return __init__
-        cls.__init__ = make(init)
+    def make_forward(orig):
+        def forward(self, x):
+            seq = self.model
+            last = seq[len(seq) - 1] if isinstance(seq, nn.Sequential) and len(seq) else None
+            if type(last) is not SpectralConv or last.geometry != S2K4:
+                return orig(self, x)
+            return _rewrite.run_with_add(seq, x, self.shortcut(x))
+        return forward
     cls = None if base_function is None else getattr(base_function, "ResBlockEncoder", None)
-    if cls is not None and "forward" in cls.__dict__ and not getattr(cls.__dict__["forward"], "_gfla_residual_in_epilogue", False):
+    if _rewrite.wrap_method(cls, "forward", "_gfla_residual_in_epilogue", make_forward):
         wrapped.append("ResBlockEncoder")
-
-        def make_forward(orig):
-            def forward(self, x):
-                seq = self.model
-                last = seq[len(seq) - 1] if isinstance(seq, nn.Sequential) and len(seq) else None
-                if type(last) is not SpectralConv or last.geometry != _gc.S2K4:
-                    return orig(self, x)
-                return _run_with_add(seq, x, self.shortcut(x))
-            forward._gfla_residual_in_epilogue = True
-            forward.__wrapped__ = orig
-            forward.__doc__ = orig.__doc__
-            return forward
-        cls.forward = make_forward(cls.__dict__["forward"])
     return wrapped

@@ -14,7 +14,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._conv_common import SFX as _SFX, SRC_TYPE as _SRC_TYPE, autocast_dtype, cached, rounded_bias
+from ._conv_common import SFX as _SFX, SRC_TYPE as _SRC_TYPE, autocast_dtype, packed, rounded_bias
 
 IMPLS = _lib.IMPLS
 
@@ -33,15 +33,7 @@ LAYERS = tuple(name for name, _ in _SLICES)
 def packed_weights(weight, dtype, layout):
     """`weight` (Cout,Cin,3,3) packed for the kernels in compute type `dtype`: layout 0 for the forward, 1 for the data
     gradient (taps mirrored, Cin and Cout swapped).  Cached per parameter: a frozen network packs once."""
-    def make():
-        w = weight.detach().contiguous()
-        cout, cin = w.shape[:2]
-        esize = torch.empty((), dtype=dtype).element_size()
-        packed = _lib.workspace("gfla_conv3x3_packed_bytes", w, cout, cin, layout, esize, what="conv3x3 packed weights")
-        _lib.call("gfla_conv3x3_pack_weights_" + _SFX[dtype], w, _lib.ptr(w), _SRC_TYPE[w.dtype], _lib.ptr(packed), cout, cin,
-                  layout)
-        return packed
-    return cached(weight, "w%d" % layout, dtype, make)
+    return packed(weight, dtype, "w%d" % layout, "gfla_conv3x3_packed_bytes", "gfla_conv3x3_pack_weights_", (layout,))
 
 
 class Conv3x3ReluFunction(Function):

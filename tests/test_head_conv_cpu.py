@@ -181,6 +181,10 @@ def test_fuse_output_heads(gfla):
     for k, v in want.items():
         assert (net[k](x) - v).abs().max().item() <= 1e-6, k
     assert gfla.fuse_output_heads(net, impl="torch") == 0                               # again: nothing more
+    relu = nn.Sequential(nn.ReLU(), nn.Conv2d(6, 2, 3, 1, 1))                           # an nn.ReLU is folded in as slope 0
+    want_relu = relu(x)
+    assert gfla.fuse_output_heads(relu, impl="torch") == 1 and type(relu[0]) is nn.Identity and relu[1].pre_slope == 0.0
+    assert torch.equal(relu(x), want_relu)
     # a fused mask head still pairs with its flow convolution
     flow = nn.Conv2d(6, 2, 3, 1, 1)
     f, m = gfla.flow_mask_heads(x, flow, net["mask"], impl="torch")

@@ -76,6 +76,11 @@ def test_what_is_left_alone(gfla):
     assert net[5] is shared                                                       # the object's other slot is untouched
     assert type(net[0].conv) is nn.Conv2d and type(net[1]) is nn.ConvTranspose2d and net[2] is twice
     assert type(net[6]) is nn.Conv2d
+    # only an nn.LeakyReLU is folded in, and a second registration of a rewritten convolution gets the same module
+    again = nn.Sequential(nn.ReLU(), sn(nn.Conv2d(4, 4, 3, 1, 1)))
+    again.alias = again[1]
+    assert gfla.fuse_spectral_norm(again) == 1 and type(again[0]) is nn.ReLU
+    assert type(again[1]) is gfla.SpectralConv and again[1].pre_slope is None and again.alias is again[1]
     with pytest.raises(ValueError):
         gfla.SpectralConv(nn.Conv2d(4, 4, 3))
     with pytest.raises(ValueError):
