@@ -64,26 +64,27 @@ class MaxCosineFunction(Function):
             return None, None, None
         half = source.dtype in _lib.HALF_TYPES
         with torch.enable_grad():
-            s = source.detach().requires_grad_(need_s and not half)
-            t = target.detach().requires_grad_(need_t and not half)
-            gather_at = index.long().unsqueeze(1).expand(-1, s.size(1), -1)
-            winners = torch.gather(s, 2, gather_at)
-            if half:
-                # the winners are gathered in the storage type (no float32 copy of the source map); from there on
-                # float32, with the winners and the target as the leaves
-                winners, t = winners.float().requires_grad_(need_s), t.float().requires_grad_(need_t)
-                leaf_s = winners
-            else:
-                leaf_s = s
+            # the winners are gathered in the storage type (no float32 copy of a 16-bit source map); from there on
+            # float32, with the winners and the target as the leaves
+            gather_at = index.long().unsqueeze(1).expand(-1, source.size(1), -1)
+            winners = torch.gather(source.detach(), 2, gather_at).float().requires_grad_(need_s)
+            t = target.detach().float().requires_grad_(need_t)
+            leaf_s = winners
             winners = winners / (winners.norm(dim=1, keepdim=True) + ctx.eps)
             t_unit = t / (t.norm(dim=1, keepdim=True) + ctx.eps)
             best = (winners * t_unit).sum(1)
             wanted = [x for x, need in ((leaf_s, need_s), (t, need_t)) if need]
-            grads = list(torch.autograd.grad(best, wanted, grad_best.float() if half else grad_best))
+            grads = list(torch.autograd.grad(best, wanted, grad_best.float()))
+        if need_s:
+            # Route the winners' gradients to their source positions: float32 sums, one rounding at the end.  The positions
+            # that won nothing get 0 -- or NaN where the reference gets NaN: its bmm multiplies their zero gradient with
+            # EVERY normalised target position, so one non-finite target position makes the whole sample's source gradient
+            # NaN (0 x NaN).  The sums start from that value: 0, or NaN for such a sample (the normalised target has entries
+            # of at most 1 and NaN for a non-finite position, so its sum is NaN exactly then).
+            taint = (t_unit.detach().sum(dim=(1, 2)) * 0).view(-1, 1, 1)
+            g_src = taint.expand(source.shape).contiguous()
+            grads[0] = g_src.scatter_add_(2, gather_at, grads[0])
         if half:
-            if need_s:   # route the winners' gradients to their source positions: float32 sums, one rounding at the end
-                g_src = torch.zeros(source.shape, dtype=torch.float32, device=source.device)
-                grads[0] = g_src.scatter_add_(2, gather_at, grads[0])
             grads = [g.to(source.dtype) for g in grads]
         return (grads.pop(0) if need_s else None), (grads.pop(0) if need_t else None), None
 

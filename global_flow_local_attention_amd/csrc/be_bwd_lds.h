@@ -118,9 +118,9 @@ __global__ __launch_bounds__(kLdsThreads) void be_bwd_lds_kernel(
       const A dx = (fx0 + (A)(t - K / 2)) + (A)xf;  // block_extractor_kernel.cu:132-136
       const A dy = (fy0 + (A)(t - K / 2)) + (A)yf;
       const A fdx = floor_t<A>(dx), fdy = floor_t<A>(dy);
-      if (t == 0) {
-        x0 = (int)fdx;
-        y0 = (int)fdy;
+      if (t == 0) {   // clamped far outside any map: x0 + q and y0 + K + 1 below stay defined for an inf or 1e30 flow, whose
+        x0 = clampi((int)fdx, -(1 << 20), 1 << 20);   // conversion saturates (y0 +- k would wrap, and the window test with it)
+        y0 = clampi((int)fdy, -(1 << 20), 1 << 20);
       }
       dense = dense && ((int)fdx == x0 + t) && ((int)fdy == y0 + t);
       xL[t] = clampi((int)fdx, 0, Ws - 1);

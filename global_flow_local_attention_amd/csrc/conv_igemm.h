@@ -37,7 +37,7 @@
 //   kCvGen     y = bias + conv(act(x), w) (+ add); act = identity | LeakyReLU(slope), rounded to T once while staged;
 //              bias and add may be NULL; the addend is read by the lane that writes the same element, so add == y is allowed
 //   kCvVggFwd  y = max(0, bias + conv(x, w)), S1K3 only
-//   kCvVggBwd  dx = conv(g [ysaved > 0], w), S1K3 only, the weights packed mirrored with Cin <-> Cout (the extractor is
+//   kCvVggBwd  dx = conv(g [not ysaved <= 0], w), S1K3 only, the weights packed mirrored with Cin <-> Cout (the extractor is
 //              frozen: no weight gradient); no bias, no ReLU
 //   kCvGrad    dx = act'(x) conv(g, w) on the adjoint geometry, the weights packed for it: S1K3 mirrored with Cin <-> Cout,
 //              S2K3 (the adjoint of T2K3: k 3, s 2, p 1, halo (2 TH + 1) x (2 TW + 1), the taps as stored) and U2K4 (the
@@ -196,8 +196,8 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
   auto element = [&](int c, int off) -> uint32_t {
     if (c >= Cin) return 0u;
     const int64_t at = (int64_t)c * plane + off;
-    if constexpr (V == kCvVggBwd) {                                           // the ReLU mask of the saved output
-      if (!(Num<T>::ld(aux + (xb - x) + at) > 0.f)) return 0u;
+    if constexpr (V == kCvVggBwd) {       // the ReLU mask of the saved output; a NaN output passes its gradient on, as
+      if (Num<T>::ld(aux + (xb - x) + at) <= 0.f) return 0u;                  // torch's threshold_backward does (y <= 0 ? 0 : g)
     }
     if constexpr (V == kCvGen) {
       if (pre_act) {
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
           const int64_t at = (int64_t)co * oplane + (int64_t)gy * Wout + gx;
           float v = acc[i][j][r];
           if constexpr (V == kCvGen || V == kCvVggFwd) v += b;
-          if constexpr (V == kCvVggFwd) v = fmaxf(v, 0.f);
+          if constexpr (V == kCvVggFwd) v = v < 0.f ? 0.f : v;   // (not fmaxf: a NaN stays a NaN, as torch.relu's)
           if constexpr (V == kCvGrad) {              // act'(x) of the element this lane writes: x > 0 ? 1 : slope
             if (ab && pre_act && !(Num<T>::ld(ab + at) > 0.f)) v *= slope;
           } else {

@@ -288,6 +288,11 @@ __global__ __launch_bounds__(256) void fc_tail_bwd_kernel(
     fx_l = flow[(b * 2 + 0) * HW + pw0 + (lane & (kWalk - 1))];
     fy_l = flow[(b * 2 + 1) * HW + pw0 + (lane & (kWalk - 1))];
   }
+  // A non-finite flow makes the corner weights NaN, and fc_scatter_own_kernel's fixed-point cells cannot hold a NaN any
+  // more than a non-finite d hidden (lds_plane.h): the slot that carries max |d hidden| carries the flow's finiteness too.
+  if (amax_d && __any(!(fabsf(fx_l) < INFINITY) || !(fabsf(fy_l) < INFINITY))) {
+    if (lane == 0) atomicMax(amax_d, 0x7fc00000u);
+  }
   Corner cn;
   float gn[8];
   auto issue = [&](int it) {

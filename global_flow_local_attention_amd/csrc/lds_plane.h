@@ -220,6 +220,11 @@ __device__ __forceinline__ void flush_planes(T *__restrict__ g, const lds_acc_t 
 // exactly associative: the result does not depend on the order the lanes arrive in (bit-reproducible run to run, which
 // neither the reference's float atomics nor the double planes guarantee).  A non-finite gradient cannot be represented:
 // the workgroup then writes NaN to the planes it owns (the reference would poison only the taps the value reaches).
+// Neither can a non-finite WEIGHT (a NaN or inf flow makes the bilinear weights NaN): lds_add_fix would add the NaN's bit
+// pattern as an integer and the flush would write a finite value.  The two users whose weights come from a flow look for
+// it: fc_tail_bwd_kernel folds the flow's finiteness into the maximum that fc_scatter_own_kernel scales by, and
+// resample2d's rs_bwd1_apply_fix raises a flag in LDS for a pixel with non-finite weights, which makes the flush write NaN
+// ("Non-finite values").
 using lds_fix_t = long long;
 struct FixScale {
   float up;      // contributions are multiplied by this power of two before the conversion

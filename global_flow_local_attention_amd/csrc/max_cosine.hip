@@ -44,42 +44,75 @@ __device__ __forceinline__ float unpack_best(unsigned long long key, int *idx) {
 
 // out[b, n] = 1 / (sqrt(sum_c x[b, c, n]^2) + eps): lanes along n (coalesced), 4 channel slices; float32 sums whatever
 // the storage type T (float, f16_t, bf16_t).
-// keys != NULL: also reset the packed maxima of these positions.
+// keys != NULL (the target map): also reset the packed maxima of these positions and the sample's first_bad slot.
+//
+// Non-finite features.  In the reference a position with a NaN or an inf among its channels normalises to a vector with
+// a NaN in it (x / (|x| + eps): NaN / NaN, inf / inf), so every similarity it takes part in is NaN, and torch.max
+// returns NaN at the FIRST NaN of a column.  The similarity of two finite positions is finite, hence: a column is NaN
+// iff its target position is bad (first NaN: row 0) or the sample has a bad source position (first NaN: the first such
+// row).  Both are known here, and nothing in the MFMA kernels' loops has to look for a NaN: a bad position gets the
+// scale NaN -- its similarities are NaN and are never merged (val > best is false) --, the first bad source position
+// of a sample goes to first_bad[b] (keys == NULL: the source map), and max_cosine_finish_kernel puts the NaN and its
+// index in place.  Only a sum that is not finite is looked at again, channel by channel: a sum that merely overflowed
+// (all features finite) keeps the scale 0 it always had.
 template <typename T>
 __global__ __launch_bounds__(256) void inv_norm_kernel(const T *__restrict__ x, float *__restrict__ out,
-                                                      unsigned long long *__restrict__ keys, int C, int N,
-                                                      float eps) {
+                                                      unsigned long long *__restrict__ keys,
+                                                      int *__restrict__ first_bad, int C, int N, float eps) {
   __shared__ float part[4][64];
   const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
   const int n = blockIdx.x * 64 + lane;
   const int64_t b = blockIdx.y;
+  const T *p = x + b * C * (int64_t)N + min(n, N - 1);
   float s = 0.f;
   if (n < N) {
-    const T *p = x + b * C * (int64_t)N + n;
     for (int c = slice; c < C; c += 4) {
       const float v = Num<T>::ld(p + (int64_t)c * N);
       s = fmaf(v, v, s);
     }
   }
   part[slice][lane] = s;
+  if (keys && blockIdx.x == 0 && threadIdx.x == 0) first_bad[b] = 0x7fffffff;
   __syncthreads();
   if (slice == 0 && n < N) {
     s = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-    out[b * N + n] = 1.f / (sqrtf(s) + eps);
+    float r = 1.f / (sqrtf(s) + eps);
+    if (!(s < INFINITY)) {
+      bool bad = false;
+      for (int c = 0; c < C; ++c) bad |= !(fabsf(Num<T>::ld(p + (int64_t)c * N)) < INFINITY);
+      if (bad) {
+        r = __uint_as_float(0x7fc00000u);
+        if (!keys) atomicMin(&first_bad[b], n);
+      }
+    }
+    out[b * N + n] = r;
     if (keys) keys[b * N + n] = 0ull;
   }
 }
 
+// keys -> (best, index).  A column that merged no key (every similarity NaN), a bad target position and a sample with
+// a bad source position come out NaN at the index torch.max gives (see inv_norm_kernel); the index is in [0, Ns) always.
 __global__ __launch_bounds__(256) void max_cosine_finish_kernel(const unsigned long long *__restrict__ keys,
                                                                const float *__restrict__ rt,
+                                                               const int *__restrict__ first_bad,
                                                                float *__restrict__ out_max, int *__restrict__ out_idx,
-                                                               int64_t n) {
+                                                               int64_t n, int Ns, int Nt) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   int idx;
-  const float v = unpack_best(keys[i], &idx);
-  out_max[i] = v * rt[i];
-  if (out_idx) out_idx[i] = idx;
+  const unsigned long long key = keys[i];
+  const float scale = rt[i];
+  float v = unpack_best(key, &idx) * scale;
+  const int fb = first_bad[i / Nt];
+  if (scale != scale || key == 0ull) {
+    v = __uint_as_float(0x7fc00000u);
+    idx = 0;
+  } else if (fb < Ns) {
+    v = __uint_as_float(0x7fc00000u);
+    idx = fb;
+  }
+  out_max[i] = v;
+  if (out_idx) out_idx[i] = min(max(idx, 0), Ns - 1);
 }
 
 // Four consecutive floats of one channel row.  FAST (rows 16-byte aligned, N % 4 == 0, C % KC == 0): one
@@ -294,11 +327,13 @@ static int max_cosine(const float *source, const float *target, void *workspace,
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws);
   float *inv_t = reinterpret_cast<float *>(ws + align16(8 * B * Nt));
   float *inv_s = reinterpret_cast<float *>(ws + align16(8 * B * Nt) + align16(4 * B * Nt));
+  int *first_bad = reinterpret_cast<int *>(ws + align16(8 * B * Nt) + align16(4 * B * Nt) + align16(4 * B * Ns));
 
-  inv_norm_kernel<float><<<dim3((unsigned)ceil_div(Ns, 64), (unsigned)B), 256, 0, stream>>>(source, inv_s, nullptr, (int)C,
-                                                                                    (int)Ns, (float)eps);
-  inv_norm_kernel<float><<<dim3((unsigned)ceil_div(Nt, 64), (unsigned)B), 256, 0, stream>>>(target, inv_t, keys, (int)C,
-                                                                                    (int)Nt, (float)eps);
+  // the target map first: it resets first_bad, which the source map's pass then lowers
+  inv_norm_kernel<float><<<dim3((unsigned)ceil_div(Nt, 64), (unsigned)B), 256, 0, stream>>>(target, inv_t, keys, first_bad,
+                                                                                    (int)C, (int)Nt, (float)eps);
+  inv_norm_kernel<float><<<dim3((unsigned)ceil_div(Ns, 64), (unsigned)B), 256, 0, stream>>>(source, inv_s, nullptr, first_bad,
+                                                                                    (int)C, (int)Ns, (float)eps);
   const int64_t per_xcd = ceil_div(total, kNumXCD);
   const dim3 grid((unsigned)(per_xcd * kNumXCD));
   const bool fast = C % 32 == 0 && Ns % 4 == 0 && Nt % 4 == 0 && Ns >= 4 && Nt >= 4 &&
@@ -314,8 +349,8 @@ static int max_cosine(const float *source, const float *target, void *workspace,
   else
     GFLA_MC_LAUNCH(false, 32, 8);
 #undef GFLA_MC_LAUNCH
-  max_cosine_finish_kernel<<<dim3((unsigned)ceil_div(B * Nt, 256)), 256, 0, stream>>>(keys, inv_t, out_max, out_idx,
-                                                                                     B * Nt);
+  max_cosine_finish_kernel<<<dim3((unsigned)ceil_div(B * Nt, 256)), 256, 0, stream>>>(keys, inv_t, first_bad, out_max,
+                                                                                     out_idx, B * Nt, (int)Ns, (int)Nt);
   return launch_status();
 }
 
@@ -594,11 +629,12 @@ static int max_cosine16(const uint16_t *source, const uint16_t *target, void *wo
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws);
   float *inv_t = reinterpret_cast<float *>(ws + align16(8 * B * Nt));
   float *inv_s = reinterpret_cast<float *>(ws + align16(8 * B * Nt) + align16(4 * B * Nt));
+  int *first_bad = reinterpret_cast<int *>(ws + align16(8 * B * Nt) + align16(4 * B * Nt) + align16(4 * B * Ns));
   const T *src_t = reinterpret_cast<const T *>(source), *tgt_t = reinterpret_cast<const T *>(target);
-  inv_norm_kernel<T><<<dim3((unsigned)ceil_div(Ns, 64), (unsigned)B), 256, 0, stream>>>(src_t, inv_s, nullptr, (int)C,
-                                                                                       (int)Ns, (float)eps);
-  inv_norm_kernel<T><<<dim3((unsigned)ceil_div(Nt, 64), (unsigned)B), 256, 0, stream>>>(tgt_t, inv_t, keys, (int)C,
-                                                                                       (int)Nt, (float)eps);
+  inv_norm_kernel<T><<<dim3((unsigned)ceil_div(Nt, 64), (unsigned)B), 256, 0, stream>>>(tgt_t, inv_t, keys, first_bad,
+                                                                                       (int)C, (int)Nt, (float)eps);
+  inv_norm_kernel<T><<<dim3((unsigned)ceil_div(Ns, 64), (unsigned)B), 256, 0, stream>>>(src_t, inv_s, nullptr, first_bad,
+                                                                                       (int)C, (int)Ns, (float)eps);
   const int64_t per_xcd = ceil_div(total, kNumXCD);
   const dim3 grid((unsigned)(per_xcd * kNumXCD));
   const bool fast = Ns % 8 == 0 && Nt % 8 == 0 && Ns >= 8 && Nt >= 8 &&
@@ -621,8 +657,8 @@ static int max_cosine16(const uint16_t *source, const uint16_t *target, void *wo
     else GFLA_MC16_LAUNCH(false, 128);
   }
 #undef GFLA_MC16_LAUNCH
-  max_cosine_finish_kernel<<<dim3((unsigned)ceil_div(B * Nt, 256)), 256, 0, stream>>>(keys, inv_t, out_max, out_idx,
-                                                                                     B * Nt);
+  max_cosine_finish_kernel<<<dim3((unsigned)ceil_div(B * Nt, 256)), 256, 0, stream>>>(keys, inv_t, first_bad, out_max,
+                                                                                     out_idx, B * Nt, (int)Ns, (int)Nt);
   return launch_status();
 }
 
@@ -631,7 +667,7 @@ static int max_cosine16(const uint16_t *source, const uint16_t *target, void *wo
 extern "C" {
 int64_t gfla_max_cosine_workspace_bytes(int64_t B, int64_t Ns, int64_t Nt) {
   if (B < 0 || Ns < 0 || Nt < 0) return 0;
-  return gfla::align16(8 * B * Nt) + gfla::align16(4 * B * Nt) + gfla::align16(4 * B * Ns);
+  return gfla::align16(8 * B * Nt) + gfla::align16(4 * B * Nt) + gfla::align16(4 * B * Ns) + gfla::align16(4 * B);
 }
 
 int gfla_max_cosine_fwd_f32(const float *source, const float *target, void *workspace, float *out_max,

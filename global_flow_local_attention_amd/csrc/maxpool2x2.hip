@@ -2,20 +2,23 @@
 // is dropped and its gradient is zero.  Forward: one thread per output element, the winner's stored bits are copied.
 // Backward: one thread per INPUT element; it finds the winner of its window again from the saved pool input (no index
 // tensor) and writes g or 0, so every element of dX is written exactly once: no atomics, no memset.  Ties go to the first
-// maximum in scan order (row, then column), as F.max_pool2d does.  16-bit values are compared after exact widening.
+// maximum in scan order (row, then column), as F.max_pool2d does; a NaN wins its window, as there.  16-bit values are
+// compared after exact widening.
 #include "gfla_common.h"
 
 namespace gfla {
 
-// index 0..3 (scan order) of the first maximum of the window whose top-left element is p
+// index 0..3 (scan order) of the first maximum of the window whose top-left element is p.  F.max_pool2d's rule: a later
+// element replaces the winner if it is larger OR a NaN, so a window with a NaN in it returns NaN (the last one in scan
+// order) and routes the gradient there.
 template <typename T>
 __device__ __forceinline__ int pool_winner(const T *p, int W) {
   float best = (float)Num<T>::ld(p);
   int at = 0;
   const float b = (float)Num<T>::ld(p + 1), c = (float)Num<T>::ld(p + W), d = (float)Num<T>::ld(p + W + 1);
-  if (b > best) { best = b; at = 1; }
-  if (c > best) { best = c; at = 2; }
-  if (d > best) { best = d; at = 3; }
+  if (b > best || b != b) { best = b; at = 1; }
+  if (c > best || c != c) { best = c; at = 2; }
+  if (d > best || d != d) { best = d; at = 3; }
   return at;
 }
 

@@ -208,8 +208,17 @@ template <typename T, int N>
 __device__ __forceinline__ void rs_bwd1_apply_fix(const int (&ro)[N], const int (&co)[N], const float (&qy)[N],
                                                   const float (&wx)[N], float g_first, const T *__restrict__ g,
                                                   int64_t gstride, lds_fix_t *__restrict__ gplane, int64_t plane_sz, int nch,
-                                                  float gscale) {
+                                                  float gscale, unsigned *poison) {
   // g_first = the first channel's gradient at g (the caller requested it an iteration ahead)
+  // poison (a word of the workgroup's LDS): set when this pixel's weights are not finite -- a NaN or inf flow or sigma.
+  // The cells cannot hold such a contribution (lds_plane.h: its bit pattern would be added as an integer and come out
+  // finite); the caller then flushes NaN, as it does for a non-finite gradient.
+  {
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < N; ++q) ok = ok && fabsf(wx[q]) < INFINITY && fabsf(qy[q]) < INFINITY;
+    if (!ok) *poison = 1u;
+  }
   // The product (gradient x row weight / sum) is formed in DOUBLE: qy = w_y / sum alone is not bounded by 1 (only qy * wx
   // is), and with a sigma small enough for the column weights to underflow go * qy overflows float while the contribution
   // itself is <= |go| (advisor finding, round 3).
@@ -253,7 +262,8 @@ __device__ __forceinline__ void rs_bwd1_apply_fix(const int (&ro)[N], const int 
 }
 template <typename T, typename PT, int KH, typename A, typename Where>
 __device__ __forceinline__ void rs_bwd1_pixel(const Taps<A, KH> &t, const T *__restrict__ g, int64_t gstride,
-                                              PT *__restrict__ gplane, int64_t plane_sz, int nch, A gscale = 1) {
+                                              PT *__restrict__ gplane, int64_t plane_sz, int nch, A gscale = 1,
+                                              unsigned *poison = nullptr) {
   constexpr int N = 2 * KH;
   int ro[N], co[N];
   A qy[N], wx[N];
@@ -265,7 +275,7 @@ __device__ __forceinline__ void rs_bwd1_pixel(const Taps<A, KH> &t, const T *__r
     wx[r] = t.col_w(r);
   }
   if constexpr (std::is_same<Where, LdsFixPlane>::value)
-    rs_bwd1_apply_fix<T, N>(ro, co, qy, wx, Num<T>::ld(g), g, gstride, gplane, plane_sz, nch, gscale);
+    rs_bwd1_apply_fix<T, N>(ro, co, qy, wx, Num<T>::ld(g), g, gstride, gplane, plane_sz, nch, gscale, poison);
   else
     rs_bwd1_apply<T, PT, N, A, Where>(ro, co, qy, wx, g, gstride, gplane, plane_sz, nch, gscale);
 }
@@ -466,7 +476,7 @@ __global__ __launch_bounds__(kLdsThreads) void rs_lds_kernel(const T *__restrict
   static_assert(!FIX || (MODE == 1 && std::is_same<A, float>::value), "fixed-point planes: float scatter only");
   static_assert(!TAB || (MODE == 1 && KH == 2 && std::is_same<T, float>::value), "tap records: float scatter, kernel_size 4 / 5");
   extern __shared__ __attribute__((aligned(16))) unsigned char gfla_smem[];
-  __shared__ unsigned s_amax;
+  __shared__ unsigned s_amax, s_poison;
   // adaptive dispatch (patch_mfma.hip): the matrix-core path took this launch when its statistic is within the limit
   if (skip_stat) {  // the statistic is a sum over 32 counters (patch_mfma.hip: kPmStatSlots)
     unsigned tot = 0;
@@ -494,7 +504,7 @@ __global__ __launch_bounds__(kLdsThreads) void rs_lds_kernel(const T *__restrict
   const T *in1_0 = in1 + ((int64_t)b * C + c0) * plane_sz;
   if constexpr (MODE == 1) {
     zero_planes<PT>(planes, gc * win_sz);
-    if (FIX && threadIdx.x == 0) s_amax = 0;
+    if (FIX && threadIdx.x == 0) s_amax = 0, s_poison = 0;
   } else {
     for (int c = 0; c < gc; ++c)
       stage_planes<T, PT>(in1_0 + (int64_t)c * plane_sz + win.lo * Wi, planes + (size_t)c * win_sz, win_sz);
@@ -538,7 +548,7 @@ __global__ __launch_bounds__(kLdsThreads) void rs_lds_kernel(const T *__restrict
       const T *go = gout0 + p;
       if (inside) {
         if constexpr (FIX)
-          rs_bwd1_apply_fix<T, 4>(ro, co, qy, wx, g_first, go, HW, planes0, win_sz, gc, fix.up);
+          rs_bwd1_apply_fix<T, 4>(ro, co, qy, wx, g_first, go, HW, planes0, win_sz, gc, fix.up, &s_poison);
         else
           rs_bwd1_apply<T, PT, 4, A, LdsPlane>(ro, co, qy, wx, go, HW, planes0, win_sz, gc, (A)1);
       } else {
@@ -564,7 +574,7 @@ __global__ __launch_bounds__(kLdsThreads) void rs_lds_kernel(const T *__restrict
       const T *go = gout + ((int64_t)b * C + c0) * HW + p;
       if (inside) {
         if constexpr (FIX)
-          rs_bwd1_pixel<T, PT, KH, A, LdsFixPlane>(t, go, HW, planes0, win_sz, gc, fix.up);
+          rs_bwd1_pixel<T, PT, KH, A, LdsFixPlane>(t, go, HW, planes0, win_sz, gc, fix.up, &s_poison);
         else
           rs_bwd1_pixel<T, PT, KH, A, LdsPlane>(t, go, HW, planes0, win_sz, gc);
       } else
@@ -584,6 +594,7 @@ __global__ __launch_bounds__(kLdsThreads) void rs_lds_kernel(const T *__restrict
   }
   if constexpr (MODE == 1) {
     __syncthreads();
+    if constexpr (FIX) fix.finite = fix.finite && s_poison == 0;   // (a pixel with non-finite weights: rs_bwd1_apply_fix)
     for (int c = 0; c < gc; ++c) {  // bit 1 of the flag word: overwrite (host-checked)
       T *dst = outp + ((int64_t)b * C + c0 + c) * plane_sz + win.lo * Wi;
       if constexpr (FIX)
@@ -773,7 +784,7 @@ __global__ __launch_bounds__(512) void rs_bwd1_tile_kernel(const T *__restrict__
   extern __shared__ __attribute__((aligned(16))) unsigned char gfla_smem[];
   PT *planes = reinterpret_cast<PT *>(gfla_smem);
   __shared__ int s_box[4];
-  __shared__ unsigned s_amax;
+  __shared__ unsigned s_amax, s_poison;
   const int64_t v = xcd_swizzle(blockIdx.x, nwg);
   const int g = (int)(v % ngroups);
   const int64_t rest = v / ngroups;
@@ -786,7 +797,7 @@ __global__ __launch_bounds__(512) void rs_bwd1_tile_kernel(const T *__restrict__
   const int HW = H * W, plane_sz = Hi * Wi;
   const int p = active ? y * W + x : 0;
   box_init(s_box);
-  if (threadIdx.x == 0) s_amax = 0;
+  if (threadIdx.x == 0) s_amax = 0, s_poison = 0;
   __syncthreads();
   // ---- taps of this thread's pixel (rows as INDICES: pitch 1), kept for all channel rounds
   int row[N], col[N];
@@ -846,15 +857,15 @@ __global__ __launch_bounds__(512) void rs_bwd1_tile_kernel(const T *__restrict__
     if (active && !(abl & 2)) {
       const T *go = go0 + (int64_t)cb * HW;
       if constexpr (FIX)
-        rs_bwd1_apply_fix<T, N>(ro, co, qy, wx, Num<T>::ld(go), go, HW, planes, win, n, fix.up);
+        rs_bwd1_apply_fix<T, N>(ro, co, qy, wx, Num<T>::ld(go), go, HW, planes, win, n, fix.up, &s_poison);
       else
         rs_bwd1_apply<T, PT, N, A, LdsPlane>(ro, co, qy, wx, go, HW, planes, win, n, (A)1);
     }
     __syncthreads();
     if (!(abl & 4)) {
       const TileWin w{ymin, xmin, rows, cols, win};
-      const double down = fix.finite ? fix.down : __longlong_as_double(0x7ff8000000000000ll);
-      const bool finite = fix.finite;
+      const bool finite = fix.finite && s_poison == 0;   // (a pixel with non-finite weights: rs_bwd1_apply_fix)
+      const double down = finite ? fix.down : __longlong_as_double(0x7ff8000000000000ll);
       flush_windows<T>(gin0 + (int64_t)cb * plane_sz, plane_sz, Wi, w, n, [=](int i) {
         const PT raw = planes[i];
         if constexpr (FIX) return raw == 0 ? 0.0 : (finite ? (double)raw * down : down);

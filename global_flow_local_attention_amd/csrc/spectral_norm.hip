@@ -51,11 +51,13 @@ __device__ __forceinline__ float sn_block_sum(float v, float *lds) {
   return total;
 }
 
-// max(||x||_2, eps) of a vector of n floats, the same bits in every workgroup that asks
+// max(||x||_2, eps) of a vector of n floats, the same bits in every workgroup that asks.  A NaN norm stays NaN, as
+// F.normalize's clamp_min keeps it (fmaxf would hand back eps, and a vector with one NaN entry would keep its others)
 __device__ __forceinline__ float sn_denominator(const float *x, int n, float eps, float *lds) {
   float acc = 0.f;
   for (int i = threadIdx.x; i < n; i += kBlock) acc += x[i] * x[i];
-  return fmaxf(sqrtf(sn_block_sum(acc, lds)), eps);
+  const float norm = sqrtf(sn_block_sum(acc, lds));
+  return norm < eps ? eps : norm;
 }
 
 // t = W^T u.  from_s: u = s / max(||s||, eps) of the iteration before, else the module's buffer.

@@ -40,8 +40,8 @@ class Conv3x3ReluFunction(Function):
     """(x (B,Cin,H,W), weight (Cout,Cin,3,3), bias (Cout,)) -> relu(conv2d(x, weight, bias, stride 1, padding 1)) on the
     matrix cores (csrc/conv3x3.hip).  x: float32 / float16 / bfloat16 on the GPU, read as stored; sums are float32, a
     16-bit result is rounded once.  Parameters stored in another float type are packed into x's dtype.  Only d/dx exists
-    (the extractor is frozen): dx = conv3x3(g [y > 0], weight mirrored), launched only when x needs a gradient; otherwise
-    nothing is saved."""
+    (the extractor is frozen): dx = conv3x3(g [not y <= 0], weight mirrored), launched only when x needs a gradient;
+    otherwise nothing is saved.  A NaN sum stays NaN through the ReLU and passes its gradient on, as torch.relu does."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):

@@ -541,7 +541,9 @@ int gfla_gemm_f64(double *c, const int64_t *c_view, const double *a, const int64
  * out_idx (B,Nt; int32 row of the maximum, may be NULL) are fully overwritten.  `workspace` is caller-
  * provided scratch of gfla_max_cosine_workspace_bytes(B, Ns, Nt) bytes, 16-byte aligned (the inverse
  * norms and the packed running maxima live there).  fp32 only (exact-f32 MFMA); the [Ns,Nt] matrix is
- * never written.  NaN similarities are ignored by the max (the reference's torch.max propagates them). */
+ * never written.  Non-finite features behave as in the reference: a position with a NaN or an inf among its channels
+ * normalises to NaN, every similarity it takes part in is NaN, and such a column's out_max is NaN with out_idx the row of
+ * its first NaN, as torch.max(dim=1) returns it.  out_idx is in [0, Ns) for every input. */
 int64_t gfla_max_cosine_workspace_bytes(int64_t B, int64_t Ns, int64_t Nt);
 int gfla_max_cosine_fwd_f32(const float *source, const float *target, void *workspace, float *out_max,
                             int32_t *out_idx, int64_t B, int64_t C, int64_t Ns, int64_t Nt, double eps,

@@ -67,8 +67,11 @@ def truth(name, shape, opts_key):
     """dict of y, gx, gw, gb (None without a bias) in float64 and of Sy, Sx, Sw, Sb, the same from absolute values;
     computed once per case and shared: treat it as read-only"""
     opts = dict(opts_key)
-    pool, slope = opts.get("pool", 1), opts.get("slope")
-    x, w, b, g = inputs(name, shape, opts_key)
+    return truth_of(*inputs(name, shape, opts_key), pool=opts.get("pool", 1), slope=opts.get("slope"))
+
+
+def truth_of(x, w, b, g, pool=1, slope=None):
+    """truth() of host tensors given as they are stored (tests/nonfinite_util.py plants a NaN in one first)"""
     dact = torch.ones(x.shape, dtype=torch.float64) if slope is None else \
         torch.where(x.float() > 0, 1.0, float(torch.tensor(slope, dtype=torch.float32))).double()
 
@@ -90,11 +93,13 @@ def truth(name, shape, opts_key):
 
 def bars(name, shape, opts_key):
     """the four bars of a case (see the module docstring), each of its quantity's shape"""
-    opts = dict(opts_key)
-    dtype, pool = gu.DTYPES[name], opts.get("pool", 1)
+    return bars_of(truth(name, shape, opts_key), gu.DTYPES[name], shape, dict(opts_key).get("pool", 1))
+
+
+def bars_of(t, dtype, shape, pool=1):
+    """bars() from a truth dict"""
     B, Cin, Cout, H, W = shape
     ho, wo = out_size(H, W, pool)
-    t = truth(name, shape, opts_key)
     u, eps = gu.UNIT[dtype], 2.0 ** -24
     staged = u if pool == 2 else 0.0                     # the one rounding of each pooled value
     out = {"y": 2.0 * (Cin + 2 + (3 if pool == 2 else 0)) * eps * t["Sy"] + u * t["y"].abs() + staged * t["Sy"],

@@ -408,7 +408,9 @@ def test_owner_computes_scatter_equals_the_atomics(lib, gfla, mode, k, C, H, W, 
 
 def test_owner_computes_scatter_non_finite_gradient(lib, gfla):
     """An inf in the upstream gradient: the fixed-point cells cannot hold it -- the owned rows come out NaN (the reference's float
-    atomics would poison only the cells the value reaches); nothing hangs, the other sample stays finite."""
+    atomics would poison only the cells the value reaches); nothing hangs, the forward stays finite.  A non-finite FLOW
+    entry under a finite gradient takes the same route (fc_tail_bwd_kernel folds the flow's finiteness into the slot that
+    carries max |d hidden|): tests/test_nonfinite_gpu.py plants one."""
     B, C, H, W, k = 2, 8, 12, 10, 5
     s, t = randn((B, C, H, W), seed=71).to(DEV), randn((B, C, H, W), seed=72).to(DEV)
     f = make_flow("smooth", B, H, W, seed=73).to(DEV)

@@ -78,15 +78,42 @@ def pool_input(kind, dtype):
     g = torch.Generator().manual_seed(11)
     if kind == "ties":
         return (torch.randn(2, 3, 9, 12, generator=g) * 2).round().div(2).clamp(-1, 1).to(dtype)   # multiples of 0.5
+    if kind.startswith("nan"):
+        # the odd map with a NaN in slot 0..3 (scan order) of one window, and in two slots of another: F.max_pool2d returns
+        # NaN for a window with a NaN in it and routes the gradient to the last one
+        x = torch.randn(2, 5, 7, 9, generator=g).to(dtype)
+        slot = int(kind[3])
+        x[0, 3, 4 + slot // 2, 6 + slot % 2] = float("nan")
+        x[1, 0, 0, 0] = x[1, 0, 1, slot % 2] = float("nan")
+        return x
     shape = {"odd": (2, 5, 7, 9), "empty": (1, 3, 1, 1), "even": (1, 64, 16, 10)}[kind]
     return torch.randn(shape, generator=g).to(dtype)
 
 
+def equal_with_nans(a, b):
+    """torch.equal that takes a NaN for equal to a NaN: equal NaN masks, equal values elsewhere"""
+    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.nan_to_num(a, nan=0.0), torch.nan_to_num(b, nan=0.0))
+
+
 @pytest.mark.parametrize("name", list(DTYPES))
-@pytest.mark.parametrize("kind", ["odd", "empty", "even", "ties"])
+@pytest.mark.parametrize("kind", ["odd", "empty", "even", "ties", "nan0", "nan1", "nan2", "nan3"])
 def test_maxpool2x2_is_bit_equal_to_torch(gfla, kind, name):
     dtype = DTYPES[name]
     x = pool_input(kind, dtype)
+    if kind.startswith("nan"):
+        xg = x.cuda().requires_grad_()
+        y = gfla.maxpool2x2(xg)
+        xr = x.float().requires_grad_()
+        yr = F.max_pool2d(xr, kernel_size=2, stride=2)
+        assert int(torch.isnan(yr).sum()) == 2
+        assert y.dtype == dtype and equal_with_nans(y.detach().cpu().float(), yr.detach())
+        g = torch.randn(yr.shape, generator=torch.Generator().manual_seed(5)).to(dtype)
+        g = g + (g == 0).to(dtype)
+        y.backward(g.cuda())
+        yr.backward(g.float())
+        assert torch.equal(xg.grad.cpu().float(), xr.grad)           # routed exactly: the gradient itself has no NaN
+        assert not xg.grad[:, :, 6].any() and not xg.grad[:, :, :, 8].any()
+        return
     xg = x.cuda().requires_grad_()
     y = gfla.maxpool2x2(xg)
     if kind == "empty":
