@@ -315,7 +315,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
         if constexpr (G == 2) {
 #pragma unroll
           for (int dy = 0; dy < 2; ++dy) {
-            const int64_t at = (int64_t)co * oplane + (int64_t)(2 * gy + dy) * Wout + 2 * gx;   // even: the pair is aligned
+            const int64_t at = (int64_t)co * oplane + (int64_t)(2 * gy + dy) * Wout + 2 * gx;   // even: the pair lies in one row
             float v0 = acc[i][j * PH + 2 * dy][r] + b, v1 = acc[i][j * PH + 2 * dy + 1][r] + b;
             if (ab) {
               const Pack<T, 2> a = *reinterpret_cast<const Pack<T, 2> *>(ab + at);
@@ -431,8 +431,10 @@ static int cv_run(int geometry, const T *x, const void *wp, const float *bias, c
   int64_t cblocks = 0;
   const int rc = cv_check(geometry, B, Cin, Cout, H, W, pad_mode, &g, &cblocks);
   if (rc != GFLA_OK) return rc;
-  // T2K3 stores (and reads the addend) in pairs of elements
-  if (geometry == 2 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(aux)) % (2 * sizeof(T))) != 0)
+  // T2K3 stores (and reads the addend) in pairs of elements that start at an even column: inside the map wherever y and the
+  // addend lie, on a pair boundary only where they do.  Any pointer aligned to its element is taken (include/gfla_hip.h,
+  // "Pointer placement")
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(aux)) % sizeof(T) != 0)
     return GFLA_ERR_UNSUPPORTED;
   auto launch = [&](auto geo) {
     conv_igemm_kernel<T, decltype(geo)::value, V>

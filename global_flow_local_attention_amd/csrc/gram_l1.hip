@@ -307,7 +307,7 @@ __global__ __launch_bounds__(kBlock) void gram_bwd_kernel(const T *__restrict__ 
   const float *Db = diff + b * C * (int64_t)C + (int64_t)c0 * C;
   const T *Fb = feat + b * C * (int64_t)N;
   const int rowsA = C - c0;
-  const bool vecD = C % 4 == 0;   // rows of D are 16-byte aligned (the allocation is)
+  const bool vecD = C % 4 == 0;   // rows of D are whole float4s: 16-byte aligned where `diff` is, the same loads unaligned elsewhere
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, kh = lane >> 5;

@@ -459,8 +459,12 @@ static int64_t in_workspace_bytes(int64_t BC, const InPlan &p) {
   return 8 * (2 * BC + (p.regime == 2 ? 3 * BC * p.wpp : 0));
 }
 
-static bool in_same_alignment(const void *a, const void *b) {
-  return ((reinterpret_cast<uintptr_t>(a) ^ reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+// The kernels take a span's head / vectors / tail from x's address (in_span) and use the same element offsets for y, dy and
+// dx: every access stays inside the span whatever the other pointers' phase is, it only is no longer 16-byte aligned there.
+// So any pointer aligned to its element is taken (include/gfla_hip.h, "Pointer placement").
+template <typename T>
+static bool in_element_aligned(const T *p) {
+  return reinterpret_cast<uintptr_t>(p) % sizeof(T) == 0;
 }
 
 // run the statement with NV = the plan's vector count (only the counts in_round_nv gives for T are instantiated)
@@ -487,7 +491,7 @@ static int in_fwd(const T *x, const typename Num<T>::acc *gamma, const typename 
   if (!x || !y || !mean || !rstd || !workspace) return GFLA_ERR_NULL_POINTER;
   InPlan p;
   if (int rc = in_plan(B, C, H, W, (int)sizeof(T), &p)) return rc;
-  if (!(eps >= 0) || !in_same_alignment(x, y)) return GFLA_ERR_UNSUPPORTED;
+  if (!(eps >= 0) || !in_element_aligned(x) || !in_element_aligned(y)) return GFLA_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t BC = B * C;
   const int N = (int)(H * W), seg = (int)p.seg_len, wpp = (int)p.wpp;
@@ -517,7 +521,7 @@ static int in_bwd(const T *x, const T *dy, const typename Num<T>::acc *gamma, co
   if (!x || !dy || !mean || !rstd || !workspace) return GFLA_ERR_NULL_POINTER;
   InPlan p;
   if (int rc = in_plan(B, C, H, W, (int)sizeof(T), &p)) return rc;
-  if (!in_same_alignment(x, dy) || (dx && !in_same_alignment(x, dx))) return GFLA_ERR_UNSUPPORTED;
+  if (!in_element_aligned(x) || !in_element_aligned(dy) || !in_element_aligned(dx)) return GFLA_ERR_UNSUPPORTED;
   if (!dx && !dgamma && !dbeta) return GFLA_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t BC = B * C;

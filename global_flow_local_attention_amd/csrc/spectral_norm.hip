@@ -189,15 +189,31 @@ __global__ __launch_bounds__(kBlock) void sn_bwd_dot_kernel(const SnRec *__restr
   for (int j = 0; j < kSnElems / (4 * kBlock); ++j) {
     const int64_t e = e0 + (int64_t)(j * kBlock + threadIdx.x) * 4;
     if (e >= total) break;
-    if (vec && e + 4 <= total) {
-      const float4 w = *reinterpret_cast<const float4 *>(W + e);
-      const float4 g = *reinterpret_cast<const float4 *>(G + e);
-      acc += g.x * w.x;
-      acc += g.y * w.y;
-      acc += g.z * w.z;
-      acc += g.w * w.w;
+    // The pointers decide how a group of four is LOADED, never how it is added.  Left to the compiler the float4 branch
+    // became v_pk_mul_f32 + v_add_f32 (every product rounded) and the scalar branch v_fmac_f32 (fused), so <G, W>, and
+    // with it c and grad_w, changed in the last bit with the phase of W.  A whole group rounds its products, the ragged
+    // last group of a matrix is fused: what an aligned call has always computed.
+    if (e + 4 <= total) {
+      float g[4], w[4];
+      if (vec) {
+        const float4 w4 = *reinterpret_cast<const float4 *>(W + e);
+        const float4 g4 = *reinterpret_cast<const float4 *>(G + e);
+        g[0] = g4.x, g[1] = g4.y, g[2] = g4.z, g[3] = g4.w;
+        w[0] = w4.x, w[1] = w4.y, w[2] = w4.z, w[3] = w4.w;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] = G[e + i], w[i] = W[e + i];
+      }
+      {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float p = g[i] * w[i];
+          acc = acc + p;
+        }
+      }
     } else {
-      for (int64_t i = e; i < e + 4 && i < total; ++i) acc += G[i] * W[i];
+      for (int64_t i = e; i < total; ++i) acc = fmaf(G[i], W[i], acc);
     }
   }
   acc = sn_block_sum(acc, red);

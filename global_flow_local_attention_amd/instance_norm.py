@@ -29,8 +29,9 @@ def _acc_dtype(dtype):
 
 
 def _aligned(t):
-    """contiguous, and on a 16-byte boundary (the kernels' vector loads want x, y, dy and dx to agree modulo 16; fresh
-    allocations sit on 256): the tensor itself when it already is"""
+    """contiguous, and on a 16-byte boundary: the tensor itself when it already is.  The kernels take any element-aligned
+    pointer, but they split a plane into head / vectors / tail by x's address, and the sums regroup with it: from a copy
+    the result is the same bit for bit wherever the caller's tensor starts"""
     t = t.contiguous()
     return t.clone() if t.data_ptr() % 16 else t
 

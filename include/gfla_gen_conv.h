@@ -11,7 +11,8 @@
  *                   >= 2); y (B,Cout,H,W).
  * geometry 1  S2K4  Conv2d(k 4, s 2, p 1), zero padding, H, W >= 2 (odd sizes are valid); y (B,Cout,(H-2)/2+1,(W-2)/2+1).
  * geometry 2  T2K3  ConvTranspose2d(k 3, s 2, p 1, output_padding 1), w (Cin,Cout,3,3); y (B,Cout,2H,2W), computed as four
- *                   output phases of 1 / 2 / 2 / 4 taps per input pixel; y and add must be aligned to two elements.
+ *                   output phases of 1 / 2 / 2 / 4 taps per input pixel; y and add are accessed in pairs of elements, on any
+ *                   element boundary.
  * bias: Cout float32 values, or NULL.  add: NULL, or a tensor of y's shape and type, added in float32 before the one
  * rounding; add == y (in place) is allowed.
  * `packed`: gfla_gen_conv_packed_bytes(Cout, Cin, geometry, sizeof(T)) bytes, 16-byte aligned, written by

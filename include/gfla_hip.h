@@ -28,7 +28,15 @@
  *   - suffix = storage type: _f32, _f64 (the two types the reference dispatches,
  *     AT_DISPATCH_FLOATING_TYPES), _bf16 and _f16 (new, 16-bit storage: forward AND backward, fp32 arithmetic inside,
  *     reductions over channels returned in float32).  bf16 / f16 buffers are raw uint16_t bit patterns; f16 is IEEE
- *     binary16 (stores round to nearest even, overflow to +-inf, subnormals kept).
+ *     binary16 (stores round to nearest even, overflow to +-inf, subnormals kept);
+ *   - pointer placement: a tensor pointer need only be aligned to its element type.  An entry point computes the same
+ *     result wherever its tensors lie (a contiguous view that starts inside a larger buffer is as good as a fresh
+ *     allocation; the 16-byte vector paths are chosen per pointer, DESIGN.md "Pointer placement" lists per op what is
+ *     bit-equal to the aligned call), reads nothing before the first and writes nothing behind the last element of a
+ *     buffer.  A pointer that is not aligned to its element type is refused with GFLA_ERR_UNSUPPORTED before anything is
+ *     launched by the entry points that inspect their pointers (instance norm, the generator convolutions); elsewhere it
+ *     is outside the ABI.  Workspaces (`workspace`, `scratch`, `packed`) are different: they want the alignment their
+ *     entry point states, 256 bytes where it states none -- what every allocator of device memory returns.
  */
 #ifndef GFLA_HIP_H_
 #define GFLA_HIP_H_
@@ -772,7 +780,8 @@ GFLA_DECL_MAXPOOL2X2(bf16, uint16_t)
  * fully overwritten otherwise.  Per-plane sums go to the workspace and are added over b in ascending order: no atomics,
  * every result is bit-identical from call to call.
  * `workspace`: gfla_instance_norm_workspace_bytes(B, C, H, W, sizeof(T)) bytes, 8-byte aligned, uninitialised, for fwd and
- * for bwd.  x, y (x, dy, dx) must agree in their address modulo 16 (-3 otherwise; fresh allocations do).
+ * for bwd.  x, y (x, dy, dx) may lie anywhere (aligned to their element): the head / vectors / tail split of a span follows
+ * x's address and the other tensors are accessed at the same element offsets.
  * gfla_instance_norm_geometry: the launch plan, host only: out[0..6] = regime (0 wave per plane, 1 workgroup per plane, 2
  * split plane), threads per workgroup, planes per workgroup, workgroups per plane, values per thread, LDS bytes, workgroups
  * per launch.  It depends on (B C, H W, elem_size) only.

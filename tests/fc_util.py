@@ -148,6 +148,9 @@ _STRUCT = {
     (5, 2, 16, 2, 9): dict(channel=("loud", 3), spatial=None, positive=True),
     (5, 1, 33, 13, 31): dict(channel=("loud", 2), spatial=("quiet_frame", 3), positive=False, outliers=3),
     (3, 3, 17, 7, 5): dict(channel=("loud", 3), spatial=("quiet_frame", 3), positive=True),
+    # tests/placement_util.py's vector-friendly FC shapes: C, H W and the fold's R W multiples of 4
+    (5, 3, 16, 8, 6): dict(channel=("quiet", 3), spatial=("loud_frame", 2), positive=False),
+    (3, 3, 16, 8, 6): dict(channel=("loud", 3), spatial=("quiet_frame", 3), positive=True),
     (3, 1, 40, 13, 31): dict(channel=("quiet", 2), spatial=("loud_frame", 3), positive=False, outliers=3),
     (3, 2, 8, 33, 65): dict(channel=("quiet", 4), spatial=("loud_frame", 2), positive=True, up_density=0.005),
     COLLAPSE: dict(channel=("loud", 3), spatial=("loud_frame", 2), positive=False, up_density=0.001),

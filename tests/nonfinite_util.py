@@ -152,13 +152,19 @@ def over_poisoning_stand_in(case, want):
     return out
 
 
+def to_dev(t):
+    """Every host -> device move of the `run` functions goes through here (looked up at call time), so that
+    tests/placement_util.py can put the device tensor where it wants it"""
+    return t.to(DEV)
+
+
 def _leaf(t, need=True, dtype=None):
     if t is None:
         return None
-    t = t.detach().clone().to(DEV)
+    t = t.detach().clone()
     if dtype is not None:
         t = t.to(dtype)
-    return t.requires_grad_(need)
+    return to_dev(t).requires_grad_(need)
 
 
 def _grad(t):
@@ -194,14 +200,14 @@ def _relu_conv_oracle(dtype, shape):
 
 def _relu_conv_run(gfla, inp):
     x = _leaf(inp["x"])
-    y = gfla.conv3x3_relu(x, inp["w"].float().to(DEV), inp["b"].float().to(DEV))
+    y = gfla.conv3x3_relu(x, to_dev(inp["w"].float()), to_dev(inp["b"].float()))
     assert type(y.grad_fn).__name__ == "Conv3x3ReluFunctionBackward"
-    y.backward(inp["gy"].to(DEV))
+    y.backward(to_dev(inp["gy"]))
     return {"y": y, "gx": x.grad}
 
 
-def relu_conv_cases():
-    B, Cin, Cout, H, W = RELU_SHAPE
+def relu_conv_cases(shape=RELU_SHAPE):
+    B, Cin, Cout, H, W = shape
     spots = [("x", "interior", (0, 2, 3, 4), ("nan", "+inf", "-inf"), 0), ("x", "corner", (0, 1, 0, 0), ("nan", "+inf"), 0),
              ("x", "last-sample", (1, 4, 5, 8), ("nan",), 1), ("w", "weight", (3, 2, 1, 1), ("nan", "+inf"), None),
              ("b", "bias", (4,), ("nan", "+inf"), None)]      # (-inf in a bias: relu makes it 0, nothing is non-finite)
@@ -211,14 +217,14 @@ def relu_conv_cases():
         for tensor, label, index, values, sample in spots:
             for vname in values if dname == "f32" else values[:1]:
                 def make(tensor=tensor, index=index, vname=vname, dtype=dtype):
-                    x, w, b, gy = vu.conv_inputs(RELU_SHAPE, dtype, seed=sum(RELU_SHAPE))
+                    x, w, b, gy = vu.conv_inputs(shape, dtype, seed=sum(shape))
                     inp = {"x": x, "w": w, "b": b, "gy": gy}
                     inp[tensor] = plant(inp[tensor], index, VALUE_NAMES[vname])
                     return inp
 
                 cases.append(Case("conv3x3_relu-%s-%s-%s" % (dname, label, vname), "conv3x3_relu", sample, make,
-                                  _relu_conv_oracle(dtype, RELU_SHAPE), _relu_conv_run,
-                                  _spot_where(RELU_SHAPE, tensor, label, index)))
+                                  _relu_conv_oracle(dtype, shape), _relu_conv_run,
+                                  _spot_where(shape, tensor, label, index)))
     return cases
 
 
@@ -227,9 +233,9 @@ POOL_SHAPE = (2, 5, 7, 9)        # odd both ways: the last row and column are dr
 POOL_WINDOW = (2, 3)             # the window (output row, output column) the value goes into, in plane (sample, 3)
 
 
-def pool_input(dtype, slot, sample=0, value=NAN):
+def pool_input(dtype, slot, sample=0, value=NAN, shape=POOL_SHAPE):
     """tests/test_vgg19_gpu.py's `odd` map with `value` in slot 0..3 (scan order) of one window"""
-    x = torch.randn(POOL_SHAPE, generator=torch.Generator().manual_seed(11)).to(dtype)
+    x = torch.randn(shape, generator=torch.Generator().manual_seed(11)).to(dtype)
     oy, ox = POOL_WINDOW
     return plant(x, (sample, 3, 2 * oy + slot // 2, 2 * ox + slot % 2), value)
 
@@ -245,11 +251,11 @@ def _pool_run(gfla, inp):
     x = _leaf(inp["x"])
     y = gfla.maxpool2x2(x)
     assert type(y.grad_fn).__name__ == "MaxPool2x2FunctionBackward"
-    y.backward(inp["gy"].to(DEV))
+    y.backward(to_dev(inp["gy"]))
     return {"y": y, "gx": x.grad}
 
 
-def pool_cases():
+def pool_cases(shape=POOL_SHAPE):
     cases = []
     for dname in ("f32", "f16", "bf16"):
         dtype = DTYPES[dname]
@@ -259,15 +265,15 @@ def pool_cases():
                 continue
 
             def make(dtype=dtype, slot=slot, sample=sample, vname=vname):
-                g = torch.randn((POOL_SHAPE[0], POOL_SHAPE[1], POOL_SHAPE[2] // 2, POOL_SHAPE[3] // 2),
+                g = torch.randn((shape[0], shape[1], shape[2] // 2, shape[3] // 2),
                                 generator=torch.Generator().manual_seed(5)).to(dtype)
-                return {"x": pool_input(dtype, slot, sample, VALUE_NAMES[vname]), "gy": g + (g == 0).to(dtype)}
+                return {"x": pool_input(dtype, slot, sample, VALUE_NAMES[vname], shape), "gy": g + (g == 0).to(dtype)}
 
             def where(inp, slot=slot, sample=sample):
                 hit = (~torch.isfinite(inp["x"])).nonzero()
                 oy, ox = POOL_WINDOW
                 return hit.shape[0] == 1 and tuple(hit[0].tolist()) == (sample, 3, 2 * oy + slot // 2, 2 * ox + slot % 2) \
-                    and 2 * oy + 1 < POOL_SHAPE[2] - 1 and 2 * ox + 1 < POOL_SHAPE[3] - 1
+                    and 2 * oy + 1 < shape[2] - 1 and 2 * ox + 1 < shape[3] - 1
             cases.append(Case("maxpool2x2-%s-slot%d-sample%d-%s" % (dname, slot, sample, vname), "maxpool2x2", sample, make,
                               _pool_oracle, _pool_run, where))
     return cases
@@ -329,7 +335,7 @@ def _gen_run(geometry, opts):
             _leaf(inp.get("add"))
         y = _gen_call(gfla, geometry, x, w, b, reflect, slope, add)
         assert type(y.grad_fn).__name__ == "GenConvFunctionBackward"
-        y.backward(inp["gy"].to(DEV))
+        y.backward(to_dev(inp["gy"]))
         out = {"y": y, "gx": x.grad, "gw": w.grad, "gb": b.grad}
         if add is not None:
             out["gadd"] = add.grad
@@ -369,9 +375,9 @@ def _spot_where(shape, tensor, label, index):
     return where
 
 
-def gen_conv_cases():
+def gen_conv_cases(rows=GEN_ROWS):
     cases = []
-    for label, geometry, shape, opts in GEN_ROWS:
+    for label, geometry, shape, opts in rows:
         out_hw = gu.out_size(geometry, shape[3], shape[4])
         for dname in ("f32", "bf16") if geometry != gu.S2K4 else ("f32", "f16"):
             dtype = DTYPES[dname]
@@ -397,9 +403,9 @@ def gen_conv_cases():
 C11_ROWS = [("conv1x1-pool1", (2, 20, 40, 9, 7), {"slope": 0.1}), ("conv1x1-pool2", (2, 20, 40, 7, 5), {"pool": 2})]
 
 
-def conv1x1_cases():
+def conv1x1_cases(rows=C11_ROWS):
     cases = []
-    for label, shape, opts in C11_ROWS:
+    for label, shape, opts in rows:
         pool, slope = opts.get("pool", 1), opts.get("slope")
         B, Cin, Cout, H, W = shape
         out_hw = cu.out_size(H, W, pool)
@@ -427,7 +433,7 @@ def conv1x1_cases():
                         x, w, b = _leaf(inp["x"]), _leaf(inp["w"]), _leaf(inp["b"])
                         y = gfla.conv1x1(x, w, b, pre_slope=slope, pool=pool, grad="kernels")
                         assert type(y.grad_fn).__name__ == "Conv1x1FunctionBackward"
-                        y.backward(inp["gy"].to(DEV))
+                        y.backward(to_dev(inp["gy"]))
                         return {"y": y, "gx": x.grad, "gw": w.grad, "gb": b.grad}
                     cases.append(Case("%s-%s-%s-%s" % (label, dname, spot, vname), "conv1x1", sample, make, oracle, run,
                                       _spot_where(shape, tensor, spot, index)))
@@ -441,9 +447,9 @@ HEAD_ROWS = [  # (label, (shape, Cout, post, split), padding, pre_slope): the fa
 ]
 
 
-def head_conv_cases():
+def head_conv_cases(rows=HEAD_ROWS):
     cases = []
-    for label, (shape4, cout, post, split), padding, slope in HEAD_ROWS:
+    for label, (shape4, cout, post, split), padding, slope in rows:
         B, Cin, H, W = shape4
         shape = (B, Cin, cout, H, W)
         spots = [("x", "interior", (0, Cin - 1, H // 2, W // 2), ("nan", "+inf", "-inf"), 0),
@@ -485,9 +491,11 @@ def head_conv_cases():
                         x, w, b = _leaf(inp["x"]), _leaf(inp["w"]), _leaf(inp["b"])
                         ys = fn(x, w, b)
                         ys = ys if isinstance(ys, tuple) else (ys,)
-                        up = inp["up"].to(DEV)
-                        parts = (up,) if split is None else (up[:, :split], up[:, split:])
-                        sum((y * u).sum() for y, u in zip(ys, parts)).backward()
+                        # each output's upstream gradient reaches the backward as the tensor made here (the same value as
+                        # the gradient of sum(y * u))
+                        up = inp["up"]
+                        parts = (up,) if split is None else (up[:, :split].contiguous(), up[:, split:].contiguous())
+                        torch.autograd.backward(list(ys), [to_dev(u.to(y.dtype)) for y, u in zip(ys, parts)])
                         out = {"y%d" % j: y for j, y in enumerate(ys)}
                         out.update({"gx": x.grad, "gw": w.grad, "gb": b.grad})
                         return out
@@ -509,7 +517,10 @@ _SPLIT_SHAPE = {}
 
 def instance_norm_shape(label, elem_size):
     """regime 0 from the sweep; "split": the smallest two-plane shape the library itself splits for this element size (B = 2,
-    C = 1: the planes are the samples).  Asked of the library when a case runs, so that building the case list needs none."""
+    C = 1: the planes are the samples).  Asked of the library when a case runs, so that building the case list needs none.
+    A label that is a shape stands for itself."""
+    if isinstance(label, tuple):
+        return label
     if label == "small":
         return (2, 5, 3, 7)
     if elem_size not in _SPLIT_SHAPE:
@@ -517,12 +528,12 @@ def instance_norm_shape(label, elem_size):
     return _SPLIT_SHAPE[elem_size]
 
 
-def instance_norm_cases():
+def instance_norm_cases(labels=("small", "split")):
     cases = []
     for dname in ("f32", "bf16"):
         dtype = DTYPES[dname]
         esize = torch.empty((), dtype=dtype).element_size()
-        for label in ("small", "split"):
+        for label in labels:
             for last, first_plane, vname in [(False, False, "nan"), (False, False, "+inf"), (True, True, "nan")]:
                 if dname != "f32" and (vname != "nan" or last):
                     continue
@@ -544,7 +555,7 @@ def instance_norm_cases():
                 def evaluate(fn, inp):
                     x, w, b = _leaf(inp["x"]), _leaf(inp["w"]), _leaf(inp["b"])
                     y = fn(x, w, b)
-                    (y * inp["up"].to(DEV)).sum().backward()
+                    y.backward(to_dev(inp["up"].to(y.dtype)))
                     return {"y": y, "gx": x.grad, "gw": w.grad, "gb": b.grad}
 
                 def run(gfla, inp, evaluate=evaluate):
@@ -560,7 +571,8 @@ def instance_norm_cases():
                     hit = ~torch.isfinite(inp["x"])
                     regime = iu.geometry(*inp["x"].shape, inp["x"].element_size())["regime"]
                     return int(hit.sum()) == 1 and bool(hit[index_of(tuple(inp["x"].shape))]) and (regime == 2) == (label == "split")
-                cases.append(Case("instance_norm_act-%s-%s-sample%s-%s" % (label, dname, "last" if last else "0", vname),
+                cases.append(Case("instance_norm_act-%s-%s-sample%s-%s" % ("x".join(map(str, label)) if isinstance(label, tuple) else label,
+                                                                           dname, "last" if last else "0", vname),
                                   "instance_norm_act", 1 if last else 0, make, oracle, run, where, composition))
     return cases
 
@@ -580,11 +592,11 @@ def cosine_features(shape, seed, dtype):
     return x.to(dtype).contiguous()
 
 
-def max_cosine_cases():
+def max_cosine_cases(rows=COSINE_ROWS):
     from oracle.cpu_modules import max_cosine_cpu
     from util import randn
     cases = []
-    for label, shape, split in COSINE_ROWS:
+    for label, shape, split in rows:
         B, C, Ns, Nt = shape
         # a source position in the SECOND tile (row 200), a target position, one +inf feature; the last sample once
         spots = [("source", "source-position", (0, 3, 200), "nan", 0), ("target", "target-position", (0, C - 1, Nt - 1), "nan", 0),
@@ -630,7 +642,7 @@ def max_cosine_cases():
                     host = index.cpu()
                     assert host.dtype == torch.int32 and int(host.min()) >= 0 and int(host.max()) < shape[2], \
                         "max_cosine_similarity returned an index outside [0, Ns): %d .. %d" % (int(host.min()), int(host.max()))
-                    (best * inp["up"].to(DEV)).sum().backward()
+                    best.backward(to_dev(inp["up"].to(best.dtype)))
                     return {"y": best, "gs": s.grad, "gt": t.grad, "index": host}
 
                 def where(inp, shape=shape, tensor=tensor, index=index, spot=spot, label=label, dtype=dtype):
@@ -678,7 +690,7 @@ def vgg_case():
         return m.to(DEV)
 
     def run(gfla, inp):
-        out = module(gfla, inp)(inp["image"].to(DEV))
+        out = module(gfla, inp)(to_dev(inp["image"]))
         return {"y_" + layer: out[layer] for layer in vu.LAYERS}
 
     def where(inp):
@@ -704,11 +716,11 @@ def _top(t):
 WARP_SHAPE = (2, 16, 12, 10)      # tests/test_flow_warp_gpu.py's first sweep row, the flow of the source's size, "pixel"
 
 
-def flow_warp_cases():
+def flow_warp_cases(shape=WARP_SHAPE):
     import flow_warp_util as fu
     from global_flow_local_attention_amd.flow_warp import convention_scalars, torch_flow_warp
     from util import make_flow, randn
-    B, C, H, W = WARP_SHAPE
+    B, C, H, W = shape
     scalars = convention_scalars("pixel", H, W)
     spots = [("src", "source", (0, 3, 5, 4), ("nan", "+inf"), 0), ("flow", "flow-x", (0, 0, 6, 5), ("nan", "+inf"), 0),
              ("flow", "flow-y", (0, 1, 6, 5), ("nan", "-inf"), 0), ("src", "last-sample", (B - 1, C - 1, 6, 5), ("nan",), B - 1),
@@ -720,7 +732,7 @@ def flow_warp_cases():
             for vname in values if dname == "f32" else values[:1]:
                 def make(dtype=dtype, tensor=tensor, index=index, vname=vname):
                     flow = fu.clear_of_kinks(make_flow("coherent", B, H, W, seed=4), [scalars])
-                    inp = {"src": randn(WARP_SHAPE, seed=3).to(dtype), "flow": flow, "up": randn(WARP_SHAPE, seed=5)}
+                    inp = {"src": randn(shape, seed=3).to(dtype), "flow": flow, "up": randn(shape, seed=5)}
                     inp[tensor] = plant(inp[tensor], index, VALUE_NAMES[vname])
                     return inp
 
@@ -732,7 +744,7 @@ def flow_warp_cases():
                 def evaluate(fn, inp):
                     s, f = _leaf(inp["src"]), _leaf(inp["flow"])
                     out = fn(s, f)
-                    (out * inp["up"].to(DEV)).sum().backward()
+                    out.backward(to_dev(inp["up"].to(out.dtype)))
                     return {"y": out, "gs": s.grad, "gf": f.grad}
 
                 def run(gfla, inp, evaluate=evaluate):
@@ -756,10 +768,10 @@ def flow_warp_cases():
 AFFINE_SHAPE, AFFINE_KZ = (2, 9, 8), 3
 
 
-def affine_cases():
+def affine_cases(shape=AFFINE_SHAPE):
     import affine_util as au
     from util import make_flow
-    B, H, W = AFFINE_SHAPE
+    B, H, W = shape
     half_ulp = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
     cases = []
     for dname in ("f32", "bf16"):
@@ -801,9 +813,9 @@ def affine_cases():
 CMAP_SHAPE = (2, 12, 70)
 
 
-def correctness_map_cases():
+def correctness_map_cases(shape=CMAP_SHAPE):
     from util import randn
-    B, C, N = CMAP_SHAPE
+    B, C, N = shape
     spots = [("warped", "warped", (0, 3, 20), ("nan", "+inf"), 0), ("target", "target", (0, 4, 33), ("nan", "-inf"), 0),
              ("best", "best", (0, 41), ("nan",), 0), ("warped", "last-sample", (B - 1, 0, 69), ("nan",), B - 1),
              ("up", "upstream", (0, 7), ("nan",), 0)]
@@ -815,7 +827,7 @@ def correctness_map_cases():
                 continue
             for vname in values if dname == "f32" else values[:1]:
                 def make(dtype=dtype, tensor=tensor, index=index, vname=vname):
-                    inp = {"warped": cosine_features(CMAP_SHAPE, 21, torch.float32), "target": cosine_features(CMAP_SHAPE, 22, dtype),
+                    inp = {"warped": cosine_features(shape, 21, torch.float32), "target": cosine_features(shape, 22, dtype),
                            "best": (randn((B, N), seed=23).abs() * 0.5 + 0.2).contiguous(), "up": randn((B, N), seed=24)}
                     inp[tensor] = plant(inp[tensor], index, VALUE_NAMES[vname])
                     return inp
@@ -833,7 +845,7 @@ def correctness_map_cases():
                 def run(gfla, inp):
                     x, t, best = _leaf(inp["warped"]), _leaf(inp["target"]), _leaf(inp["best"])
                     out = gfla.CorrectnessMapFunction.apply(x, t, best, 1e-8)
-                    (out * inp["up"].to(DEV)).sum().backward()
+                    out.backward(to_dev(inp["up"].to(out.dtype)))
                     return {"y": out, "gx": x.grad, "gt": t.grad, "gb": best.grad}
                 cases.append(Case("correctness_map-%s-%s-%s" % (dname, spot, vname), "CorrectnessMapFunction", sample, make, oracle,
                                   run, _one_hit(tensor, index)))
@@ -851,10 +863,10 @@ def _one_hit(tensor, index):
 GRAM_SHAPE = (2, 40, 9, 7)
 
 
-def gram_cases():
+def gram_cases(shape=GRAM_SHAPE):
     import style_util as su
     from global_flow_local_attention_amd.losses import compute_gram
-    B, C, H, W = GRAM_SHAPE
+    B, C, H, W = shape
     half_ulp = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
     cases = []
     for dname in ("f32", "f16"):
@@ -911,7 +923,7 @@ def fc_layer_run(c, mode):
     from global_flow_local_attention_amd import _lib, fc_mfma
     k, B, C, H, W, slope = c["k"], c["B"], c["C"], c["H"], c["W"], c["slope"]
     assert fc_mfma.resolve_mode(C, H, W, k, mode) == mode
-    s, t, f, w0, b0, w1, b1, up = (c[n].float().to(DEV).contiguous() for n in ("s", "t", "f", "w0", "b0", "w1", "b1", "up"))
+    s, t, f, w0, b0, w1, b1, up = (to_dev(c[n].float().contiguous()) for n in ("s", "t", "f", "w0", "b0", "w1", "b1", "up"))
     ws = torch.empty(fc_mfma.workspace_bytes(B, C, H, W, k, mode, 0), dtype=torch.uint8, device=DEV)
     sc = torch.empty(fc_mfma.workspace_bytes(B, C, H, W, k, mode, 1), dtype=torch.uint8, device=DEV)
     lg = torch.full((B, k * k, H, W), NAN, device=DEV)
@@ -926,10 +938,10 @@ def fc_layer_run(c, mode):
     return dict(zip(FC_NAMES, (lg, gs, gt, gf, gw0, gb0, gw1, gb1)))
 
 
-def fc_layer_cases():
+def fc_layer_cases(rows=FC_ROWS):
     import fc_util as fu
     cases = []
-    for shape, mode in FC_ROWS:
+    for shape, mode in rows:
         k, B, C, H, W = shape
         live = fu.make_case(shape, False, "narrow")["up"].abs().sum(1) > 0      # the case's upstream gradient is sparse
 
@@ -986,10 +998,10 @@ def fc_layer_cases():
 SCATTER_SHAPE = (2, 8, 20, 14)
 
 
-def scatter_cases():
+def scatter_cases(shape=SCATTER_SHAPE):
     from oracle import cpu_modules
     from util import make_flow, randn
-    B, C, H, W = SCATTER_SHAPE
+    B, C, H, W = shape
     cases = []
     for op, k in (("Resample2d", 4), ("BlockExtractor", 3)):
         for dname in ("f32", "bf16"):
@@ -1000,9 +1012,9 @@ def scatter_cases():
                 index = (sample, 0, 7, 5)
 
                 def make(dtype=dtype, index=index, op=op, k=k):
-                    up_shape = SCATTER_SHAPE if op == "Resample2d" else (B, C, H * k, W * k)
+                    up_shape = shape if op == "Resample2d" else (B, C, H * k, W * k)
                     up = randn(up_shape, seed=82).to(dtype)
-                    return {"src": randn(SCATTER_SHAPE, seed=80).to(dtype), "up": up + (up == 0).to(dtype),
+                    return {"src": randn(shape, seed=80).to(dtype), "up": up + (up == 0).to(dtype),
                             "flow": plant(make_flow("coherent", B, H, W, seed=81).to(dtype), index, NAN)}
 
                 def forward(op=op, k=k):
@@ -1032,7 +1044,7 @@ def scatter_cases():
                 def run(gfla, inp, forward=forward):
                     s, f = _leaf(inp["src"]), _leaf(inp["flow"])
                     out = forward()(gfla, s, f)
-                    out.backward(inp["up"].to(DEV))
+                    out.backward(to_dev(inp["up"]))
                     return {"y": out, "gs": s.grad, "gf": f.grad}
                 cases.append(Case("%s-%s-flow-nan-sample%d" % (op, dname, sample), op, sample, make, oracle, run,
                                   _one_hit("flow", index)))

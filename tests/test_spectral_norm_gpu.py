@@ -84,6 +84,17 @@ def test_determinism_and_batch_invariance(gfla):
                 assert torch.equal(a[q], c[q]), (iters, q, "batched against alone")
 
 
+def test_a_matrix_behind_a_ragged_one_equals_itself_alone(gfla):
+    """The batch layout does not pad: behind a matrix whose R K is no multiple of 4 the next one's slice of the upstream
+    gradient starts off a 16-byte boundary, and the backward's dot takes its scalar loads.  It must add as the float4 loads do
+    (du.MATRICES has its only ragged matrix last, so the test above never puts one in front)."""
+    ragged, whole = du.matrix_inputs(3, 5, seed=8), du.matrix_inputs(64, 512, seed=576)
+    assert ragged[0].numel() % 4 != 0 and whole[0].numel() % 4 == 0
+    behind, alone = lib_run(gfla, [ragged, whole], 1)[1], lib_run(gfla, [whole], 1)[0]
+    for q in QUANTITIES:
+        assert torch.equal(behind[q], alone[q]), q
+
+
 def test_buffers_in_place_and_eval_untouched(gfla):
     W, u, v, _ = du.matrix_inputs(32, 27, seed=9)
     W, u, v = W.cuda(), u.cuda(), v.cuda()
