@@ -148,11 +148,24 @@ static CvTile cv_tile(int geometry, int64_t Cout, int64_t H, int64_t W) {
 // x: (B, Cin, H, W), the map that is convolved; wp: packed weights; bias: Cout float32 (kCvGen: or NULL; kCvVggBwd:
 // unused); aux: kCvGen: the addend, y's shape, or NULL (may alias y, so neither carries __restrict__); kCvVggBwd: the saved
 // forward output, x's shape; y: (B, Cout, Hout, Wout).  reflect, pre_act and slope are read by kCvGen only.
-template <typename T, int G, int V>
+//
+// WIN (the frames-major 3-D convolutions of conv3d.hip, kCvGen and kCvGrad only): x is (B, win.Lin, win.Cf, H, W) and
+// blockIdx.z = b win.Lo + l counts the samples of the result.  Sample (b, l) reduces over the Cin = KT win.Cf channels of
+// the KT frames that start at frame l + win.off -- contiguous in x, so the sample starts at ((b Lin + l + off) Cf) planes
+// and everything else is the 2-D kernel's; channels of frames outside [0, Lin) read as zero and are never addressed.  aux
+// and y are plain (B Lo, Cout, ..) batches.  A compile-time choice: without it the body is the 2-D kernel's, unchanged.
+struct CvWin {
+  int Lin, Lo, off, Cf;
+};
+struct CvNoWin {};
+
+template <typename T, int G, int V, int WIN = 0>
 __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restrict__ x, const unsigned char *__restrict__ wp,
                                                                const float *__restrict__ bias, const T *aux, T *y, int Cin,
                                                                int Cout, int H, int W, int Hout, int Wout, int tw_log2,
-                                                               int WM, int tilesX, int reflect, int pre_act, float slope) {
+                                                               int WM, int tilesX, int reflect, int pre_act, float slope,
+                                                               std::conditional_t<WIN != 0, CvWin, CvNoWin> win = {}) {
+  static_assert(!WIN || V == kCvGen || V == kCvGrad, "the window exists for the generator variant and its gradient");
   static_assert(G <= 2 || V == kCvGrad, "the adjoint geometries exist for the gradient variant only");
   static_assert(V == kCvGen || V == kCvGrad || G == 0, "the VGG variants and the padded-domain gradient exist for S1K3 only");
   static_assert(V != kCvGrad || (G != 1 && G != 2), "a gradient runs on the adjoint geometry");
@@ -173,7 +186,15 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
   const int iy0 = G == 0 || G == kCvU2K4 ? y0 - O0 : G == 1 || G == kCvS2K3 ? 2 * y0 - 1 : y0;
   const int ix0 = G == 0 || G == kCvU2K4 ? x0 - O0 : G == 1 || G == kCvS2K3 ? 2 * x0 - 1 : x0;
   const int64_t plane = (int64_t)H * W, oplane = (int64_t)Hout * Wout;
-  const T *xb = x + (int64_t)blockIdx.z * Cin * plane;
+  int clo = 0, chi = Cin;                                                     // the reduced channels that exist
+  int64_t xat = (int64_t)blockIdx.z * Cin * plane;
+  if constexpr (WIN) {
+    const int wb = blockIdx.z / win.Lo, f0 = (int)blockIdx.z - wb * win.Lo + win.off;      // first frame of the window
+    clo = f0 < 0 ? -f0 * win.Cf : 0;
+    chi = win.Lin - f0 < Cin / win.Cf ? (win.Lin - f0) * win.Cf : Cin;
+    xat = ((int64_t)wb * win.Lin + f0) * win.Cf * plane;
+  }
+  const T *xb = x + xat;
   const int NCH = (Cin + CK - 1) / CK, MP = (Cout + 31) / 32 * 32;
 
   // what this thread stages per chunk: word q (channels 2q, 2q + 1 of the chunk, or channel q) of halo pixel p
@@ -194,7 +215,11 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(const T *__restri
     }
   }
   auto element = [&](int c, int off) -> uint32_t {
-    if (c >= Cin) return 0u;
+    if constexpr (WIN) {
+      if (c < clo || c >= chi) return 0u;
+    } else {
+      if (c >= Cin) return 0u;
+    }
     const int64_t at = (int64_t)c * plane + off;
     if constexpr (V == kCvVggBwd) {       // the ReLU mask of the saved output; a NaN output passes its gradient on, as
       if (Num<T>::ld(aux + (xb - x) + at) <= 0.f) return 0u;                  // torch's threshold_backward does (y <= 0 ? 0 : g)

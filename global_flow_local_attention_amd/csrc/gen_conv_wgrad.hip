@@ -27,6 +27,7 @@
 // channel: every thread sums its strided share of g in ascending order, then a fixed tree over the workgroup.  No atomics:
 // bit-identical from call to call.
 #include "conv1x1.h"
+#include "conv3d.h"
 
 namespace gfla {
 
@@ -51,11 +52,16 @@ __device__ __forceinline__ T wg_pool(const T *p, int W) {
   return (T)(s * 0.25f);
 }
 
-template <typename T, int KW>
+// WIN (the frames-major 3-D convolutions, conv3d.hip): P is the (B win.Lo, CP, HP, WP) batch of grad_y and Q is x
+// (B, win.Lin, win.Cf, HQ, WQ); sample n = b Lo + l reads the CQ = KT Cf channels of the KT frames that start at frame
+// l + win.off, channels of frames outside [0, Lin) as zero (conv_igemm.h's window).  A compile-time choice.
+template <typename T, int KW, int WIN = 0>
 __global__ __launch_bounds__(kBlock) void gen_conv_wgrad_kernel(const T *__restrict__ P, const T *__restrict__ Q,
                                                                 float *__restrict__ partial, int CP, int CQ, int HP, int WP,
                                                                 int HQ, int WQ, int S, int reflect, int act_p, int act_q,
-                                                                float slope, int64_t L, int64_t per_split) {
+                                                                float slope, int64_t L, int64_t per_split,
+                                                                std::conditional_t<WIN != 0, CvWin, CvNoWin> win = {}) {
+  static_assert(!WIN || KW == 3 || KW == 4, "the window exists for the k 3 and k 4 geometries");
   constexpr int TAPS = KW * KW, RSB = kWgPix * (int)sizeof(T) + 16, CKP = cv_ck<T>();
   __shared__ __attribute__((aligned(16))) unsigned char Ps[kWgTile * RSB];
   __shared__ __attribute__((aligned(16))) unsigned char Qs[kWgTile * RSB];
@@ -75,6 +81,15 @@ __global__ __launch_bounds__(kBlock) void gen_conv_wgrad_kernel(const T *__restr
     const bool live = pix < end;
     const int64_t b = live ? pix / planeP : 0;
     const int rem = live ? (int)(pix - b * planeP) : 0, py = rem / WP, px = rem - py * WP;
+    int clo = 0, chi = CQ;                              // the window's channels that exist, and where its sample starts
+    int64_t qb = b * CQ;
+    if constexpr (WIN) {
+      const int64_t wb = b / win.Lo;
+      const int f0 = (int)(b - wb * win.Lo) + win.off;
+      clo = f0 < 0 ? -f0 * win.Cf : 0;
+      chi = win.Lin - f0 < CQ / win.Cf ? (win.Lin - f0) * win.Cf : CQ;
+      qb = (wb * win.Lin + f0) * win.Cf;
+    }
 #pragma unroll 4
     for (int i = 0; i < kWgTile / 4; ++i) {
       const int r = r0 + 4 * i, cp = m0 + r, n = n0 + r;
@@ -91,8 +106,8 @@ __global__ __launch_bounds__(kBlock) void gen_conv_wgrad_kernel(const T *__restr
             qy = qy == -1 ? 1 : qy == HQ ? HQ - 2 : qy;
             qx = qx == -1 ? 1 : qx == WQ ? WQ - 2 : qx;
           }
-          if (qy >= 0 && qy < HQ && qx >= 0 && qx < WQ)
-            qv = wg_act<T>(Q + (b * CQ + cq) * planeQ + (int64_t)qy * WQ + qx, act_q, slope);
+          if (qy >= 0 && qy < HQ && qx >= 0 && qx < WQ && (!WIN || (cq >= clo && cq < chi)))
+            qv = wg_act<T>(Q + (qb + cq) * planeQ + (int64_t)qy * WQ + qx, act_q, slope);
         }
       }
       *reinterpret_cast<T *>(Ps + r * RSB + col * (int)sizeof(T)) = pv;
@@ -202,13 +217,22 @@ static int wg_plan_1x1(int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t 
 // the launches of a plan: the split reduction and its sum, then the bias gradient over g's planes of `plane` pixels
 template <typename T>
 static int wg_run(const WgPlan &p, const T *gy, const T *x, float *grad_w, float *grad_b, void *ws, int64_t B, int64_t Cout,
-                  int64_t plane, int pad_mode, int pre_act, double pre_slope, gfla_stream_t stream) {
+                  int64_t plane, int pad_mode, int pre_act, double pre_slope, gfla_stream_t stream,
+                  const CvWin *win = nullptr) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (grad_w) {
     const T *P = p.act_p ? x : gy, *Q = p.act_p ? gy : x;
     const int act = pre_act ? 1 : 0;
     const dim3 grid((unsigned)p.tilesN, (unsigned)p.tilesM, (unsigned)p.splits);
     auto launch = [&](auto kw) {
+      if constexpr (decltype(kw)::value != 1) {
+        if (win) {                                      // the frames-major 3-D convolutions: Q through the window
+          gen_conv_wgrad_kernel<T, decltype(kw)::value, 1><<<grid, kBlock, 0, s>>>(
+              P, Q, static_cast<float *>(ws), (int)p.CP, (int)p.CQ, (int)p.HP, (int)p.WP, (int)p.HQ, (int)p.WQ, p.S, 0, 0, act,
+              (float)pre_slope, p.L, p.per_split, *win);
+          return;
+        }
+      }
       gen_conv_wgrad_kernel<T, decltype(kw)::value><<<grid, kBlock, 0, s>>>(
           P, Q, static_cast<float *>(ws), (int)p.CP, (int)p.CQ, (int)p.HP, (int)p.WP, (int)p.HQ, (int)p.WQ, p.S, pad_mode,
           p.act_p ? act : 0, p.act_p ? 0 : act, (float)pre_slope, p.L, p.per_split);
@@ -251,6 +275,32 @@ static int conv1x1_bwd_weight(const T *gy, const T *x, float *grad_w, float *gra
   return wg_run<T>(p, gy, x, grad_w, grad_b, ws, B, Cout, p.HP * p.WP, 0, pre_act, pre_slope, stream);
 }
 
+// the frames-major 3-D convolutions (conv3d.hip): P = g, a (B Lout, Cout, Hout, Wout) batch; Q = x through the window
+static int wg_plan_3d(int64_t B, int64_t L, int64_t C, int64_t Cout, int64_t H, int64_t W, int geometry, WgPlan *p,
+                      C3Shape *s) {
+  const int rc = c3_check(B, L, C, Cout, H, W, geometry, s);                            // the forward's own limits
+  if (rc != GFLA_OK) return rc;
+  p->KW = geometry == 1 ? 4 : 3;
+  p->S = geometry == 0 ? 1 : 2;
+  p->act_p = 0;
+  p->CP = Cout, p->CQ = kC3KT * C, p->HP = s->Hout, p->WP = s->Wout, p->HQ = H, p->WQ = W;
+  p->L = B * s->Lout * s->Hout * s->Wout;
+  return wg_split(p, kWgTarget);
+}
+
+template <typename T>
+static int conv3d_bwd_weight(const T *gy, const T *x, float *grad_w, float *grad_b, void *ws, int64_t B, int64_t L,
+                             int64_t C, int64_t Cout, int64_t H, int64_t W, int geometry, int pre_act, double pre_slope,
+                             gfla_stream_t stream) {
+  if (!gy || (!grad_w && !grad_b) || (grad_w && (!x || !ws))) return GFLA_ERR_NULL_POINTER;
+  WgPlan p;
+  C3Shape s;
+  const int rc = wg_plan_3d(B, L, C, Cout, H, W, geometry, &p, &s);
+  if (rc != GFLA_OK) return rc;
+  const CvWin win = {(int)L, (int)s.Lout, -s.pt, (int)C};
+  return wg_run<T>(p, gy, x, grad_w, grad_b, ws, B * s.Lout, Cout, s.Hout * s.Wout, 0, pre_act, pre_slope, stream, &win);
+}
+
 }  // namespace gfla
 
 using gfla::bf16_t;
@@ -278,6 +328,16 @@ int64_t gfla_conv1x1_bwd_workspace_bytes(int64_t B, int64_t Cin, int64_t Cout, i
   return p.max_splits * p.CP * p.N * 4 + 16;                                             // the float32 partial sums
 }
 
+int64_t gfla_conv3d_bwd_workspace_bytes(int64_t B, int64_t L, int64_t C, int64_t Cout, int64_t H, int64_t W, int geometry,
+                                        int elem_size) {
+  if (elem_size != 2 && elem_size != 4) return GFLA_ERR_BAD_SHAPE;
+  gfla::WgPlan p;
+  gfla::C3Shape s;
+  const int rc = gfla::wg_plan_3d(B, L, C, Cout, H, W, geometry, &p, &s);
+  if (rc != GFLA_OK) return rc;
+  return p.max_splits * p.CP * p.N * 4 + 16;                                             // the float32 partial sums
+}
+
 #define GFLA_DEF_GEN_CONV_WGRAD(SFX, T, CT)                                                                               \
   int gfla_gen_conv_bwd_weight_##SFX(const T *grad_y, const T *x, float *grad_w, float *grad_b, void *workspace,          \
                                      int64_t B, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int geometry,            \
@@ -292,6 +352,17 @@ int64_t gfla_conv1x1_bwd_workspace_bytes(int64_t B, int64_t Cin, int64_t Cout, i
     return gfla::conv1x1_bwd_weight<CT>(reinterpret_cast<const CT *>(grad_y), reinterpret_cast<const CT *>(x), grad_w,    \
                                         grad_b, workspace, B, Cin, Cout, H, W, pool, pre_act, pre_slope, stream);         \
   }
+#define GFLA_DEF_CONV3D_WGRAD(SFX, T, CT)                                                                                 \
+  int gfla_conv3d_bwd_weight_##SFX(const T *grad_y, const T *x, float *grad_w, float *grad_b, void *workspace, int64_t B, \
+                                   int64_t L, int64_t C, int64_t Cout, int64_t H, int64_t W, int geometry, int pre_act,   \
+                                   double pre_slope, gfla_stream_t stream) {                                              \
+    return gfla::conv3d_bwd_weight<CT>(reinterpret_cast<const CT *>(grad_y), reinterpret_cast<const CT *>(x), grad_w,     \
+                                       grad_b, workspace, B, L, C, Cout, H, W, geometry, pre_act, pre_slope, stream);     \
+  }
+GFLA_DEF_CONV3D_WGRAD(f32, float, float)
+GFLA_DEF_CONV3D_WGRAD(f16, uint16_t, f16_t)
+GFLA_DEF_CONV3D_WGRAD(bf16, uint16_t, bf16_t)
+#undef GFLA_DEF_CONV3D_WGRAD
 GFLA_DEF_GEN_CONV_WGRAD(f32, float, float)
 GFLA_DEF_GEN_CONV_WGRAD(f16, uint16_t, f16_t)
 GFLA_DEF_GEN_CONV_WGRAD(bf16, uint16_t, bf16_t)

@@ -44,7 +44,8 @@ def _bind_vgg(cls, vgg):
 
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
             dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False, fuse_instance_norm=False,
-            fuse_heads=False, inference_convs=False, train_convs=False, discriminator_convs=False, pointwise_convs=False):
+            fuse_heads=False, inference_convs=False, train_convs=False, discriminator_convs=False, pointwise_convs=False,
+            temporal_convs=False):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -113,7 +114,17 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     and in the discriminators the pooled shortcut of every ResBlockEncoder -- its AvgPool2d(2) folded into the convolution
     -- and the final Conv2d(C, 1, 1) (fuse_spectral_norm(pointwise="kernels")).  Together with train_convs a ResDiscriminator
     then trains with no vendor convolution at all.  False (the default) changes nothing; without inference_convs or
-    discriminator_convs it raises ValueError."""
+    discriminator_convs it raises ValueError.
+
+    temporal_convs: with discriminator_convs, True puts the two ResBlock3DEncoder of a TemporalDiscriminator built AFTER
+    install() on the library's own kernels as well (fuse_spectral_norm(temporal="kernels"), conv3d.py): the network
+    converts its input to frames-major (B,L,C,H,W) once, the Conv3d of both blocks run as 2-D convolutions over a sliding
+    window of three frames (csrc/conv3d.hip), the AvgPool3d((3,2,2), (1,2,2)) on csrc/avg_pool_frames.hip, the 1x1x1 bypass
+    on csrc/conv1x1.hip, and their spectral norms join the one batched call.  With train_convs and pointwise_convs a
+    TemporalDiscriminator then trains with no vendor convolution or pool.  State-dict keys, Parameter and buffer objects are
+    unchanged.  False (the default) changes nothing; without discriminator_convs it raises ValueError."""
+    if temporal_convs and not discriminator_convs:
+        raise ValueError("install: temporal_convs=True needs discriminator_convs")
     if pointwise_convs and not (inference_convs or discriminator_convs):
         raise ValueError("install: pointwise_convs=True needs inference_convs or discriminator_convs")
     if train_convs and not (inference_convs or discriminator_convs):
@@ -182,7 +193,8 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
         patch_reference_discriminators(importlib.import_module("model.networks.discriminator"), base_function,
                                        discriminator_convs if isinstance(discriminator_convs, str) else "auto",
                                        "kernels" if train_convs else "torch",
-                                       "kernels" if pointwise_convs else "torch")
+                                       "kernels" if pointwise_convs else "torch",
+                                       "kernels" if temporal_convs else "torch")
     if vgg is not None:
         from . import losses
         external_function = importlib.import_module("model.networks.external_function")

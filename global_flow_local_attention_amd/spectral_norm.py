@@ -10,6 +10,7 @@ shortcut folded into the convolution (gen_conv.conv1x1).
     spectral_normalize      the functional form over a batch of (weight, u, v)
     SpectralNormFunction    the autograd Function on the kernels
     SpectralConv            module with the hooked convolution's Parameters, buffers and names
+    SpectralConv3d          the same for the Conv3d of a ResBlock3DEncoder, on frames-major maps (conv3d.py)
     fuse_spectral_norm      rewrite the hooked convolutions of a network in place
     patch_reference_discriminators   the reference's discriminators, rewritten as they are built
 
@@ -18,6 +19,7 @@ float64, 16-bit parameters and impl="torch" take the torch composition: the oper
 the hook's order, so on the CPU it is bit-identical to the hook.
 """
 import ctypes
+import types
 
 import torch
 import torch.nn.functional as F
@@ -27,10 +29,12 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import _rewrite
+from . import conv3d as _c3
 from . import gen_conv as _gc
 from ._conv_common import P1K1, S1K3, S2K4, check_grad, conv_geometry
 
 POINTWISE = ("torch", "kernels")
+TEMPORAL = ("torch", "kernels")
 _TABLE_CACHE = {}
 _TABLE_CACHE_MAX = 64
 
@@ -175,7 +179,36 @@ def _is_pool2(module):
         pair(module.padding) == (0, 0) and not module.ceil_mode and module.divisor_override is None
 
 
-class SpectralConv(nn.Module):
+class _Normalized(nn.Module):
+    """What SpectralConv and SpectralConv3d share: the hooked convolution's Parameters and buffers under its names and in
+    its order, the hook's numbers, and the weight that the network's batched call hands over."""
+
+    def _adopt(self, conv, hook):
+        self.n_power_iterations, self.eps = int(hook.n_power_iterations), float(hook.eps)
+        for name, p in conv._parameters.items():
+            self.register_parameter(name, p)
+        for name, b in conv._buffers.items():
+            self.register_buffer(name, b, persistent=name not in conv._non_persistent_buffers_set)
+        self.__dict__["original"] = conv           # not a submodule: its geometry, and its own forward for what the kernels lack
+        self.__dict__["_handed"] = None
+        self.train(conv.training)
+
+    def power_iterations(self):
+        return self.n_power_iterations if self.training else 0
+
+    def hand(self, weight):
+        """the normalised weight for the next forward (fuse_spectral_norm's network hook)"""
+        self.__dict__["_handed"] = weight
+
+    def normalized_weight(self):
+        weight, self.__dict__["_handed"] = self.__dict__["_handed"], None
+        if weight is None:
+            weight = spectral_normalize([self.weight_orig], [self.weight_u], [self.weight_v], self.power_iterations(),
+                                        self.eps, self.impl)[0]
+        return weight
+
+
+class SpectralConv(_Normalized):
     """[LeakyReLU(pre_slope)] -> the convolution `conv` under torch's spectral_norm hook (+ add), with the normalisation
     on the batched op.  `weight_orig`, `bias`, `weight_u` and `weight_v` are conv's own Parameter and buffer objects under
     conv's names and in conv's order, so state dicts interchange with the hooked form in both directions;
@@ -199,7 +232,6 @@ class SpectralConv(nn.Module):
                              "other hook")
         self.impl, self.grad = impl, grad
         self.pre_slope = None if pre_slope is None else float(pre_slope)
-        self.n_power_iterations, self.eps = int(hook.n_power_iterations), float(hook.eps)
         geometry = (conv_geometry(conv) or (None,))[0]
         self.geometry = geometry if geometry in (S1K3, S2K4) else None
         self.pointwise = pointwise == "kernels" and geometry == P1K1
@@ -207,27 +239,7 @@ class SpectralConv(nn.Module):
             raise ValueError("SpectralConv: pool is 1, or 2 on a 1x1 convolution with pointwise='kernels' and no pre_slope "
                              "(got %r)" % (pool,))
         self.pool = pool
-        for name, p in conv._parameters.items():
-            self.register_parameter(name, p)
-        for name, b in conv._buffers.items():
-            self.register_buffer(name, b, persistent=name not in conv._non_persistent_buffers_set)
-        self.__dict__["original"] = conv           # not a submodule: its geometry, and F.conv2d for what the kernels lack
-        self.__dict__["_handed"] = None
-        self.train(conv.training)
-
-    def power_iterations(self):
-        return self.n_power_iterations if self.training else 0
-
-    def hand(self, weight):
-        """the normalised weight for the next forward (fuse_spectral_norm's network hook)"""
-        self.__dict__["_handed"] = weight
-
-    def normalized_weight(self):
-        weight, self.__dict__["_handed"] = self.__dict__["_handed"], None
-        if weight is None:
-            weight = spectral_normalize([self.weight_orig], [self.weight_u], [self.weight_v], self.power_iterations(),
-                                        self.eps, self.impl)[0]
-        return weight
+        self._adopt(conv, hook)
 
     def forward(self, x, add=None):
         weight = self.normalized_weight()
@@ -247,6 +259,152 @@ class SpectralConv(nn.Module):
             self.impl, self.grad, ", pointwise='kernels', pool=%d" % self.pool if self.pointwise else "")
 
 
+def conv3d_geometry(module):
+    """"k333" / "k344" / "k111" for an nn.Conv3d of one of the three shapes a ResBlock3DEncoder has, else None"""
+    if type(module) is not nn.Conv3d or module.groups != 1 or tuple(module.dilation) != (1, 1, 1) or \
+            module.padding_mode != "zeros":
+        return None
+    return {((3, 3, 3), (1, 1, 1), (1, 1, 1)): "k333", ((3, 4, 4), (1, 2, 2), (0, 1, 1)): "k344",
+            ((1, 1, 1), (1, 1, 1), (0, 0, 0)): "k111"}.get((tuple(module.kernel_size), tuple(module.stride),
+                                                            tuple(module.padding)))
+
+
+class SpectralConv3d(_Normalized):
+    """[LeakyReLU(pre_slope)] -> the Conv3d `conv` under torch's spectral_norm hook (+ add) on a FRAMES-MAJOR map
+    (B,L,C,H,W) -> (B,Lout,Cout,Hout,Wout), for the three convolutions of a ResBlock3DEncoder: k (3,3,3) s 1 p 1 and
+    k (3,4,4) s (1,2,2) p (0,1,1) through conv3d.conv3d_frames, the 1x1x1 bypass through gen_conv.conv1x1 on the
+    (B L, C, H, W) batch its input is.  SpectralConv's contract otherwise: conv's own `weight_orig`, `bias`, `weight_u`,
+    `weight_v` under conv's names and in conv's order, the normalisation through spectral_normalize -- which flattens the
+    5-D weight to (Cout, -1), so u and v keep torch's order --, with all the others of the network in one call; the
+    frames-major permutation is applied to the NORMALISED weight, when it is packed.  Whatever the kernels do not run (CPU,
+    float64, impl="torch", a gradient needed without grad="kernels") is conv's own forward on the permuted map."""
+
+    def __init__(self, conv, pre_slope=None, impl="auto", grad="torch"):
+        super(SpectralConv3d, self).__init__()
+        _lib.check_impl(impl)
+        check_grad(grad)
+        hook = _rewrite.spectral_norm_hook(conv)
+        self.geometry = conv3d_geometry(conv)
+        if self.geometry is None or hook is None:
+            raise ValueError("SpectralConv3d: an nn.Conv3d of kernel (3,3,3) / (3,4,4) stride (1,2,2) / 1 under "
+                             "torch.nn.utils.spectral_norm (name 'weight', dim 0) and no other hook")
+        if self.geometry == "k111" and pre_slope is not None:
+            raise ValueError("SpectralConv3d: the 1x1x1 convolution takes no pre-activation (got %r)" % (pre_slope,))
+        self.impl, self.grad = impl, grad
+        self.pre_slope = None if pre_slope is None else float(pre_slope)
+        self._adopt(conv, hook)
+
+    def _own(self, x, weight):               # the convolution's own arithmetic on the normalised weight, in torch's layout
+        a = x if self.pre_slope is None else F.leaky_relu(x, self.pre_slope)
+        return _c3.frames_major_result(self.original._conv_forward(a.permute(0, 2, 1, 3, 4), weight, self.bias))
+
+    def forward(self, x, add=None):
+        weight = self.normalized_weight()
+        if self.geometry != "k111":
+            if self.impl == "torch" or not x.is_cuda:
+                y = self._own(x, weight)
+                return y if add is None else y + add
+            return _c3.conv3d_frames(x, weight, self.bias, self.geometry, self.pre_slope, add, self.grad, self.impl)
+        if x.dim() != 5:
+            raise ValueError("SpectralConv3d: a frames-major (B,L,C,H,W) map (got %s)" % (tuple(x.shape),))
+        B, L, C, H, W = x.shape
+        cout = weight.size(0)
+        y = _gc.run(P1K1, x.reshape(B * L, C, H, W), weight.reshape(cout, C, 1, 1), self.bias, "zeros", None, None, 1,
+                    self.impl, self.grad, lambda _: self._own(x, weight).reshape(B * L, cout, H, W))
+        y = y.reshape(B, L, cout, H, W)
+        return y if add is None else y + add
+
+    def extra_repr(self):
+        c = self.original
+        return "%s, %d -> %d, n_power_iterations=%d, pre_slope=%s, impl=%r, grad=%r" % (
+            self.geometry, c.in_channels, c.out_channels, self.n_power_iterations, self.pre_slope, self.impl, self.grad)
+
+
+def _is_pool322(module):
+    """nn.AvgPool3d((3,2,2), (1,2,2)): what conv3d.avg_pool_frames computes"""
+    def triple(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v, v)
+    return type(module) is nn.AvgPool3d and triple(module.kernel_size) == (3, 2, 2) and triple(module.stride) == (1, 2, 2) \
+        and triple(module.padding) == (0, 0, 0) and not module.ceil_mode and module.divisor_override is None and \
+        _rewrite.no_hooks(module)
+
+
+def _temporal_block(block):
+    """(conv k333, conv k344, pool, conv k111) of a module shaped like the reference's ResBlock3DEncoder without a norm
+    layer -- model = Sequential(LeakyReLU, Conv3d k333, LeakyReLU, Conv3d k344), shortcut = Sequential(AvgPool3d((3,2,2),
+    (1,2,2)), Conv3d 1x1x1), all three convolutions under the spectral-norm hook and nothing else hooked --, else None"""
+    model, shortcut = block._modules.get("model"), block._modules.get("shortcut")
+    if type(model) is not nn.Sequential or type(shortcut) is not nn.Sequential or len(model) != 4 or len(shortcut) != 2:
+        return None
+    if not all(_rewrite.no_hooks(m) for m in (block, model, shortcut)):
+        return None
+    act1, conv1, act2, conv2 = list(model)
+    pool, bypass = list(shortcut)
+    if _rewrite.slope_of(act1, relu=False) is None or _rewrite.slope_of(act2, relu=False) is None or not _is_pool322(pool):
+        return None
+    if not _rewrite.no_hooks(act1) or not _rewrite.no_hooks(act2):
+        return None
+    if len({id(conv1), id(conv2), id(bypass)}) != 3:
+        return None
+    for conv, geometry in ((conv1, "k333"), (conv2, "k344"), (bypass, "k111")):
+        if conv3d_geometry(conv) != geometry or _rewrite.spectral_norm_hook(conv) is None:
+            return None
+    if conv1.in_channels != bypass.in_channels or conv2.out_channels != bypass.out_channels:
+        return None
+    return conv1, conv2, pool, bypass
+
+
+class AvgPoolFrames(nn.Module):
+    """conv3d.avg_pool_frames in the slot of an nn.AvgPool3d((3,2,2), (1,2,2)), on a frames-major map"""
+
+    def __init__(self, impl="auto", grad="torch"):
+        super(AvgPoolFrames, self).__init__()
+        _lib.check_impl(impl)
+        check_grad(grad)
+        self.impl, self.grad = impl, grad
+
+    def forward(self, x):
+        return _c3.avg_pool_frames(x, self.grad, self.impl)
+
+    def extra_repr(self):
+        return "kernel_size=(3, 2, 2), stride=(1, 2, 2), impl=%r, grad=%r" % (self.impl, self.grad)
+
+
+def is_frames_major_block(block):
+    """a block rewritten by fuse_spectral_norm(temporal="kernels"): its model and shortcut take frames-major maps"""
+    return block is not None and bool(block.__dict__.get("_gfla_frames_major"))
+
+
+def frames_major_block_forward(self, x, frames_major=False):
+    """The forward of a rewritten ResBlock3DEncoder: model(x) with shortcut(x) in the epilogue of its last convolution.
+    Called on its own it takes and returns torch's (B,C,L,H,W), one permute copy each way; frames_major=True: (B,L,C,H,W)
+    in and out (the rewritten TemporalDiscriminator keeps both blocks in that layout)."""
+    if not frames_major:
+        x = _c3.to_frames_major(x)
+    y = _rewrite.run_with_add(self.model, x, self.shortcut(x))
+    return y if frames_major else _c3.from_frames_major(y)
+
+
+frames_major_block_forward._gfla_frames_major_block = True
+
+
+def _rewrite_temporal_block(block, found, impl, grad, replaced):
+    conv1, conv2, pool, bypass = found
+    model, shortcut = block._modules["model"], block._modules["shortcut"]
+    names, snames = list(model._modules.keys()), list(shortcut._modules.keys())
+    slopes = [_rewrite.slope_of(model._modules[names[i]], relu=False) for i in (0, 2)]
+    for at, conv, slope in ((1, conv1, slopes[0]), (3, conv2, slopes[1])):
+        replaced[id(conv)] = (conv, SpectralConv3d(conv, slope, impl, grad))
+        model._modules[names[at]] = replaced[id(conv)][1]
+        model._modules[names[at - 1]] = nn.Identity()
+    shortcut._modules[snames[0]] = AvgPoolFrames(impl, grad)
+    replaced[id(bypass)] = (bypass, SpectralConv3d(bypass, None, impl, grad))
+    shortcut._modules[snames[1]] = replaced[id(bypass)][1]
+    block.__dict__["_gfla_frames_major"] = True
+    if not getattr(type(block).forward, "_gfla_frames_major_block", False):      # no class-wide wrapper: this instance's own
+        block.__dict__["forward"] = types.MethodType(frames_major_block_forward, block)
+
+
 def _normalize_all(convs, impl):
     """one batched call per (power iterations, eps) present among `convs` -- one in all for a network in one mode"""
     groups = {}
@@ -259,7 +417,7 @@ def _normalize_all(convs, impl):
             c.hand(w)
 
 
-def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch"):
+def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch", temporal="torch"):
     """Rewrite, in place and recursively, every nn.Conv2d of `net` that carries torch.nn.utils.spectral_norm's hook (name
     "weight", dim 0) and no other: its slot becomes a SpectralConv with the same Parameter and buffer objects.  Indices
     and state-dict keys do not change.  Inside an nn.Sequential an nn.LeakyReLU directly in front is folded into the
@@ -272,11 +430,25 @@ def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch"):
     nn.AvgPool2d(kernel 2, stride 2, padding 0, ceil_mode False, divisor_override None) directly in front of one is folded
     into it (the pool's slot becomes nn.Identity(), the convolution gets pool=2); a pool of any other geometry stays.  The
     default "torch" leaves the 1x1 convolutions on F.conv2d and every pool in place.
+    temporal "kernels": every module shaped like the reference's ResBlock3DEncoder without a norm layer (_temporal_block:
+    model = Sequential(LeakyReLU, Conv3d k333, LeakyReLU, Conv3d k344), shortcut = Sequential(AvgPool3d((3,2,2), (1,2,2)),
+    Conv3d 1x1x1), the three convolutions hooked) runs on frames-major maps: the convolutions become SpectralConv3d with the
+    activations folded in, the pool an AvgPoolFrames, the shortcut goes into the last convolution's epilogue, and the
+    block's forward (frames_major_block_forward) converts on the way in and out when it is called on its own.  The three
+    weights join the one batched normalisation.  A block with norm layers, another pool, a CoordConv or a foreign hook is
+    left alone, uncounted.  The default "torch" looks at no Conv3d, as before.
     Returns the number of convolutions rewritten."""
     _lib.check_impl(impl)
     check_grad(grad)
     _check_pointwise(pointwise)
+    if temporal not in TEMPORAL:
+        raise ValueError("temporal: one of %s (got %r)" % (TEMPORAL, temporal))
     replaced = {}
+    if temporal == "kernels":
+        for block in list(net.modules()):
+            found = _temporal_block(block)
+            if found is not None and not any(id(c) in replaced for c in (found[0], found[1], found[3])):
+                _rewrite_temporal_block(block, found, impl, grad, replaced)
     for parent in list(net.modules()):
         if hasattr(parent, "addcoords"):                     # CoordConv: its convolution sees two more channels
             continue
@@ -296,13 +468,13 @@ def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch"):
     _rewrite.replace_aliases(net, replaced)
     if replaced and not getattr(net, "_gfla_spectral_norm_hooks", None):
         def before(module, inputs):
-            convs = [m for m in module.modules() if type(m) is SpectralConv]
+            convs = [m for m in module.modules() if isinstance(m, _Normalized)]
             if convs:
                 _normalize_all(convs, impl)
 
         def after(module, inputs, output):
             for m in module.modules():
-                if type(m) is SpectralConv:
+                if isinstance(m, _Normalized):
                     m.hand(None)
         handles = (net.register_forward_pre_hook(before), net.register_forward_hook(after, always_call=True))
         net.__dict__["_gfla_spectral_norm_hooks"] = handles
@@ -312,19 +484,51 @@ def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch"):
 _REFERENCE_DISCRIMINATORS = ("ResDiscriminator", "PatchDiscriminator", "TemporalDiscriminator")
 
 
-def patch_reference_discriminators(discriminator, base_function=None, impl="auto", grad="torch", pointwise="torch"):
+def patch_reference_discriminators(discriminator, base_function=None, impl="auto", grad="torch", pointwise="torch",
+                                   temporal="torch"):
     """Wrap the constructors of the reference's ResDiscriminator, PatchDiscriminator and TemporalDiscriminator
     (discriminator.py) so that every one built from now on comes out rewritten (fuse_spectral_norm on the finished
     network), and, given base_function, replace ResBlockEncoder.forward (base_function.py:533-556: model(x) + shortcut(x))
     by a version that hands shortcut(x) as `add` to the last convolution of `self.model` when that slot is a SpectralConv
-    on the 4x4 stride-2 kernels; otherwise it calls the original forward.  pointwise: fuse_spectral_norm's.  Idempotent.
+    on the 4x4 stride-2 kernels; otherwise it calls the original forward.  pointwise: fuse_spectral_norm's.
+    temporal "kernels" (fuse_spectral_norm's; needs base_function): ResBlock3DEncoder.forward becomes
+    frames_major_block_forward for rewritten blocks, and TemporalDiscriminator.forward (discriminator.py:130-140) converts
+    to frames-major once at entry, runs block0 and block1 in that layout and returns to the reference's out.view(b, c l,
+    h, w) with one permute copy before the 2-D encoders; unrewritten instances call the original forwards.  Idempotent.
     Returns the names of the classes wrapped."""
     _lib.check_impl(impl)
     check_grad(grad)
     _check_pointwise(pointwise)
+    if temporal not in TEMPORAL:
+        raise ValueError("temporal: one of %s (got %r)" % (TEMPORAL, temporal))
+    if temporal == "kernels":                      # before any network is built: fuse_spectral_norm looks for the flag
+        def make_block_forward(orig):
+            def forward(self, x, frames_major=False):
+                if not is_frames_major_block(self):
+                    return orig(self, x)
+                return frames_major_block_forward(self, x, frames_major)
+            forward._gfla_frames_major_block = True
+            return forward
+
+        def make_net_forward(orig):
+            def forward(self, x):
+                blocks = [getattr(self, "block0", None), getattr(self, "block1", None)]
+                if not all(is_frames_major_block(b) for b in blocks):
+                    return orig(self, x)
+                out = blocks[1](blocks[0](_c3.to_frames_major(x), frames_major=True), frames_major=True)
+                b, l, c, h, w = out.shape
+                out = out.permute(0, 2, 1, 3, 4).reshape(b, c * l, h, w)        # channel c l_count + l, one copy
+                for i in range(self.layers - 2):
+                    out = getattr(self, "encoder" + str(i))(out)
+                return self.conv(self.nonlinearity(out))
+            return forward
+        block_cls = None if base_function is None else getattr(base_function, "ResBlock3DEncoder", None)
+        _rewrite.wrap_method(block_cls, "forward", "_gfla_frames_major_forward", make_block_forward)
+        _rewrite.wrap_method(getattr(discriminator, "TemporalDiscriminator", None), "forward", "_gfla_frames_major_forward",
+                             make_net_forward)
     wrapped = [name for name in _REFERENCE_DISCRIMINATORS
                if _rewrite.wrap_init(getattr(discriminator, name, None), "_gfla_fuses_spectral_norm",
-                                     lambda self: fuse_spectral_norm(self, impl, grad, pointwise))]
+                                     lambda self: fuse_spectral_norm(self, impl, grad, pointwise, temporal))]
 
     def make_forward(orig):
         def forward(self, x):

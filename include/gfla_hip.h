@@ -868,6 +868,10 @@ int gfla_head_conv3x3_bwd_bf16(const uint16_t *x, const float *w, const uint16_t
  * documented in gfla_spectral_norm.h ---- */
 #include "gfla_spectral_norm.h"
 
+/* ---- frames-major 3-D convolutions and their pool (csrc/conv3d.hip, csrc/avg_pool_frames.hip): gfla_conv3d_*,
+ * gfla_avg_pool_frames_*, declared and documented in gfla_conv3d.h ---- */
+#include "gfla_conv3d.h"
+
 #ifdef __cplusplus
 }
 #endif
