@@ -551,7 +551,11 @@ int gfla_gemm_f64(double *c, const int64_t *c_view, const double *a, const int64
  * norms and the packed running maxima live there).  fp32 only (exact-f32 MFMA); the [Ns,Nt] matrix is
  * never written.  Non-finite features behave as in the reference: a position with a NaN or an inf among its channels
  * normalises to NaN, every similarity it takes part in is NaN, and such a column's out_max is NaN with out_idx the row of
- * its first NaN, as torch.max(dim=1) returns it.  out_idx is in [0, Ns) for every input. */
+ * its first NaN, as torch.max(dim=1) returns it.  out_idx is in [0, Ns) for every input.
+ * Ties: where several source rows share a column's maximum, out_idx is the LOWEST such row -- whatever the split of the
+ * source range (tuning key 5), the staging path and the storage type (the per-lane scan takes a later row only if it is
+ * strictly greater; the lane, wave and unit merges prefer the lower row on equal values).  A zero target vector gives
+ * (0.0, row 0).  tests/test_loss_exact_gpu.py holds all three entry points to this on inputs full of exact ties. */
 int64_t gfla_max_cosine_workspace_bytes(int64_t B, int64_t Ns, int64_t Nt);
 int gfla_max_cosine_fwd_f32(const float *source, const float *target, void *workspace, float *out_max,
                             int32_t *out_idx, int64_t B, int64_t C, int64_t Ns, int64_t Nt, double eps,
