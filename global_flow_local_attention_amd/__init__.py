@@ -26,6 +26,7 @@ from .spectral_norm import (AvgPoolFrames, SpectralConv, SpectralConv3d, Spectra
                             patch_reference_discriminators, spectral_normalize, torch_spectral_normalize)
 from .conv3d import (AvgPoolFramesFunction, Conv3dFramesFunction, avg_pool_frames, conv3d_frames,  # noqa: F401
                      from_frames_major, to_frames_major, torch_avg_pool_frames, torch_conv3d_frames)
+from .adam import FusedAdam  # noqa: F401
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401
 from .face_step import (DualStreamAttn, MaskBlendFunction, face_target_forward, generate_frames,  # noqa: F401

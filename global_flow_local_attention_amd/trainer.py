@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import dist as gdist
+from .adam import FusedAdam
 
 
 _DP_PREFIX = "module."   # what nn.DataParallel / DistributedDataParallel put in front of every key
@@ -70,20 +71,25 @@ class TrainerShell(object):
     amp: None (float32 step, the default), "fp16" -- the forward and the loss terms under torch.autocast("cuda",
     float16), the backward through a torch.amp.GradScaler -- or "bf16" (autocast bfloat16, no scaler).  With the scaler the
     bucketed all-reduce carries SCALED gradients: an inf / NaN on any rank reaches every rank through the sum, so every
-    rank's scaler skips the same step."""
+    rank's scaler skips the same step.
+    optimizer: "torch" (the default) steps with torch.optim.Adam; "kernels" with adam.FusedAdam at the same lr and betas:
+    one launch for all parameters, and under amp="fp16" the scaler's unscale and skip inside that launch."""
 
     AMP_DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
+    OPTIMIZERS = {"torch": torch.optim.Adam, "kernels": FusedAdam}
 
     def __init__(self, net_G, lr=1e-4, betas=(0.0, 0.999), lambda_rec=5.0, lambda_correct=5.0, lambda_regularization=0.0025,
                  correctness=None, regularization=None, gan_loss=None, style_content_loss=None, attn_layer=(2, 3),
-                 bucket_mb=32.0, amp=None):
+                 bucket_mb=32.0, amp=None, optimizer="torch"):
+        if optimizer not in self.OPTIMIZERS:
+            raise ValueError("TrainerShell: optimizer must be 'torch' or 'kernels' (got %r)" % (optimizer,))
         if amp is not None and amp not in self.AMP_DTYPES:
             raise ValueError("TrainerShell: amp must be None, 'fp16' or 'bf16' (got %r)" % (amp,))
         self.amp = amp
         self.scaler = torch.amp.GradScaler("cuda") if amp == "fp16" else None
         self.skipped_steps = 0   # steps the scaler skipped (inf / NaN in the gradients)
         self.net_G = net_G
-        self.optimizer_G = torch.optim.Adam([p for p in net_G.parameters() if p.requires_grad], lr=lr, betas=betas)
+        self.optimizer_G = self.OPTIMIZERS[optimizer]([p for p in net_G.parameters() if p.requires_grad], lr=lr, betas=betas)
         self.l1 = nn.L1Loss()
         self.lambdas = dict(rec=lambda_rec, correct=lambda_correct, regularization=lambda_regularization)
         self.correctness, self.regularization = correctness, regularization

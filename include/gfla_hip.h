@@ -876,6 +876,10 @@ int gfla_head_conv3x3_bwd_bf16(const uint16_t *x, const float *w, const uint16_t
  * gfla_avg_pool_frames_*, declared and documented in gfla_conv3d.h ---- */
 #include "gfla_conv3d.h"
 
+/* ---- one Adam / AdamW step over all parameters of a group (csrc/adam.hip): gfla_adam_*, declared and documented in
+ * gfla_adam.h ---- */
+#include "gfla_adam.h"
+
 #ifdef __cplusplus
 }
 #endif
