@@ -27,6 +27,8 @@ from .spectral_norm import (AvgPoolFrames, SpectralConv, SpectralConv3d, Spectra
 from .conv3d import (AvgPoolFramesFunction, Conv3dFramesFunction, avg_pool_frames, conv3d_frames,  # noqa: F401
                      from_frames_major, to_frames_major, torch_avg_pool_frames, torch_conv3d_frames)
 from .adam import FusedAdam  # noqa: F401
+from .pose_inputs import (PoseInputs, normalize_images, pose_cords, pose_maps, torch_normalize_images,  # noqa: F401
+                          torch_pose_cords, torch_pose_maps)
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401
 from .face_step import (DualStreamAttn, MaskBlendFunction, face_target_forward, generate_frames,  # noqa: F401

@@ -880,6 +880,10 @@ int gfla_head_conv3x3_bwd_bf16(const uint16_t *x, const float *w, const uint16_t
  * gfla_adam.h ---- */
 #include "gfla_adam.h"
 
+/* ---- pose inputs: key points -> heat maps and back, uint8 images -> network input (csrc/pose_inputs.hip): gfla_pose_*,
+ * gfla_normalize_images_*, declared and documented in gfla_pose.h ---- */
+#include "gfla_pose.h"
+
 #ifdef __cplusplus
 }
 #endif
