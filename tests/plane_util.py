@@ -27,7 +27,23 @@ resample2d: the weights are Gaussian, exp(-d^2 / (2 sigma^2)) / sum, evaluated i
 keeps them (they are positive and sum to 1); a coordinate error delta moves a weight w by at most w d / sigma^2 delta and a
 weight derivative w d / sigma^2 by at most w (d^2 / sigma^4 + 1 / sigma^2) delta.  With d <= (k / 2) dilation =: D the factor
 KAPPA = max(1, D / sigma^2) bounds the first and (KAPPA^2 + 1 / sigma^2) <= 2 KAPPA^2 the second (sigma >= 1), so resample2d
-uses P KAPPA^2 for P, and its d/d flow replaces each |dw / dx| by KAPPA w in A.
+uses P KAPPA^2 for P, and its d/d flow replaces each |dw / dx| by KAPPA w in A.  sigma is per pixel (input2 = dx, dy, sigma):
+given as a (B,1,H,W) field, KAPPA(b, y, x) = max(1, D / sigma^2) and with it P are fields too, and the gradient of the
+feature map, whose elements collect pixels of any sigma, takes the largest P of the case.
+
+resample2d, d/d sigma.  dw / dsigma = w d^2 / sigma^3 on each axis, so with c = (yd^2 + xd^2) / sigma^3 per tap (yd, xd its
+two distances), Vs = sum w c v and Ds = sum w c,
+
+    g_sigma = sum_c up (Vs / S - val Ds / S^2).
+
+Every distance is at most D, so 0 <= c <= 2 D^2 / sigma^3 =: c_max, |Vs| <= c_max sum w |v| and |val Ds / S^2| <= c_max
+sum w |v| / S: A = 2 c_max sum_c |up| (sum w |v|) / S, the quotient rule's two sums as for d/d flow, and the same
+n = 2 C k^2 + 2 k^2.  A coordinate error delta moves a term w c by |dw / dx| c + w |dc / dx| <= (KAPPA + 2 d / (sigma^3
+c_max)) w c_max delta = (KAPPA + d / D^2) w c_max delta <= 2 KAPPA w c_max delta (d <= D, D >= 1, KAPPA >= 1), which is
+below the 2 KAPPA^2 that d/d flow's P KAPPA^2 already pays for: P as for d/d flow.  sigma itself is an input, read exactly;
+sigma^3, its reciprocal and the squared distances are roundings inside a product (m).  All of this needs sigma >= 1
+(1 / sigma^2 <= KAPPA^2 above); `sigma_field` produces and asserts [1, 3.5].  d/d sigma is continuous in the flow wherever the
+forward is: it has no kinks of its own and is compared at every pixel.
 
 d/d flow has a jump wherever a sampling coordinate is an integer inside the range where the clamped taps still differ.
 `flow_kinks` marks those entries (within CLEAR px, or where the float32 and float64 floors differ); they are left out of the d/d
@@ -50,12 +66,14 @@ def bar(A, ref, n, P, dtype):
     return e + UNIT[dtype] * (ref.abs() + e) + TINY[dtype]
 
 
-def worst(got, ref, A, n, P, dtype, keep=None, extra=None):
+def worst(got, ref, A, n, P, dtype, keep=None, extra=None, b=None):
     """(max err / bar over the kept entries, number of entries beyond the bar); got in any dtype, anywhere.  `extra`: an
-    absolute term on top of the bar (rs_fixed_point_term)."""
+    absolute term on top of the bar (rs_fixed_point_term).  `b`: bar(A, ref, n, P, dtype) where the caller keeps it with
+    its reference."""
     got = got.detach().double().cpu()
     assert got.shape == ref.shape, (got.shape, ref.shape)
-    b = bar(A, ref, n, P, dtype)
+    if b is None:
+        b = bar(A, ref, n, P, dtype)
     if extra is not None:
         b = b + extra
     err = (got - ref).abs()
@@ -193,72 +211,105 @@ def aggregate_backward(s, f, attn, up, k, xmax_shift=0):
 
 # ------------------------------------------------------------------------------------------------------------ resample2d
 def rs_kappa(k, dil, sigma=SIGMA):
+    """KAPPA of the module docstring: a number for a number, a float64 field for a (B,1,H,W) field of stored sigmas"""
+    if torch.is_tensor(sigma):
+        sigma = sigma.double()
+        return ((k // 2) * dil / (sigma * sigma)).clamp_min(1.0)
     return max(1.0, (k // 2) * dil / (sigma * sigma))
 
 
 def _rs_axis(c, n_src, KH, dil, sigma, frac, hi_shift=0):
-    """The 2 KH taps of one axis: [(clamped index, weight, d weight / d coordinate)].  `frac` = the fraction the weights use
-    (coordinate - floor, or coordinate - trunc for the reference's d/d input1); indices always come from the floor."""
+    """The 2 KH taps of one axis: [(clamped index, weight, d weight / d coordinate, distance)].  `frac` = the fraction the
+    weights use (coordinate - floor, or coordinate - trunc for the reference's d/d input1); indices always come from the
+    floor.  sigma: a number, or a float64 tensor shaped like c."""
     c0 = c.floor().long()
     taps = []
     for t in range(KH):
         near, far = t * dil + frac, (1 + t) * dil - frac
         w_n, w_f = torch.exp(-near * near / (2 * sigma * sigma)), torch.exp(-far * far / (2 * sigma * sigma))
-        taps.append(((c0 - t * dil).clamp(0, n_src - 1 - hi_shift), w_n, -near / (sigma * sigma) * w_n))
-        taps.append(((c0 + (t + 1) * dil).clamp(0, n_src - 1 - hi_shift), w_f, far / (sigma * sigma) * w_f))
+        taps.append(((c0 - t * dil).clamp(0, n_src - 1 - hi_shift), w_n, -near / (sigma * sigma) * w_n, near))
+        taps.append(((c0 + (t + 1) * dil).clamp(0, n_src - 1 - hi_shift), w_f, far / (sigma * sigma) * w_f, far))
     return taps
 
 
-def resample2d(i1, f, up, k, dil, sigma=SIGMA, xmax_shift=0):
+def resample2d(i1, f, up, k, dil, sigma=SIGMA, xmax_shift=0, sigma_power=3):
     """Resample2d(k, dil, sigma) in float64 (resample2d_kernel.cu:20-95, :98-202 with its int() quirk as
-    oracle.resample2d_bwd(trunc_compat=True) has it, :204-330 for dx, dy).  i1 (B,C,Hi,Wi), f (B,2,H,W), up (B,C,H,W) or None.
+    oracle.resample2d_bwd(trunc_compat=True) has it, :204-330 for dx, dy, sigma).  i1 (B,C,Hi,Wi), f (B,2,H,W), up (B,C,H,W)
+    or None; sigma a number, or a (B,1,H,W) tensor of stored values (widened exactly): one sigma per pixel, the third channel
+    of input2.  With a number every entry but g_sigma is what it was before sigma could be a field, bit for bit.
     name -> (ref, A, n): out (n = 2 k^2: k^2 products and the k^2 terms of the normaliser); g_input1 (n = contributions per
     element + k^2 for the normaliser every contribution shares); g_flow (n = 2 C k^2 + 2 k^2: the two sums of the quotient
-    rule over C channels and k^2 taps, and the normaliser twice; A = 2 KAPPA sum |up| sum w |v| / S)."""
+    rule over C channels and k^2 taps, and the normaliser twice; A = 2 KAPPA sum |up| sum w |v| / S); g_sigma ((B,1,H,W), no
+    reference quirk, fractions from the floor; the same n; A = 2 (2 D^2 / sigma^3) sum |up| sum w |v| / S, module docstring).
+    xmax_shift, sigma_power: the planted bugs of the power tests (a clamp moved by one; 1 / sigma^2 for 1 / sigma^3 in c)."""
     i1, f = i1.double(), f.double()
     B, C, Hi, Wi = i1.shape
     H, W = f.shape[2:]
     KH = k // 2
+    field = sigma
+    if torch.is_tensor(sigma):
+        assert tuple(sigma.shape) == (B, 1, H, W), (tuple(sigma.shape), (B, 1, H, W))
+        field = sigma.double()
+        sigma = field[:, 0]
     xf = torch.arange(W, dtype=torch.float64).view(1, 1, W) + f[:, 0]
     yf = torch.arange(H, dtype=torch.float64).view(1, H, 1) + f[:, 1]
     cols = _rs_axis(xf, Wi, KH, dil, sigma, xf - xf.floor(), xmax_shift)
     rows = _rs_axis(yf, Hi, KH, dil, sigma, yf - yf.floor())
     flat = i1.reshape(B, C, Hi * Wi)
 
-    def tap(r, q):
-        return flat.gather(2, (r * Wi + q).view(B, 1, H * W).expand(B, C, H * W)).view(B, C, H, W)
+    def tap(r_off, q):
+        return flat.gather(2, (r_off + q).view(B, 1, H * W).expand(B, C, H * W)).view(B, C, H, W)
 
-    S = (sum(w for _, w, _ in rows) * sum(w for _, w, _ in cols)).unsqueeze(1)
-    Dx = (sum(w for _, w, _ in rows) * sum(d for _, _, d in cols)).unsqueeze(1)
-    Dy = (sum(d for _, _, d in rows) * sum(w for _, w, _ in cols)).unsqueeze(1)
-    val, mag, vx, vy, term = 0, 0, 0, 0, torch.zeros(B, C, H, W, dtype=torch.float64)
-    for r, wy, dwy in rows:
-        for q, wx, dwx in cols:
-            v = tap(r, q)
-            val = val + (wy * wx).unsqueeze(1) * v
-            mag = mag + (wy * wx).unsqueeze(1) * v.abs()
+    S = (sum(w for _, w, _, _ in rows) * sum(w for _, w, _, _ in cols)).unsqueeze(1)
+    Dx = (sum(w for _, w, _, _ in rows) * sum(d for _, _, d, _ in cols)).unsqueeze(1)
+    Dy = (sum(d for _, _, d, _ in rows) * sum(w for _, w, _, _ in cols)).unsqueeze(1)
+    val, mag, vx, vy, vs, term = 0, 0, 0, 0, 0, torch.zeros(B, C, H, W, dtype=torch.float64)
+    yd2, xd2 = [d * d for _, _, _, d in rows], [d * d for _, _, _, d in cols]
+    for (r, wy, dwy, _), y2 in zip(rows, yd2):
+        r_off = r * Wi
+        for (q, wx, dwx, _), x2 in zip(cols, xd2):
+            v = tap(r_off, q)
+            w = (wy * wx).unsqueeze(1)
+            wv = w * v
+            wv_abs = wv.abs()              # = w |v| to the bit: w >= 0
+            val = val + wv
+            mag = mag + wv_abs
             vx = vx + (wy * dwx).unsqueeze(1) * v
             vy = vy + (dwy * wx).unsqueeze(1) * v
-            term = torch.maximum(term, ((wy * wx).unsqueeze(1) * v).abs())
+            vs = vs + (y2 + x2).unsqueeze(1) * wv            # c without its 1 / sigma^3, a factor of the pixel
+            term = torch.maximum(term, wv_abs)
     res = {"out": (val / S, mag / S, 2 * k * k), "out_term": term / S}
     if up is None:
         return res
     up = up.double()
+    up_abs = up.abs()
     gf = torch.stack([(up * (vx / S - val * Dx / (S * S))).sum(1), (up * (vy / S - val * Dy / (S * S))).sum(1)], 1)
-    A_gf = (2 * rs_kappa(k, dil, sigma) * (up.abs() * mag / S).sum(1, keepdim=True)).expand(B, 2, H, W).contiguous()
+    A_gf = (2 * rs_kappa(k, dil, field) * (up_abs * mag / S).sum(1, keepdim=True)).expand(B, 2, H, W).contiguous()
     res["g_flow"] = (gf, A_gf, 2 * C * k * k + 2 * k * k)
+    # d/d sigma: Vs / S - val Ds / S^2 with c = (yd^2 + xd^2) / sigma^3 (:273-328)
+    sg = (sigma if torch.is_tensor(sigma) else torch.full((B, H, W), float(sigma), dtype=torch.float64)).unsqueeze(1)
+    s3 = sg ** sigma_power
+    Ds = (sum(w * d * d for _, w, _, d in rows) * sum(w for _, w, _, _ in cols) +
+          sum(w for _, w, _, _ in rows) * sum(w * d * d for _, w, _, d in cols)).unsqueeze(1) / s3
+    gsig = (up * (vs / s3 / S - val * Ds / (S * S))).sum(1, keepdim=True)
+    D = float(KH * dil)
+    A_gs = 2 * (2 * D * D / sg ** 3) * (up_abs * mag / S).sum(1, keepdim=True)
+    res["g_sigma"] = (gsig, A_gs, 2 * C * k * k + 2 * k * k)
     # d/d input1: weights from coordinate - int(coordinate) (:137-138), indices from the floor
     cols1 = _rs_axis(xf, Wi, KH, dil, sigma, xf - xf.trunc(), xmax_shift)
     rows1 = _rs_axis(yf, Hi, KH, dil, sigma, yf - yf.trunc())
-    S1 = (sum(w for _, w, _ in rows1) * sum(w for _, w, _ in cols1)).unsqueeze(1)
+    S1 = (sum(w for _, w, _, _ in rows1) * sum(w for _, w, _, _ in cols1)).unsqueeze(1)
     g1, A_g1, cnt = torch.zeros_like(flat), torch.zeros_like(flat), torch.zeros(B, 1, Hi * Wi, dtype=torch.float64)
-    for r, wy, _ in rows1:
-        for q, wx, _ in cols1:
-            at = (r * Wi + q).view(B, 1, H * W)
+    one = torch.ones(B, 1, H * W, dtype=torch.float64)
+    for r, wy, _, _ in rows1:
+        r_off = r * Wi
+        for q, wx, _, _ in cols1:
+            at = (r_off + q).view(B, 1, H * W)
+            at_c = at.expand(B, C, H * W)
             wn = (wy * wx).unsqueeze(1) / S1
-            g1.scatter_add_(2, at.expand(B, C, H * W), (wn * up).reshape(B, C, H * W))
-            A_g1.scatter_add_(2, at.expand(B, C, H * W), (wn * up.abs()).reshape(B, C, H * W))
-            cnt.scatter_add_(2, at, torch.ones(B, 1, H * W, dtype=torch.float64))
+            g1.scatter_add_(2, at_c, (wn * up).reshape(B, C, H * W))
+            A_g1.scatter_add_(2, at_c, (wn * up_abs).reshape(B, C, H * W))
+            cnt.scatter_add_(2, at, one)
     res["g_input1"] = (g1.view(B, C, Hi, Wi), A_g1.view(B, C, Hi, Wi), cnt.view(B, 1, Hi, Wi) + k * k)
     res["g_input1_count"] = cnt.view(B, 1, Hi, Wi)
     return res
@@ -287,6 +338,19 @@ def rs_fixed_point_term(cnt, up, dtype):
     if dtype == torch.float64:
         return torch.zeros_like(cnt)
     return cnt * 2.0 ** -40 * up.double().abs().max().item()
+
+
+# The other routes of d/d input1 have no term of their own.  The matrix-core product (csrc/patch_mfma.hip, tuning key 14 = 2)
+# float32-sums products: rs_patch_table_kernel pre-sums, in float32, the weights wy[r] / S * wx[s] of the taps that clamp onto
+# one border position, and v_mfma_f32_32x32x2_f32 multiplies and accumulates in float32 without intermediate rounding to a
+# narrower type -- the same n products in another association, which the (n - 1 + m) eps sum |terms| of the bar does not
+# depend on.  Double planes (key 23 = 1) and the global kernels (key 6 = 1) add the float32 products with float64 / float32
+# atomics: at most the float32 sum the bar allows.  Since the product decides on the device whether the fixed-point scatter
+# behind it runs instead, the float32 cases keep rs_fixed_point_term under every key set but 23 = 1 and 6 = 1.
+def rs_input1_term(cnt, up, dtype, keys):
+    if dtype == torch.float32 and (keys.get(23) == 1 or keys.get(6) == 1):      # (16-bit storage ignores both keys)
+        return torch.zeros_like(cnt)
+    return rs_fixed_point_term(cnt, up, dtype)
 
 
 # ------------------------------------------------------------------------------------------------ the GPU cases' inputs
@@ -341,6 +405,39 @@ def inputs(op, shape, dtype, kind, k):
     if op == "agg":
         return s, f, (randn((B, k * k, Hf, Wf), seed=seed + 3) * 2).to(dtype), randn((B, C, Hf, Wf), seed=seed + 2).to(dtype)
     return s, f, randn((B, C, Hf, Wf), seed=seed + 2).to(dtype)
+
+
+SIGMA_FIELDS = ("random", "levels")
+SIGMA_MIN, SIGMA_MAX = 1.0, 3.5
+
+
+def sigma_field(kind, B, H, W, dtype, seed):
+    """(B,1,H,W) sigma per pixel, rounded to the storage type, every value in [1, 3.5] (the module docstring's bar for
+    resample2d assumes sigma >= 1).  random: 1 + 2.5 rand.  levels: 1 + 0.5 ((x + 2 y + 3 b) % 6) -- six values, exact in
+    float16 and bfloat16, and different from the left, the upper and the previous sample's neighbour of every pixel: a
+    kernel that reads sigma one pixel, one row or one sample off sees another value everywhere."""
+    if kind == "random":
+        s = 1.0 + 2.5 * rand((B, 1, H, W), torch.float64, seed=seed)
+    elif kind == "levels":
+        b, y, x = torch.arange(B).view(B, 1, 1, 1), torch.arange(H).view(1, 1, H, 1), torch.arange(W).view(1, 1, 1, W)
+        s = 1.0 + 0.5 * ((x + 2 * y + 3 * b) % 6).double()
+    else:
+        raise ValueError(kind)
+    s = s.to(dtype).contiguous()
+    assert s.double().min().item() >= SIGMA_MIN and s.double().max().item() <= SIGMA_MAX, (kind, dtype)
+    return s
+
+
+def rs_sigma(shape, dtype, kind, k, field):
+    """the sigma field of one sigma-field case of resample2d (seeded by the case, like its `inputs`)"""
+    B, C, Hs, Ws, Hf, Wf = shape
+    seed = 9000 + 100 * (SHAPES.index(shape) if shape in SHAPES else len(SHAPES)) + 10 * KINDS16.index(kind) + k
+    return sigma_field(field, B, Hf, Wf, dtype, seed)
+
+
+def rs_sigma_inputs(shape, dtype, kind, k, field):
+    """The stored inputs of one sigma-field case of resample2d: (input1, flow, upstream) of `inputs` and the sigma field"""
+    return inputs("rs", shape, dtype, kind, k) + (rs_sigma(shape, dtype, kind, k, field),)
 
 
 def coordinate_bound(f, span):

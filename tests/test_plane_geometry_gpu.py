@@ -8,6 +8,13 @@ their share on these very inputs), nothing is ever left out of a forward result 
 compares anything it asks gfla_lds_plane_geometry whether the geometry it meant is the one in force, and the dispatch trace
 whether the family ran.  Forward results must not change by a bit with G and split: the forwards have no atomics.
 
+resample2d runs twice: as the module (a constant sigma plane, d/d sigma dropped by autograd's cat), and as
+Resample2dFunction with input2 = (dx, dy, sigma), one sigma per pixel (plane_util.sigma_field) and both inputs as leaves, so
+a kernel that reads sigma at the wrong (b, y, x) or puts d/d sigma in the wrong place is beyond the bar.  The second form
+also runs over the routes the geometry keys do not select: the coefficient table and the fixed-point scatter, double planes,
+the matrix-core product off and forced, the streaming d/d input2 kernel and rs_lds_kernel in its place, the global kernels,
+and the float32 widening of a refused 16-bit backward.
+
 No case sets key 5 together with 16-bit storage.  Key 10 = 16 goes with key 30 = 1 (plane_util.WINDOWS): with key 10 alone
 the few planes of these shapes would go to the tile kernels of csrc/tile_map.h instead of row windows."""
 import pytest
@@ -83,6 +90,37 @@ def rs_case(shape, dtype, kind, k, dil):
     return cached(("rs", shape, dtype, kind, k, dil), make)
 
 
+def rs_sigma_case(shape, dtype, kind, k, dil, field):
+    """resample2d with one sigma per pixel: input2 = (dx, dy, sigma) as the entry points take it.  P is a field with KAPPA
+    (plane_util's docstring); the gradient of the feature map takes its largest value."""
+    def of_flow(f):          # shared by the fields of one flow
+        # no coordinate floors differently in the kernels' arithmetic: the forward and d/d sigma are compared everywhere
+        assert torch.equal(pu.rs_coordinates(f, pu.ARITH[dtype]).floor().double(), pu.rs_coordinates(f).floor())
+        return pu.coordinate_bound(f, (k // 2) * dil), ~pu.rs_flow_kinks(f, k, dil, shape[2], shape[3], pu.ARITH[dtype])
+
+    def make():
+        s, f, up = cached(("rs in", shape, dtype, kind, k), lambda: pu.inputs("rs", shape, dtype, kind, k))
+        sig = pu.rs_sigma(shape, dtype, kind, k, field)
+        assert sig.double().min().item() >= pu.SIGMA_MIN            # what the bar's derivation stands on
+        bound, keep = cached(("rs flow", shape, dtype, kind, k, dil), lambda: of_flow(f))
+        P = bound * pu.rs_kappa(k, dil, sig) ** 2
+        ref = pu.resample2d(s, f, up, k, dil, sigma=sig)
+        P_of = {"out": P, "g_input1": P.max().item(), "g_flow": P, "g_sigma": P}
+        # the bar of each result, kept with the reference: a case compares up to three runs under every geometry
+        bars = {name: pu.bar(ref[name][1], ref[name][0], ref[name][2], P_of[name], dtype) for name in P_of}
+        return {"in": (s, torch.cat((f, sig), 1).contiguous(), up), "ref": ref, "P": P_of, "bar": bars, "keep": keep}
+    return cached(("rs sigma", shape, dtype, kind, k, dil, field), make)
+
+
+def device_leaves(c, which):
+    """fresh leaves of the case's inputs on the device (copied there once per case) and its upstream gradient; `which`:
+    indices of the inputs that require a gradient"""
+    if "dev" not in c:
+        c["dev"] = [x.to(DEV) for x in c["in"]]
+    s, i2, up = c["dev"]
+    return [x.detach().clone().requires_grad_(i in which) for i, x in enumerate((s, i2))], up
+
+
 # ------------------------------------------------------------------------------------------------------------- the harness
 class Report(object):
     """Collects every comparison of one test, prints each figure, fails at the end with all of them"""
@@ -90,10 +128,10 @@ class Report(object):
     def __init__(self, what):
         self.what, self.bad, self.worst = what, [], {}
 
-    def compare(self, name, got, entry, P, dtype, keep=None, extra=None, tag=""):
+    def compare(self, name, got, entry, P, dtype, keep=None, extra=None, tag="", bar=None):
         ref, A, n = entry
         assert got.dtype == dtype and tuple(got.shape) == tuple(ref.shape), (name, got.dtype, tuple(got.shape), tuple(ref.shape))
-        ratio, beyond = pu.worst(got, ref, A, n, P, dtype, keep, extra)    # extra: resample2d's fixed-point planes
+        ratio, beyond = pu.worst(got, ref, A, n, P, dtype, keep, extra, bar)    # extra: resample2d's fixed-point planes
         print("  %-9s %-40s err/bar %.3f" % (name, tag, ratio))
         self.worst[name] = max(self.worst.get(name, 0.0), ratio)
         if beyond:
@@ -317,6 +355,163 @@ def test_resample2d_over_geometries(gfla, dtype, geo):
                         _, (_, gfa) = grads(mod, (s, f), up, (1,))
                         rep.compare("g_input1", g1a, c["ref"]["g_input1"], c["P"], dtype, extra=fix, tag=tag + " alone")
                         rep.compare("g_flow", gfa, c["ref"]["g_flow"], c["P"], dtype, c["keep"], tag=tag + " alone")
+    rep.finish()
+
+
+# --------------------------------------------------------------------------------------- resample2d, one sigma per pixel
+RS_FIELD_KD = ((4, 1), (2, 1), (4, 2), (6, 1))       # (6, 1): KH = 3
+
+
+def rs_field_run(fn, c, which):
+    """forward and backward of fn on fresh leaves of case c; (out, d/d input1, d/d input2) as host tensors, None where not
+    asked for"""
+    (a, b), up = device_leaves(c, which)
+    out = fn(a, b)
+    out.backward(up)
+    return [None if t is None else t.detach().cpu() for t in (out, a.grad, b.grad)]
+
+
+def rs_field_compare(rep, c, out, g1, g2, dtype, fix, tag):
+    """the four results of one sigma-field run; g2 = d/d (dx, dy, sigma) in the storage type, None entries are not compared"""
+    ref, P, bar = c["ref"], c["P"], c["bar"]
+    if out is not None:
+        rep.compare("out", out, ref["out"], P["out"], dtype, tag=tag, bar=bar["out"])
+    if g1 is not None:
+        rep.compare("g_input1", g1, ref["g_input1"], P["g_input1"], dtype, extra=fix, tag=tag, bar=bar["g_input1"])
+    if g2 is not None:
+        assert g2.dtype == dtype and g2.shape[1] == 3, (tag, g2.dtype, tuple(g2.shape))      # the storage type
+        rep.compare("g_flow", g2[:, :2], ref["g_flow"], P["g_flow"], dtype, c["keep"], tag=tag, bar=bar["g_flow"])
+        # everywhere: d/d sigma has no kinks of its own
+        rep.compare("g_sigma", g2[:, 2:], ref["g_sigma"], P["g_sigma"], dtype, tag=tag, bar=bar["g_sigma"])
+
+
+RS_FIELD_PAIRS = (("wild", "levels"), ("wild", "random"), ("smooth", "levels"), ("smooth", "random"))
+
+
+def rs_field_runs(dtype, si, ki):
+    """[(flow kind, sigma field, each gradient alone as well)] of shape `si` of pu.SHAPES at entry `ki` of RS_FIELD_KD.  Wild
+    and smooth flows under both fields, three of the four pairs per case: the pair left out rotates with si + ki, so every
+    pair runs at two or three of the first three (k, dil) of every shape, every case has both kinds and both fields, and
+    each gradient is requested alone on its first wild pair.  `oob` (16-bit storage) puts every tap of a pixel on one corner
+    of the map; the normalised weights then sum to 1 whatever sigma is and d/d sigma is a difference of two equal sums: one
+    field.
+
+    All four pairs at every case is beyond 1.5 x the time of the constant-sigma test of the same id: the first geometry of
+    a storage type evaluates every reference on the host.  For the same reason kernel_size 6 (KH = 3), whose 36 taps cost
+    the host twice the time of 16, runs in float32 and float64 only (the arithmetic of 16-bit storage is the float32 one),
+    one wild and one smooth pair at the two small shapes and the wild pair at the two large ones, the fields swapped from
+    shape to shape."""
+    if RS_FIELD_KD[ki][0] == 6:
+        if dtype in (F16, BF16):
+            return []
+        runs = [RS_FIELD_PAIRS[si % 2]] + ([RS_FIELD_PAIRS[3 - si % 2]] if si < 2 else [])
+    else:
+        runs = [pair for i, pair in enumerate(RS_FIELD_PAIRS) if i != (si + ki) % 4]
+        assert {r[0] for r in runs} == {"wild", "smooth"} and {r[1] for r in runs} == set(pu.SIGMA_FIELDS)
+    assert runs[0][0] == "wild"
+    runs = [(kind, field, (kind, field) == runs[0]) for kind, field in runs]
+    return runs + ([("oob", "random", False)] if dtype in (F16, BF16) else [])
+
+
+@pytest.mark.parametrize("dtype,geo", CASES, ids=CASE_IDS)
+def test_resample2d_sigma_field_over_geometries(gfla, dtype, geo):
+    """Resample2dFunction with input2 = (dx, dy, sigma) and BOTH inputs as leaves: sigma varies from pixel to pixel
+    (plane_util.sigma_field) and d/d sigma, which the module form drops, is compared at every pixel."""
+    from global_flow_local_attention_amd import _lib
+    keys = geo_of(dtype, geo)
+    rep = Report("resample2d sigma field %s %s" % (NAMES[dtype], keys))
+    with pu.Tuning(gfla, keys):
+        for si, shape in enumerate(pu.SHAPES):
+            for ki, (k, dil) in enumerate(RS_FIELD_KD):
+                fn = lambda a, b: gfla.Resample2dFunction.apply(a, b, k, dil)
+                runs = rs_field_runs(dtype, si, ki)
+                if not runs:
+                    continue
+                assert check_geometry(_lib, 5, shape, k, dil, dtype, keys)["G"] > 0
+                check_geometry(_lib, 6, shape, k, dil, dtype, keys)
+                check_geometry(_lib, 7, shape, k, dil, dtype, keys)
+                for kind, field, alone in runs:
+                    c = rs_sigma_case(shape, dtype, kind, k, dil, field)
+                    tag = "%s k%d d%d %s %s" % (shape, k, dil, kind, field)
+                    out, g1, g2 = rs_field_run(fn, c, (0, 1))
+                    fix = cached(("rs fix", shape, dtype, kind, k, dil, field),
+                                 lambda: pu.rs_fixed_point_term(c["ref"]["g_input1_count"], c["in"][2], dtype))
+                    rs_field_compare(rep, c, out, g1, g2, dtype, fix, tag)
+                    want = default_forward(gfla, ("rs sigma", shape, dtype, kind, k, dil, field), lambda: fn(*c["dev"][:2]))
+                    rep.same_bits("out", out, want[0], tag)
+                    if alone:
+                        _, g1a, none2 = rs_field_run(fn, c, (0,))
+                        _, none1, g2a = rs_field_run(fn, c, (1,))
+                        assert none1 is None and none2 is None
+                        rs_field_compare(rep, c, None, g1a, g2a, dtype, fix, tag + " alone")
+    rep.finish()
+
+
+# the routes the geometry keys do not select (csrc/gs_route.h: rs_fwd_route / rs_bwd_route; key 14: csrc/patch_mfma.hip)
+ROUTES = [({}, (F32, F64, F16, BF16)),     # coefficient table + fixed point, streaming d/d input2, the product where it pays
+          ({23: 1}, (F32,)),               # double planes, no table
+          ({23: 2}, (F32,)),               # fixed point without the table
+          ({22: 1}, (F32, F16, BF16)),     # rs_lds_kernel gathers d/d input2 instead of the streaming kernel
+          ({14: 1}, (F32,)),               # matrix-core product off
+          ({14: 2}, (F32,)),               # ... wherever the shape is supported
+          ({6: 1}, (F32, F64))]            # global kernels (16-bit storage ignores the key)
+ROUTE_CASES = [(keys, dt) for keys, dts in ROUTES for dt in dts]
+ROUTE_IDS = ["%s-%s" % (",".join("%d=%d" % kv for kv in sorted(keys.items())) or "default", NAMES[dt]) for keys, dt in ROUTE_CASES]
+
+
+@pytest.mark.parametrize("keys,dtype", ROUTE_CASES, ids=ROUTE_IDS)
+def test_resample2d_sigma_field_over_routes(gfla, keys, dtype):
+    """The same comparison on the routes that build the per-pixel weights away from the plain kernels.  What a route
+    shows of itself is asserted: the planes-in-LDS query (ops 5-7) says whole planes, or `not taken` under key 6 = 1, and
+    the big-plane counters 15-17 stay put.  Every route float32-sums products or scatters into the fixed-point planes:
+    plane_util.rs_input1_term."""
+    import ctypes
+    import gs_route_util
+    from global_flow_local_attention_amd import _lib
+    rep = Report("resample2d sigma field routes %s %s" % (NAMES[dtype], keys))
+    is_global = keys.get(6) == 1 and dtype in (F32, F64)
+    big = [_lib.path_count(i) for i in (15, 16, 17)]
+    with pu.Tuning(gfla, keys):
+        for shape in (pu.SHAPES[0], pu.SHAPES[1], gs_route_util.S):
+            for k, dil in ((4, 1), (4, 2), (2, 1)):
+                fn = lambda a, b: gfla.Resample2dFunction.apply(a, b, k, dil)
+                for qop in (5, 6, 7):
+                    g = pu.query(_lib, qop, shape, k, dil, elem_of(dtype))
+                    assert (g["G"] == 0) if is_global else (g["G"] >= 1 and g["margin"] < 0 and g["split"] == 1), (qop, shape, keys, g)
+                if shape == gs_route_util.S and (k, dil) == (4, 1) and dtype != F64 and not is_global:
+                    # the streaming d/d input2 kernel can take the shape (a K = 3 patch)
+                    assert _lib.lib().gfla_aggregate_fwd_geometry(*shape, 3, (ctypes.c_int64 * 9)()) == 0
+                for field in pu.SIGMA_FIELDS:
+                    c = rs_sigma_case(shape, dtype, "wild", k, dil, field)
+                    tag = "%s k%d d%d wild %s" % (shape, k, dil, field)
+                    out, g1, g2 = rs_field_run(fn, c, (0, 1))
+                    fix = pu.rs_input1_term(c["ref"]["g_input1_count"], c["in"][2], dtype, keys)
+                    rs_field_compare(rep, c, out, g1, g2, dtype, fix, tag)
+    assert [_lib.path_count(i) for i in (15, 16, 17)] == big, "a big-plane kernel took a call"
+    rep.finish()
+
+
+def test_resample2d_sigma_field_through_the_widened_16_bit_backward(gfla):
+    """bfloat16 planes beyond a forced 16 KB budget: the bfloat16 backward entry point refuses, Resample2dFunction widens
+    the three inputs to float32 -- the sigma plane with them -- and rounds once at the end."""
+    import gs_route_util
+    from global_flow_local_attention_amd import _lib
+    shape, dtype, k, dil = gs_route_util.W, BF16, 4, 1
+    B, C, Hi, Wi, H, W = shape
+    rep = Report("resample2d sigma field widened bf16")
+    with pu.Tuning(gfla, {10: 16}):
+        for field in pu.SIGMA_FIELDS:
+            c = rs_sigma_case(shape, dtype, "wild", k, dil, field)
+            (a, b), g = device_leaves(c, ())
+            g1, g2 = torch.zeros_like(a), torch.zeros(B, 3, H, W, dtype=F32, device=DEV)
+            with pytest.raises(_lib.Unsupported):
+                _lib.call("gfla_resample2d_bwd_bf16", a, _lib.ptr(a), _lib.ptr(b), _lib.ptr(g), _lib.ptr(g1), _lib.ptr(g2),
+                          B, C, Hi, Wi, H, W, k, dil, 1)
+            before = [_lib.path_count(i) for i in (16, 17)]
+            out, g1, g2 = rs_field_run(lambda x, y: gfla.Resample2dFunction.apply(x, y, k, dil), c, (0, 1))
+            assert [_lib.path_count(i) for i in (16, 17)] == [before[0] + 1, before[1] + 1]      # the float32 big-plane kernels
+            fix = pu.rs_fixed_point_term(c["ref"]["g_input1_count"], c["in"][2], dtype)
+            rs_field_compare(rep, c, out, g1, g2, dtype, fix, "%s k%d d%d wild %s" % (shape, k, dil, field))
     rep.finish()
 
 
