@@ -29,6 +29,8 @@ from .conv3d import (AvgPoolFramesFunction, Conv3dFramesFunction, avg_pool_frame
 from .adam import FusedAdam  # noqa: F401
 from .pose_inputs import (PoseInputs, normalize_images, pose_cords, pose_maps, torch_normalize_images,  # noqa: F401
                           torch_pose_cords, torch_pose_maps)
+from .image_inputs import (affine_images, augmentation_matrices, resize_images, torch_affine_images,  # noqa: F401
+                           torch_resize_images)
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401
 from .face_step import (DualStreamAttn, MaskBlendFunction, face_target_forward, generate_frames,  # noqa: F401

@@ -14,6 +14,7 @@
 // normalize_images stages 1024 interleaved pixels in LDS with 16-byte loads, at the byte phase of their address, and
 // writes each channel's span through a 256-entry table of ((v / 255) - mean) / std, one entry per thread.
 #include "gfla_common.h"
+#include "span_store.h"
 
 namespace gfla {
 
@@ -22,34 +23,6 @@ constexpr int64_t kPoseMaxW = 4096;            // ex[W] (skewed: + W / 32) + ey[
 constexpr double kPoseClamp = 1073741824.0;    // 2^30
 constexpr int kNormPix = 1024;                 // pixels per workgroup: 4 KB of uint8 at C = 4
 constexpr int64_t kMaxGrid = 2147483647;
-
-// n elements at dst, any multiple of sizeof(T).  A generator yields the elements in the arithmetic type: seek(k) positions
-// it at element k, next() yields that element and moves on by one, pack(q) fills a pack with the V elements at its position
-// without moving, jump(m) moves it on by m elements (always kBlock * V here).  A thread divides once, in its first seek.
-template <typename T, typename Gen>
-__device__ __forceinline__ void store_span(T *dst, int n, Gen &gen) {
-  constexpr int V = 16 / (int)sizeof(T);
-  const int tid = threadIdx.x;
-  int head = (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) / sizeof(T));
-  if (head > n) head = n;
-  if (tid < head) {
-    gen.seek(tid);
-    dst[tid] = Num<T>::from(gen.next());
-  }
-  const int nv = (n - head) / V;
-  if (tid < nv) gen.seek(head + tid * V);
-  for (int v = tid; v < nv; v += kBlock) {
-    Pack<T, V> q;
-    gen.pack(q);
-    *reinterpret_cast<Pack<T, V> *>(dst + head + v * V) = q;
-    gen.jump(kBlock * V);
-  }
-  const int done = head + nv * V;
-  if (tid < n - done) {
-    gen.seek(done + tid);
-    dst[done + tid] = Num<T>::from(gen.next());
-  }
-}
 
 // ---- key points -> heat maps ---------------------------------------------------------------------------------------
 // ex lives in LDS skewed by one double per 32: the lanes of a wave, whose columns are V apart, then read from 32 different
@@ -249,28 +222,6 @@ static int pose_cords(const T *maps, int64_t *out, int64_t planes, int64_t H, in
 }
 
 // ---- uint8 images -> network input ---------------------------------------------------------------------------------
-struct NormCoef {
-  float mean[4], std[4];
-};
-
-struct NormGen {
-  const uint8_t *px;                                 // this channel's first byte of the staged pixels
-  const float *lut;
-  int C, at;
-  __device__ __forceinline__ void seek(int k) { at = k * C; }
-  __device__ __forceinline__ void jump(int m) { at += m * C; }
-  __device__ __forceinline__ float next() {
-    const float v = lut[px[at]];
-    at += C;
-    return v;
-  }
-  template <typename T, int V>
-  __device__ __forceinline__ void pack(Pack<T, V> &q) const {
-#pragma unroll
-    for (int i = 0; i < V; ++i) q.v[i] = Num<T>::from(lut[px[at + i * C]]);
-  }
-};
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void normalize_images_kernel(const uint8_t *__restrict__ images, T *__restrict__ out,
                                                                   int64_t P, int C, int chunks, NormCoef coef) {
@@ -281,11 +232,7 @@ __global__ __launch_bounds__(kBlock) void normalize_images_kernel(const uint8_t 
   const int npix = (int)min((int64_t)kNormPix, P - p0);
   const int nbytes = npix * C;
   const int tid = threadIdx.x;
-  {
-#pragma clang fp contract(off)
-    const float q = (float)tid / 255.f;
-    for (int c = 0; c < C; ++c) lut[c * 256 + tid] = (q - coef.mean[c]) / coef.std[c];
-  }
+  norm_lut_fill(lut, C, coef);
   const uint8_t *src = images + (b * P + p0) * C;
   uint8_t *bytes = reinterpret_cast<uint8_t *>(raw);
   const int phase = (int)(reinterpret_cast<uintptr_t>(src) & 15u);

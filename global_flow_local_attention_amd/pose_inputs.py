@@ -8,7 +8,8 @@ key points and uint8 pixels -- and the tensors PoseGenerator.forward takes.
 
 GPU tensors run on the library's kernels.  CPU tensors, and impl="torch" on any device, take the torch compositions
 below: the same float64 / float32 expressions in the same order, which the tests pin to the reference on the host and
-compare the kernels with on the device.  Datasets, file formats and the PIL augmentation of the image stay in the loader.
+compare the kernels with on the device.  The PIL augmentation of the pixels is image_inputs.py's: PoseInputs takes its inverse
+matrices as warp1 / warp2.
 """
 import ctypes
 import functools
@@ -265,20 +266,26 @@ class PoseInputs(object):
 
         inputs = PoseInputs((256, 176), old_size=(256, 176))
         batch = inputs(P1_u8, P2_u8, cords1, cords2, affine1, affine2)      # {"P1", "BP1", "P2", "BP2"} on the device
+        inverse, forward = augmentation_matrices(angle, shift, scale, (256, 176))
+        batch = inputs(P1_u8, P2_u8, cords1, cords2, forward, None, warp1=inverse)          # P1 augmented on the device
 
-    P*_u8: (B, H, W, C) uint8, already augmented by the loader; cords*: (B, J, 2) key points, rows (y, x); affine*: None or
-    the (B, 3, 3) / (B, 2, 3) float64 matrices the images were augmented with.  Host tensors are copied non_blocking from
+    P*_u8: (B, H, W, C) uint8; cords*: (B, J, 2) key points, rows (y, x); affine*: None or the (B, 3, 3) / (B, 2, 3) float64
+    forward matrices the key points are augmented with; warp*: None -- the image is already augmented, or is not to be --
+    or the (B, 2, 3) float64 inverse matrices affine_images warps it with, out-of-frame pixels taking `fill`
+    (image_inputs.augmentation_matrices makes both kinds).  Host tensors are copied non_blocking from
     pinned staging this object owns: two sets take turns, each behind the event of its last copies, so a set is never
     rewritten while a copy may still read it; nothing else waits for the device and nothing reads from it.  With device
     tensors no copy is made, and the call may be captured in a graph: replaying after the key points (or the pixels) were
     overwritten in place gives the new tensors."""
 
-    def __init__(self, size, old_size=None, sigma=6.0, dtype=torch.float32, device="cuda", mean=0.5, std=0.5):
+    def __init__(self, size, old_size=None, sigma=6.0, dtype=torch.float32, device="cuda", mean=0.5, std=0.5, fill=128):
         self.size = _size(size, "PoseInputs: size")
         self.old_size = self.size if old_size is None else _size(old_size, "PoseInputs: old_size")
         _two_sigma_sq(sigma)
         self.sigma, self.dtype = float(sigma), _storage(dtype, "PoseInputs: dtype")
-        self.mean, self.std = mean, std
+        from .image_inputs import _fill_values
+        _fill_values(fill, len(fill) if isinstance(fill, (tuple, list)) else 1)
+        self.mean, self.std, self.fill = mean, std, fill
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise NotImplementedError("GFLA ops run on the GPU only (got device %s); there is no CPU path" % (self.device,))
@@ -294,8 +301,14 @@ class PoseInputs(object):
         pinned.copy_(t)
         return pinned.to(self.device, non_blocking=True)
 
-    def __call__(self, P1_u8, P2_u8, cords1, cords2, affine1=None, affine2=None):
-        records = (P1_u8, P2_u8, cords1, cords2, affine1, affine2)
+    def _image(self, images_u8, warp):
+        if warp is None:
+            return normalize_images(images_u8, self.mean, self.std, self.dtype)
+        from .image_inputs import affine_images
+        return affine_images(images_u8, warp, self.fill, self.mean, self.std, self.dtype)
+
+    def __call__(self, P1_u8, P2_u8, cords1, cords2, affine1=None, affine2=None, warp1=None, warp2=None):
+        records = (P1_u8, P2_u8, cords1, cords2, affine1, affine2, warp1, warp2)
         if any(t is not None and not t.is_cuda for t in records):
             stage = self._staging[self._turn]
             self._turn = 1 - self._turn
@@ -306,9 +319,9 @@ class PoseInputs(object):
                 if stage.event is None:
                     stage.event = torch.cuda.Event()
                 stage.event.record(torch.cuda.current_stream(self.device))
-        P1_u8, P2_u8, cords1, cords2, affine1, affine2 = records
+        P1_u8, P2_u8, cords1, cords2, affine1, affine2, warp1, warp2 = records
         maps = dict(size=self.size, old_size=self.old_size, sigma=self.sigma, dtype=self.dtype)
-        return {"P1": normalize_images(P1_u8, self.mean, self.std, self.dtype),
+        return {"P1": self._image(P1_u8, warp1),
                 "BP1": pose_maps(cords1, affine=affine1, **maps),
-                "P2": normalize_images(P2_u8, self.mean, self.std, self.dtype),
+                "P2": self._image(P2_u8, warp2),
                 "BP2": pose_maps(cords2, affine=affine2, **maps)}

@@ -884,6 +884,10 @@ int gfla_head_conv3x3_bwd_bf16(const uint16_t *x, const float *w, const uint16_t
  * gfla_normalize_images_*, declared and documented in gfla_pose.h ---- */
 #include "gfla_pose.h"
 
+/* ---- image inputs: Pillow's nearest-neighbour affine transform fused with ToTensor + Normalize, Pillow's 8-bit resize
+ * (csrc/image_inputs.hip): gfla_affine_images_*, gfla_resize_pass_u8, declared and documented in gfla_image.h ---- */
+#include "gfla_image.h"
+
 #ifdef __cplusplus
 }
 #endif
