@@ -1,7 +1,8 @@
 """ctypes binding of libgfla_hip.so.
 
 include/gfla_hip.h is the single description of the C ABI: the argument and return types of every entry point, the
-dispatch-trace ids (enum gfla_path -> PATH_*), the status codes and ABI_VERSION are read from it, never restated here.
+dispatch-trace ids (enum gfla_path -> PATH_*), the tuning keys (enum gfla_tuning_key -> TUNE_*), the status codes and
+ABI_VERSION are read from it, never restated here.
 Headers it includes (include/gfla_gen_conv.h, include/gfla_lds_plane.h, include/gfla_spectral_norm.h,
 include/gfla_conv3d.h, include/gfla_adam.h, include/gfla_pose.h, include/gfla_image.h) are read in the same way.
 
@@ -9,6 +10,7 @@ The library is the only implementation of the ops: there is no Python/torch fall
 is missing or fails to load, importing an op raises; if a call returns a non-zero status, a
 RuntimeError is raised (the reference swallows native errors, block_extractor_cuda.cc:11).
 """
+import contextlib
 import ctypes
 import os
 import re
@@ -98,6 +100,9 @@ ABI_VERSION = _CONSTANTS["GFLA_ABI_VERSION"]
 _ERR_UNSUPPORTED = _CONSTANTS["GFLA_ERR_UNSUPPORTED"]
 # dispatch-trace ids: GFLA_PATH_X of enum gfla_path is PATH_X here (PATH_BE_BWD_LDS ... PATH_COUNT)
 globals().update((name[len("GFLA_"):], value) for name, value in _CONSTANTS.items() if name.startswith("GFLA_PATH_"))
+# tuning keys: GFLA_TUNE_X of enum gfla_tuning_key is TUNE_X here; the header says what each selects and who reads it
+TUNING_KEYS = {name[len("GFLA_"):]: value for name, value in _CONSTANTS.items() if name.startswith("GFLA_TUNE_")}
+globals().update(TUNING_KEYS)
 
 
 def exported_symbols():
@@ -257,8 +262,25 @@ def unfold_supported(Hs, Ws, k, elem_size):
 
 
 def set_tuning(key, value):
-    """Process-global tuning knob (include/gfla_hip.h); returns the old value."""
+    """Process-global tuning knob `key` (a TUNE_* of include/gfla_hip.h: enum gfla_tuning_key); returns the old value.
+    ValueError for a key that is no enumerator: the library would accept it and do nothing."""
+    if int(key) not in TUNING_KEYS.values():
+        raise ValueError("set_tuning: %r is no tuning key of include/gfla_hip.h (enum gfla_tuning_key)" % (key,))
     return lib().gfla_set_tuning(int(key), int(value))
+
+
+@contextlib.contextmanager
+def tuned(keys):
+    """with tuned({TUNE_X: value, ...}): the keys set for the block, their previous values back on every way out, in
+    reverse order.  Nests."""
+    old = []
+    try:
+        for key, value in keys.items():
+            old.append((key, set_tuning(key, value)))
+        yield
+    finally:
+        for key, value in reversed(old):
+            set_tuning(key, value)
 
 
 def fc_path(mode, backward=False):

@@ -241,21 +241,26 @@ inline AggStreamGeo agg_stream_geometry(int64_t B, int64_t C, int64_t Hs, int64_
       twl = cand;
     }
   }
-  if (tuning(16) == 8 || tuning(16) == 16 || tuning(16) == 32) twl = tuning(16) == 8 ? 3 : tuning(16) == 16 ? 4 : 5;
+  if (tuning(GFLA_TUNE_AGG_STREAM_TILE_W) == 8 || tuning(GFLA_TUNE_AGG_STREAM_TILE_W) == 16 ||
+      tuning(GFLA_TUNE_AGG_STREAM_TILE_W) == 32)
+    twl = tuning(GFLA_TUNE_AGG_STREAM_TILE_W) == 8 ? 3 : tuning(GFLA_TUNE_AGG_STREAM_TILE_W) == 16 ? 4 : 5;
   const int64_t ntile = ceil_div(W, 1 << twl) * ceil_div(H, 64 >> twl);
-  const int64_t tmax = tuning(9) >= 64 && tuning(9) <= kAggStreamWaves * 64 ? tuning(9) / 64 : kAggStreamWaves;  // tiles (waves) per workgroup
+  // tiles (waves) per workgroup
+  const int64_t tmax = tuning(GFLA_TUNE_AGG_STREAM_THREADS) >= 64 && tuning(GFLA_TUNE_AGG_STREAM_THREADS) <= kAggStreamWaves * 64
+                           ? tuning(GFLA_TUNE_AGG_STREAM_THREADS) / 64 : kAggStreamWaves;
   const int64_t tgroups = ceil_div(ntile, tmax);
   const int64_t twg = ceil_div(ntile, tgroups);  // balanced
   const int64_t threads = twg * 64;
   int pitch = (int)(ceil_div(2 * Ws + 32, 64) * 64 - 32);  // smallest value >= 2 Ws that is 32 mod 64
-  if (tuning(17) >= 2 * Ws && !(tuning(17) & 3)) pitch = tuning(17);  // experiment: pair pitch in words
+  if (tuning(GFLA_TUNE_AGG_STREAM_PITCH) >= 2 * Ws && !(tuning(GFLA_TUNE_AGG_STREAM_PITCH) & 3))
+    pitch = tuning(GFLA_TUNE_AGG_STREAM_PITCH);  // experiment: pair pitch in words
   const int64_t per_plane = ceil_div(Hs, 2) * pitch * 4;
   const int64_t budget = 160 * 1024 - 64;
   // chunk: as many planes as two buffers fit and kAggPre word pairs per thread cover
   int64_t CH = std::min<int64_t>((budget / 2 - 16) / per_plane, kAggPre * threads / (Hs * (Ws / 2)));
   if (CH > C) CH = C;
   if (CH > kAggMaxChunk) CH = kAggMaxChunk;   // the forward kernel keeps a chunk's results in registers
-  if (tuning(4) > 0 && tuning(4) < CH) CH = tuning(4);
+  if (tuning(GFLA_TUNE_G_CAP) > 0 && tuning(GFLA_TUNE_G_CAP) < CH) CH = tuning(GFLA_TUNE_G_CAP);
   if (CH >= 2) CH &= ~1LL;  // channel pairs
   if (CH < 1) return g;
   // channel ranges: more of them = more workgroups, fewer chunks each (the first chunk of a workgroup is not overlapped)
@@ -272,7 +277,7 @@ inline AggStreamGeo agg_stream_geometry(int64_t B, int64_t C, int64_t Hs, int64_
       best_ns = ns;
     }
   }
-  if (tuning(5) > 0) best_ns = tuning(5);
+  if (tuning(GFLA_TUNE_SPLIT) > 0) best_ns = tuning(GFLA_TUNE_SPLIT);
   const int64_t CS = ceil_div(ceil_div(C, best_ns), CH) * CH;
   g = AggStreamGeo{(int)CH, (int)CS, (int)ceil_div(C, CS), (int)tgroups, (int)threads, pitch, twl, (int)ntile,
                    (unsigned)(2 * (CH * per_plane + 16))};

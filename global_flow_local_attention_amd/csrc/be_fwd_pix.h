@@ -265,7 +265,7 @@ inline PixGeo pix_geometry(int CH, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
   if (G > C) G = C;
   if (G >= CH) G = (G / CH) * CH;
   const int64_t HW = Hf * Wf, nblk = ceil_div(HW, 64);
-  if (tuning(4) > 0) G = tuning(4) < G ? tuning(4) : G;
+  if (tuning(GFLA_TUNE_G_CAP) > 0) G = tuning(GFLA_TUNE_G_CAP) < G ? tuning(GFLA_TUNE_G_CAP) : G;
   else if (G > CH && nblk >= 8) G = CH;
   g.G = (int)G;
   g.ngroups = (int)ceil_div(C, G);
@@ -274,11 +274,11 @@ inline PixGeo pix_geometry(int CH, int64_t B, int64_t C, int64_t Hs, int64_t Ws,
   // 40.6 us, 11 waves (one block each) 46.4, 16 waves 46.3 (profiles/r4_be_fwd_pix_threads.txt)
   const int64_t items = nblk * ceil_div(G, CH);
   int waves = items < 8 ? (int)items : 8;
-  if (tuning(24) >= 64) waves = tuning(24) / 64;
+  if (tuning(GFLA_TUNE_BE_FWD_THREADS) >= 64) waves = tuning(GFLA_TUNE_BE_FWD_THREADS) / 64;
   if (waves < 1) waves = 1;
   if (waves > 16) waves = 16;
   g.threads = waves * 64;
-  g.split = tuning(5) > 0 ? tuning(5) : 1;
+  g.split = tuning(GFLA_TUNE_SPLIT) > 0 ? tuning(GFLA_TUNE_SPLIT) : 1;
   g.lds_bytes = (unsigned)(G * plane_bytes);
   return g;
 }
@@ -294,11 +294,11 @@ static int launch_fwd_pix(const PixGeo &g, const T *src, const T *flow, T *out, 
 #define GFLA_PIX_LAUNCH(NT_, ABL_)                                                                                      \
   launch_lds(be_fwd_pix_kernel<T, K, CH, NT_, ABL_>, grid, block, g.lds_bytes, stream, src, flow, out, (int)C, (int)Hs,   \
              (int)Ws, (int)Hf, (int)Wf, g.G, g.ngroups, g.split)
-  if (tuning(25) == 1) GFLA_PIX_LAUNCH(true, 0);   // non-temporal stores: measured at half the rate, kept for A/B
+  if (tuning(GFLA_TUNE_BE_FWD_PIX_NT) == 1) GFLA_PIX_LAUNCH(true, 0);   // non-temporal stores: measured at half the rate, kept for A/B
 #ifdef GFLA_PROBES   // timing ablations (results are garbage): key 27 bit 0 = no patch reads, bit 1 = no stores
-  else if (tuning(27) == 1) GFLA_PIX_LAUNCH(false, 1);
-  else if (tuning(27) == 2) GFLA_PIX_LAUNCH(false, 2);
-  else if (tuning(27) == 3) GFLA_PIX_LAUNCH(false, 3);
+  else if (tuning(GFLA_TUNE_BE_FWD_PROBE) == 1) GFLA_PIX_LAUNCH(false, 1);
+  else if (tuning(GFLA_TUNE_BE_FWD_PROBE) == 2) GFLA_PIX_LAUNCH(false, 2);
+  else if (tuning(GFLA_TUNE_BE_FWD_PROBE) == 3) GFLA_PIX_LAUNCH(false, 3);
 #endif
   else GFLA_PIX_LAUNCH(false, 0);
 #undef GFLA_PIX_LAUNCH

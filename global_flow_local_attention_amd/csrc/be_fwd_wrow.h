@@ -232,7 +232,7 @@ inline WrowGeo wrow_geometry(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64
                              int elem_bytes) {
   WrowGeo g{0, 0, 0, 0, 0, 0, 0};
   if (Wf > 64 || Wf < 1) return g;
-  const int64_t budget = tuning(10) >= 16 ? lds_budget() : 78 * 1024;
+  const int64_t budget = tuning(GFLA_TUNE_LDS_KB) >= 16 ? lds_budget() : 78 * 1024;
   const int64_t plane_bytes = Hs * (Ws + 2 * K) * acc_bytes;
   const int64_t rpw = 64 / Wf;
   const int64_t tile_stride = (rpw * K * K * Wf * elem_bytes + 16 + 15) & ~(int64_t)15;   // + room for the 16-byte phase
@@ -240,12 +240,12 @@ inline WrowGeo wrow_geometry(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64
   int64_t waves = 0, G = 0;
   const int64_t slots = 2 * kNumCU;
   for (int64_t w : {(int64_t)8, (int64_t)4, (int64_t)2, (int64_t)1}) {
-    int64_t cand = tuning(24) >= 64 ? tuning(24) / 64 : w;
+    int64_t cand = tuning(GFLA_TUNE_BE_FWD_THREADS) >= 64 ? tuning(GFLA_TUNE_BE_FWD_THREADS) / 64 : w;
     if (cand > 16) cand = 16;
     if (cand > nrg) cand = nrg;
     if (cand < 1) cand = 1;
     if (plane_bytes + cand * tile_stride > budget) {
-      if (tuning(24) >= 64) return g;   // the forced wave count does not fit
+      if (tuning(GFLA_TUNE_BE_FWD_THREADS) >= 64) return g;   // the forced wave count does not fit
       continue;
     }
     int64_t gmax = (budget - cand * tile_stride) / plane_bytes;
@@ -265,7 +265,7 @@ inline WrowGeo wrow_geometry(int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64
     if (G >= 2 || w == 1) break;
   }
   if (waves < 1 || G < 1) return g;
-  if (tuning(4) > 0 && tuning(4) < G) G = tuning(4);
+  if (tuning(GFLA_TUNE_G_CAP) > 0 && tuning(GFLA_TUNE_G_CAP) < G) G = tuning(GFLA_TUNE_G_CAP);
   g.G = (int)G;
   g.ngroups = (int)ceil_div(C, G);
   g.rpw = (int)rpw;
@@ -284,9 +284,9 @@ static int launch_fwd_wrow(const WrowGeo &g, const T *src, const T *flow, T *out
 #define GFLA_WROW_ABL(N_)                                                                                                 \
   launch_lds(be_fwd_wrow_kernel<T, K, N_>, dim3((unsigned)blocks), dim3((unsigned)g.threads), g.lds_bytes, stream, src,    \
              flow, out, (int)C, (int)Hs, (int)Ws, (int)Hf, (int)Wf, g.G, g.ngroups, g.rpw, g.tile_off, g.tile_stride)
-  if (tuning(27) == 1) GFLA_WROW_ABL(1);
-  else if (tuning(27) == 2) GFLA_WROW_ABL(2);
-  else if (tuning(27) == 3) GFLA_WROW_ABL(3);
+  if (tuning(GFLA_TUNE_BE_FWD_PROBE) == 1) GFLA_WROW_ABL(1);
+  else if (tuning(GFLA_TUNE_BE_FWD_PROBE) == 2) GFLA_WROW_ABL(2);
+  else if (tuning(GFLA_TUNE_BE_FWD_PROBE) == 3) GFLA_WROW_ABL(3);
   else
 #undef GFLA_WROW_ABL
 #endif

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void be_fwd_gpix_kernel(const T *__restrict__ 
 
 // channels per wave: as many as keep >= `want` waves in flight (tuning key 33 overrides)
 inline int big_channels_per_wave(int64_t B, int64_t C, int64_t nblk, int ch, int64_t want) {
-  if (tuning(33) > 0) return tuning(33) < C ? tuning(33) : (int)C;
+  if (tuning(GFLA_TUNE_BIG_GATHER_CPW) > 0) return tuning(GFLA_TUNE_BIG_GATHER_CPW) < C ? tuning(GFLA_TUNE_BIG_GATHER_CPW) : (int)C;
   int64_t cpw = C;
   while (cpw > ch && B * nblk * ceil_div(C, cpw) < want) cpw = ceil_div(cpw, 2);
   cpw = ceil_div(cpw, ch) * ch;
@@ -351,9 +351,9 @@ static int launch_fwd_tile(const BigGeo &bg, const T *src, const T *flow, T *out
   launch_lds(be_fwd_tile_kernel<T, K, CH_>, dim3((unsigned)nwg), dim3((unsigned)tg.threads), lds_bytes, stream, src, flow, out, (int)C, \
              (int)Hs, (int)Ws, (int)Hf, (int)Wf, tg.th, tg.tw, tg.ntx, tg.nty, G, (int)ngroups, (int)(lds_bytes / sizeof(A)), nwg)
   if constexpr (sizeof(A) == 4) {   // tuning key 40: channels evaluated together per pixel (registers against requests in flight)
-    if (tuning(40) == 1) GFLA_BE_FWD_TILE(1);
-    else if (tuning(40) == 2) GFLA_BE_FWD_TILE(2);
-    else if (tuning(40) == 4) GFLA_BE_FWD_TILE(4);
+    if (tuning(GFLA_TUNE_BE_FWD_TILE_CHUNK) == 1) GFLA_BE_FWD_TILE(1);
+    else if (tuning(GFLA_TUNE_BE_FWD_TILE_CHUNK) == 2) GFLA_BE_FWD_TILE(2);
+    else if (tuning(GFLA_TUNE_BE_FWD_TILE_CHUNK) == 4) GFLA_BE_FWD_TILE(4);
     else GFLA_BE_FWD_TILE(CH_TILE);
   } else {
     GFLA_BE_FWD_TILE(CH_TILE);
@@ -680,7 +680,7 @@ static int launch_be_bwd_tile(const BigGeo &bg, const T *src, const T *flow, con
 #define GFLA_BE_TILE_LAUNCH(S, F)                                                                                          \
   launch_lds(be_bwd_tile_kernel<T, K, S, F>, grid, blk, lds_bytes, stream, src, flow, gout, gsrc, gflow, (int)C, (int)Hs,  \
              (int)Ws, (int)Hf, (int)Wf, tg.th, tg.tw, tg.ntx, tg.nty, G, (int)ngroups, (int)lds_bytes, nwg, tile_probe_bits(),     \
-             tuning(41) != 1 ? 1 : 0)
+             tuning(GFLA_TUNE_BE_BWD_TILE_NO_FOLD) != 1 ? 1 : 0)
     if (gsrc && gflow) GFLA_BE_TILE_LAUNCH(true, true);
     else if (gsrc) GFLA_BE_TILE_LAUNCH(true, false);
     else GFLA_BE_TILE_LAUNCH(false, true);

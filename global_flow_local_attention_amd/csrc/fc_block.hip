@@ -79,9 +79,9 @@ static FcPlan fc_plan(int64_t B, int C, int H, int W, int k, int mode) {
   P.wgrad = fc_is_wino(mode) || P.wgrad_x32 ? (mode == 5 && k == 5 ? kWgradWino16 : kWgradWino32)
                                             : (P.split ? kWgradDirect16 : kWgradDirect32);
   P.wgrad_both = P.wgrad_x32 ? kWgradWino16 : P.wgrad;
-  P.wgrads_together = tuning(21) != 2;
+  P.wgrads_together = tuning(GFLA_TUNE_WINO_LAUNCH) != 2;
   const FcHalf hs = fc_half(H, W, k, true);
-  P.own_scatter = tuning(46) != 1 && fc_scatter_own_rows(B, hs.Ho, hs.Wo) >= 1;
+  P.own_scatter = tuning(GFLA_TUNE_FC_SCATTER_ATOMICS) != 1 && fc_scatter_own_rows(B, hs.Ho, hs.Wo) >= 1;
   return P;
 }
 

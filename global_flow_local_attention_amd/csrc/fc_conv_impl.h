@@ -246,7 +246,7 @@ inline int fc_conv_tile_pixels(int mb, int Wv, int Wp, int k) {
 inline int pick_conv_tiling(int M, int64_t B, int ntiles_n, int Wv, int Wp, int k, int mode, ConvTiling *tl) {
   const int ns = fc_nsplit(mode), pitch = mode ? 48 : 80;
   const int nb = (int)ceil_div(M, 32);
-  const int forced = tuning(11);
+  const int forced = tuning(GFLA_TUNE_FC_ROW_BLOCKS);
   int64_t T = (2 * kNumCU) / (B * ntiles_n);
   if (T < 1) T = 1;
   if (T > nb) T = nb;

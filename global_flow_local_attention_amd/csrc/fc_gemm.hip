@@ -795,7 +795,7 @@ __global__ __launch_bounds__(512, 4) void fc_wgrad_f32_kernel(PackedDesc X, Pack
 int fc_wgrad_splits(int64_t B, int Mk, int cpad) {
   const int nch = cpad / kFcChunk;
   const int64_t total = B * ceil_div(Mk, kWgKC);
-  int64_t s = tuning(12) > 0 ? tuning(12) : (2 * kNumCU) / nch;
+  int64_t s = tuning(GFLA_TUNE_FC_WGRAD_SPLITS) > 0 ? tuning(GFLA_TUNE_FC_WGRAD_SPLITS) : (2 * kNumCU) / nch;
   if (s < 1) s = 1;
   return (int)(s > total ? total : s);
 }

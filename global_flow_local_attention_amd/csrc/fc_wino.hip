@@ -336,7 +336,7 @@ static int wn_launch(const WnConvJob *jobs, int njobs, int64_t B, int nch, hipSt
   if (!L.db) GFLA_WINO_LAUNCH(0, false)
 #ifdef GFLA_PROBES  // `make PROBES=1`: timing ablations of the k = 5 kernel (tuning key 20; their results are garbage, so
                     // a default build does not contain them and a stray key 20 cannot corrupt a forward / backward)
-  switch (K_ == 5 ? tuning(20) : 0) {
+  switch (K_ == 5 ? tuning(GFLA_TUNE_WINO_PROBE) : 0) {
     case 1: GFLA_WINO_LAUNCH(1, true)
     case 2: GFLA_WINO_LAUNCH(2, true)
     case 4: GFLA_WINO_LAUNCH(4, true)
@@ -358,7 +358,7 @@ int fc_wino_conv_jobs(const WnConvJob *jobs, int njobs, int64_t B, int nch, int 
   if (njobs > 2) return GFLA_ERR_UNSUPPORTED;
   for (int j = 0; j < njobs; ++j)
     if (!fc_wino_fits(jobs[j].M, jobs[j].Wv, jobs[j].Wp, k)) return GFLA_ERR_UNSUPPORTED;
-  if (njobs == 2 && tuning(21) == 2) {
+  if (njobs == 2 && tuning(GFLA_TUNE_WINO_LAUNCH) == 2) {
     const int st = fc_wino_conv_jobs(jobs, 1, B, nch, k, stream);
     return st != GFLA_OK ? st : fc_wino_conv_jobs(jobs + 1, 1, B, nch, k, stream);
   }
@@ -566,9 +566,9 @@ WwGeo ww_geometry(int Ho, int Wo, int k) {
   // within kWwRawMax bytes and the staging registers of the instantiation.  Tuning key 29: 1 = one row per unit (round 3),
   // 2 = at most 16 tiles per unit.
   g.R = 1;
-  if (g.nseg == 1 && tuning(29) != 1) {
+  if (g.nseg == 1 && tuning(GFLA_TUNE_WINO_WGRAD_UNITS) != 1) {
     const int pfm = (k == 5 ? 4 : 5) * kWnThreads;
-    const int cap = tuning(29) == 2 ? 16 : 1 << 20;
+    const int cap = tuning(GFLA_TUNE_WINO_WGRAD_UNITS) == 2 ? 16 : 1 << 20;
     auto steps = [&](int R) { return (g.TH / R) * ((R * g.TW + 15) / 16) + (g.TH % R ? ((g.TH % R) * g.TW + 15) / 16 : 0); };
     int best = 1, best_steps = steps(1);
     for (int R = 2; R <= g.TH && R * g.TW <= cap; ++R) {
@@ -586,7 +586,7 @@ int fc_wino_wgrad_splits(int64_t B, int Ho, int Wo, int cpad, int k) {
   const WwGeo g = ww_geometry(Ho, Wo, k);
   const int64_t units = B * g.ups;
   // 8 waves per workgroup, two per SIMD: ONE workgroup per CU; one round of 256 workgroups
-  int64_t s = tuning(12) > 0 ? tuning(12) : kNumCU / (cpad / kFcChunk);
+  int64_t s = tuning(GFLA_TUNE_FC_WGRAD_SPLITS) > 0 ? tuning(GFLA_TUNE_FC_WGRAD_SPLITS) : kNumCU / (cpad / kFcChunk);
   if (s < 1) s = 1;
   return (int)(s > units ? units : s);
 }
@@ -598,7 +598,7 @@ int fc_wino_wgrad_jobs(const WwJob *jobs, int njobs, int cpad, int64_t B, int k,
   return ww_launch(jobs, njobs, cpad, B, k, kWwPitch, v_bytes, fc_wino_wgrad_kernel<K_, D_, false>, fc_wino_wgrad_kernel<K_, D_, true>, stream);
   if (k != 5) GFLA_WW(3, 0)
 #ifdef GFLA_PROBES  // timing ablations (tuning key 20 = 32 + bits; results are garbage): `make PROBES=1` builds only
-  switch (tuning(20) >= 32 ? tuning(20) - 32 : 0) {
+  switch (tuning(GFLA_TUNE_WINO_PROBE) >= 32 ? tuning(GFLA_TUNE_WINO_PROBE) - 32 : 0) {
     case 1: GFLA_WW(5, 1)
     case 2: GFLA_WW(5, 2)
     case 4: GFLA_WW(5, 4)

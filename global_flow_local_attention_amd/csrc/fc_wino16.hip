@@ -329,7 +329,7 @@ int fc_wino16_conv_jobs(const WnConvJob *jobs, int njobs, const uint32_t *const 
   if (njobs > 2 || !amax_w || k != 3) return GFLA_ERR_UNSUPPORTED;   // (k = 5 runs on the direct kernels: fc_block.hip)
   for (int j = 0; j < njobs; ++j)
     if (!amax_x[j] || !fc_wino16_fits(jobs[j].M, jobs[j].Wv, jobs[j].Wp, k)) return GFLA_ERR_UNSUPPORTED;
-  if (njobs == 2 && tuning(21) == 2) {
+  if (njobs == 2 && tuning(GFLA_TUNE_WINO_LAUNCH) == 2) {
     const int st = fc_wino16_conv_jobs(jobs, 1, amax_x, B, nch, k, amax_w, stream);
     return st != GFLA_OK ? st : fc_wino16_conv_jobs(jobs + 1, 1, amax_x + 1, B, nch, k, amax_w, stream);
   }
@@ -543,7 +543,7 @@ int fc_wino16_wgrad_jobs(const WwJob *jobs, int njobs, int cpad, int64_t B, int 
     if (!amax_x[j] || !amax_z[j]) return GFLA_ERR_UNSUPPORTED;
   auto single = fc_wino16_wgrad_kernel<false>, multi = fc_wino16_wgrad_kernel<true>;
 #ifdef GFLA_PROBES
-  switch (tuning(20) >= 64 ? tuning(20) - 64 : 0) {
+  switch (tuning(GFLA_TUNE_WINO_PROBE) >= 64 ? tuning(GFLA_TUNE_WINO_PROBE) - 64 : 0) {
     case 1: single = multi = fc_wino16_wgrad_kernel<true, 1>; break;
     case 2: single = multi = fc_wino16_wgrad_kernel<true, 2>; break;
     case 3: single = multi = fc_wino16_wgrad_kernel<true, 3>; break;

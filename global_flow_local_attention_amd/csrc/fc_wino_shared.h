@@ -147,7 +147,7 @@ inline WnGeo wn_geometry(int M, int Wv, int Wp) {
   // to the V buffers (610 -> 534 pixels at 32x22: 161.5 KB -> 151 KB; the single-buffer staging costs a barrier and an exposed
   // copy per chunk).  Taken when it wastes at most 4 slots and does not add a group.  Tuning key 44 = 1: always 32.
   const int whole = g.TW < kWnTiles ? (kWnTiles / g.TW) * g.TW : kWnTiles;
-  if (whole != kWnTiles && whole >= kWnTiles - 4 && (ntiles + whole - 1) / whole == g.ngroups && tuning(44) != 1) {
+  if (whole != kWnTiles && whole >= kWnTiles - 4 && (ntiles + whole - 1) / whole == g.ngroups && tuning(GFLA_TUNE_WINO_GROUP_32) != 1) {
     const int sp = wn_span<KS>(g, whole, Wp);
     if (sp < g.span) g.tpg = whole, g.span = sp;
   }
@@ -349,7 +349,7 @@ struct WnLaunch {
 template <int KS>
 inline int wn_plan(const WnConvJob *jobs, int njobs, const uint32_t *const *amax_x, int64_t B, unsigned exchange, WnLaunch &L) {
   int64_t wgs[2] = {0, 0};
-  L.db = tuning(21) != 1;
+  L.db = tuning(GFLA_TUNE_WINO_LAUNCH) != 1;
   L.lds = 0;
   for (int j = 0; j < njobs; ++j)
     L.db = L.db && wn_lds_bytes<KS>(wn_geometry<KS>(jobs[j].M, jobs[j].Wv, jobs[j].Wp), true, exchange) <= kWnLdsLimit;

@@ -58,7 +58,7 @@ inline int big_plane_bytes(int op, int acc_size) {
 // per CU out of batch x channel groups), each beyond the LDS budget.  tuning key 30: 1 = never (round 1's windowed kernels),
 // 2 = always (tests drive the kernels at small shapes).  The routes below and out[0] of gfla_big_plane_geometry ask here.
 inline bool big_plane_regime(int op, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int acc_size) {
-  const int t = tuning(30);
+  const int t = tuning(GFLA_TUNE_BIG_PLANE);
   if (t == 1) return false;
   if (t == 2) return true;
   return Hs * Ws * (int64_t)big_plane_bytes(op, acc_size) > lds_budget() && B * C < 4 * kNumCU;
@@ -79,11 +79,11 @@ inline bool scatter_gather_planes_fit(int64_t Hs, int64_t Ws, int acc_size) {
 }
 // Policy, not correctness.  Tuning keys 3 and 8 = 1 switch the aggregation stream kernels off (round 1's kernels: the tests'
 // reference).
-inline bool agg_stream_enabled() { return tuning(3) != 1 && tuning(8) != 1; }
+inline bool agg_stream_enabled() { return tuning(GFLA_TUNE_AGG) != 1 && tuning(GFLA_TUNE_AGG_STREAM) != 1; }
 // The aggregation takes them from k = 5: k = 3 has 16 patch words per output instead of 36, and there the per-group setup
 // of agg_fwd_lds_kernel costs less than the extra coefficient pass (23 us against 20 + 5 at the bench shape); key 8 = 2
 // forces them for every odd k.  (resample2d's d/d input2 has no such break-even: agg_stream_enabled() alone.)
-inline bool agg_stream_wanted(int k) { return agg_stream_enabled() && (k >= 5 || tuning(8) == 2); }
+inline bool agg_stream_wanted(int k) { return agg_stream_enabled() && (k >= 5 || tuning(GFLA_TUNE_AGG_STREAM) == 2); }
 
 // ---- geometry of the planes-in-LDS launchers -----------------------------------------------------------------------------
 // Either the whole plane (plane_geometry) or a row window (band_geometry; tuning key 7 = 1: never).
@@ -91,7 +91,7 @@ inline PlaneGeo lds_geometry(int64_t H, int64_t W, int bytes_per_elem, int64_t B
                              int64_t items_per_row, int k_span, int chunk = 0) {
   PlaneGeo g = plane_geometry(H * W, bytes_per_elem, B, C, Hf * items_per_row, true, chunk);
   if (g.G > 0) return g;
-  if (tuning(7) == 1) return g;  // windows disabled
+  if (tuning(GFLA_TUNE_NO_WINDOWS) == 1) return g;  // windows disabled
   return band_geometry(H, W, bytes_per_elem, B, C, Hf, items_per_row, k_span);
 }
 // acc_size = sizeof(Num<T>::acc), elem_size = sizeof(T).  Unfold forward: whole gather planes only.
@@ -127,7 +127,8 @@ struct Geo {
 inline Geo chunk_geometry(int64_t B, int64_t C, int64_t items, int max_cpt, int64_t want_waves) {
   Geo g;
   g.sp_blocks = (int)ceil_div(items, kBlock);
-  int cpt = tuning(1) > 0 ? tuning(1) : pick_channels_per_thread((int64_t)g.sp_blocks * kBlock, C, B, max_cpt, want_waves);
+  int cpt = tuning(GFLA_TUNE_GLOBAL_CPT) > 0 ? tuning(GFLA_TUNE_GLOBAL_CPT)
+                                             : pick_channels_per_thread((int64_t)g.sp_blocks * kBlock, C, B, max_cpt, want_waves);
   if (cpt > C) cpt = (int)C;
   g.cpt = cpt;
   g.ncg = (int)ceil_div(C, cpt);
@@ -145,7 +146,7 @@ struct BigGatherGeo {
 inline BigGatherGeo big_gather_geometry(int64_t B, int64_t C, int64_t H, int64_t W) {
   const int64_t nsp = ceil_div(H * W, kBlock), want = 20 * kNumCU;
   int64_t cpt = C;
-  if (tuning(33) > 0) cpt = tuning(33) < C ? tuning(33) : C;
+  if (tuning(GFLA_TUNE_BIG_GATHER_CPW) > 0) cpt = tuning(GFLA_TUNE_BIG_GATHER_CPW) < C ? tuning(GFLA_TUNE_BIG_GATHER_CPW) : C;
   else while (cpt > 1 && B * nsp * (kBlock / 64) * ceil_div(C, cpt) < want) cpt = ceil_div(cpt, 2);
   const int64_t ncg = ceil_div(C, cpt);
   return BigGatherGeo{(int)cpt, (int)ncg, (int)nsp, B * nsp * ncg};
@@ -169,10 +170,10 @@ struct BeFwdRoute {
 inline BeFwdRoute be_fwd_route(int elem_size, int acc_size, int V, int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t Hf,
                                int64_t Wf, int k) {
   BeFwdRoute r{};
-  const int variant = tuning(0);
+  const int variant = tuning(GFLA_TUNE_BE_FWD);
   if (elem_size >= 4 && k >= 2 && k <= 5) {
     if (variant == 0 && big_plane_regime(0, B, C, Hs, Ws, acc_size) && Hs * Ws <= 0x3fffffffLL) {
-      if (tuning(38) == 1) {
+      if (tuning(GFLA_TUNE_BIG_GATHER_V1) == 1) {
         r.gpix = be_gpix_geometry(B, C, Hf, Wf, k, acc_size);
         if (grid_ok(r.gpix.nwg)) return r.path = BeFwdPath::kGpix, r;
       } else {
@@ -215,11 +216,11 @@ inline BeBwdRoute be_bwd_fixed_k_route(int elem_size, int acc_size, bool need_sr
                                        int64_t Hs, int64_t Ws, int64_t Hf, int64_t Wf, int k) {
   BeBwdRoute r{};
   const bool half = elem_size == 2;
-  if (tuning(2) != 1 && !half && big_plane_regime(1, B, C, Hs, Ws, acc_size)) {
+  if (tuning(GFLA_TUNE_BE_BWD) != 1 && !half && big_plane_regime(1, B, C, Hs, Ws, acc_size)) {
     r.big = big_geometry(1, B, C, Hf, Wf, k + 1, wanted_plane_bytes(need_src, need_flow, acc_size));
     if (Hs * Ws <= 0x3fffffffLL && grid_ok((int64_t)k * Hf * k * Wf) && grid_ok(r.big.nwg)) return r.path = BeBwdPath::kTile, r;
   }
-  if (tuning(2) != 1 || half) {
+  if (tuning(GFLA_TUNE_BE_BWD) != 1 || half) {
     r.lds = be_bwd_lds_geometry(kGoutTensor, elem_size, acc_size, need_src, need_flow, B, C, Hs, Ws, Hf, Wf, k);
     if (r.lds.G > 0) return r.path = grid_ok(plane_blocks(B, r.lds)) ? BeBwdPath::kLds : BeBwdPath::kUnsupported, r;
   }
@@ -263,9 +264,9 @@ struct RsFwdRoute {
 inline RsFwdRoute rs_fwd_route(int elem_size, int acc_size, int64_t B, int64_t C, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
                                int k, int dil) {
   RsFwdRoute r{};
-  if (tuning(6) != 1) {
+  if (tuning(GFLA_TUNE_RS) != 1) {
     if (big_plane_regime(2, B, C, Hi, Wi, acc_size)) {
-      if (tuning(38) != 1 && elem_size >= 4 && Hi * Wi <= 0x3fffffffLL) {
+      if (tuning(GFLA_TUNE_BIG_GATHER_V1) != 1 && elem_size >= 4 && Hi * Wi <= 0x3fffffffLL) {
         r.big = big_geometry(2, B, C, H, W, (k - 1) * dil + 1, acc_size);
         if (grid_ok(r.big.nwg)) return r.path = RsFwdPath::kBigTile, r;
       }
@@ -307,15 +308,15 @@ inline RsBwdRoute rs_bwd_route(int elem_size, int acc_size, int64_t B, int64_t C
   RsBwdRoute r{};
   const bool half = elem_size == 2, f32 = elem_size == 4, float_acc = acc_size == 4;
   const int span = (k - 1) * dil + 1;
-  const bool big = !half && tuning(6) != 1 && big_plane_regime(3, B, C, Hi, Wi, acc_size);
+  const bool big = !half && tuning(GFLA_TUNE_RS) != 1 && big_plane_regime(3, B, C, Hi, Wi, acc_size);
   r.lds1 = rs_scatter_geometry(elem_size, B, C, Hi, Wi, H, W, k, dil);
   r.lds2 = rs_gather_geometry(acc_size, B, C, Hi, Wi, H, W, k, dil, 0);
-  const bool lds = (tuning(6) != 1 || half) && r.lds1.G > 0 && r.lds2.G > 0;
-  r.product = product_allowed && f32 && want1 && workspace && dil == 1 && tuning(6) != 1 && !big;
+  const bool lds = (tuning(GFLA_TUNE_RS) != 1 || half) && r.lds1.G > 0 && r.lds2.G > 0;
+  r.product = product_allowed && f32 && want1 && workspace && dil == 1 && tuning(GFLA_TUNE_RS) != 1 && !big;
   r.lds_fallback = r.product && lds;  // adaptive only where the LDS-atomic kernel exists as the device-side fallback
   if (big && Hi * Wi <= 0x3fffffffLL) {
     r.path = RsBwdPath::kBig;
-    r.gather_tiles = tuning(38) != 1;
+    r.gather_tiles = tuning(GFLA_TUNE_BIG_GATHER_V1) != 1;
     r.big1 = big_geometry(3, B, C, H, W, span, big_plane_bytes(3, acc_size));
     r.big2 = big_geometry(4, B, C, H, W, span, acc_size);
     r.gather = big_gather_geometry(B, C, H, W);
@@ -323,11 +324,11 @@ inline RsBwdRoute rs_bwd_route(int elem_size, int acc_size, int64_t B, int64_t C
       r.path = RsBwdPath::kUnsupported;
   } else if (lds) {
     r.path = RsBwdPath::kLds;
-    r.fix = float_acc && !(f32 && tuning(23) == 1);
-    r.tab = f32 && workspace && k / 2 == 2 && Hi <= 65535 && Wi <= 65535 && tuning(23) == 0;
+    r.fix = float_acc && !(f32 && tuning(GFLA_TUNE_RS_BWD1_PLANES) == 1);
+    r.tab = f32 && workspace && k / 2 == 2 && Hi <= 65535 && Wi <= 65535 && tuning(GFLA_TUNE_RS_BWD1_PLANES) == 0;
     // B C H W < 2^31: a bound the streaming route has always had (the kernel indexes the flow map in 64 bits; dropping it
     // would move calls onto another kernel)
-    r.stream = float_acc && k == 4 && dil == 1 && tuning(22) != 1 && agg_stream_enabled() &&
+    r.stream = float_acc && k == 4 && dil == 1 && tuning(GFLA_TUNE_RS_BWD2_NO_STREAM) != 1 && agg_stream_enabled() &&
                agg_stream_shape_ok(B, C, Hi, Wi, 3, true) && B * C * H * W < (1LL << 31) &&
                agg_stream_plan(B, C, Hi, Wi, H, W, 3, r.plan);
     if ((want1 && !grid_ok(plane_blocks(B, r.lds1))) || (want2 && !r.stream && !grid_ok(plane_blocks(B, r.lds2))))
@@ -358,7 +359,7 @@ inline AggFwdRoute agg_fwd_route(int acc_size, bool workspace, int64_t B, int64_
   if (acc_size == 4 && workspace && agg_stream_wanted(k) && agg_stream_shape_ok(B, C, Hs, Ws, k, true) &&
       agg_stream_plan(B, C, Hs, Ws, H, W, k, r.plan))
     return r.path = AggFwdPath::kStream, r;
-  if (tuning(3) != 1) {
+  if (tuning(GFLA_TUNE_AGG) != 1) {
     r.lds = plane_geometry(Hs * Ws, acc_size, B, C, H * W, true, kAggChunk);
     if (r.lds.G > 0) return r.path = grid_ok(plane_blocks(B, r.lds)) ? AggFwdPath::kLds : AggFwdPath::kUnsupported, r;
   }
@@ -416,11 +417,11 @@ inline AggBwdRoute agg_bwd_route(int elem_size, int acc_size, bool need_src, boo
                                  int64_t B, int64_t C, int64_t Hs, int64_t Ws, int64_t H, int64_t W, int k) {
   AggBwdRoute r{};
   const bool half = elem_size == 2, fit = scatter_gather_planes_fit(Hs, Ws, acc_size);
-  r.product = elem_size == 4 && need_src && workspace && tuning(3) != 1 &&
+  r.product = elem_size == 4 && need_src && workspace && tuning(GFLA_TUNE_AGG) != 1 &&
               (Hs * Ws * (int64_t)acc_size <= lds_budget() || (!need_flow && !need_logits));
   r.lds_fallback = r.product && fit;
   if (r.lds_fallback) r.fallback = whole_plane_bwd_route(kGoutAttn, elem_size, acc_size, true, false, B, C, Hs, Ws, H, W, k);
-  if ((tuning(3) != 1 || half) && fit) {
+  if ((tuning(GFLA_TUNE_AGG) != 1 || half) && fit) {
     r.path = AggBwdPath::kLds;
     if (need_src || need_flow) {
       r.scatter = whole_plane_bwd_route(kGoutAttn, elem_size, acc_size, need_src, need_flow, B, C, Hs, Ws, H, W, k);

@@ -19,7 +19,7 @@ namespace gfla {
 constexpr int kLdsBudgetDefault = 64 * 1024;  // per workgroup: two workgroups of 512 threads per CU
 // tuning key 10 (KB) overrides it; more than 64 KB needs the kernel attribute raised (launch_lds below)
 inline int64_t lds_budget() {
-  const int kb = tuning(10);
+  const int kb = tuning(GFLA_TUNE_LDS_KB);
   return kb >= 16 && kb <= 160 ? (int64_t)kb * 1024 : kLdsBudgetDefault;
 }
 #define kLdsBudget (::gfla::lds_budget())
@@ -81,8 +81,8 @@ inline PlaneGeo plane_geometry(int64_t plane_elems, int bytes_per_elem, int64_t 
   if (per_channel > kLdsBudget) return g;
   int64_t G = kLdsBudget / per_channel;
   if (G > C) G = C;
-  if (tuning(4) > 0) {
-    if (tuning(4) < G) G = tuning(4);
+  if (tuning(GFLA_TUNE_G_CAP) > 0) {
+    if (tuning(GFLA_TUNE_G_CAP) < G) G = tuning(GFLA_TUNE_G_CAP);
   } else if (chunk > 0) {
     int64_t best = G, best_cost = -1;
     for (int64_t cand = G; cand >= 1; --cand) {
@@ -107,7 +107,7 @@ inline PlaneGeo plane_geometry(int64_t plane_elems, int bytes_per_elem, int64_t 
   }
   // key 5 forces a split only where the kernel can flush a shared plane (atomics); a caller that cannot split (16-bit
   // storage: one owner per plane, plain read-modify-write) keeps split = 1 whatever the key says
-  if (allow_split && tuning(5) > 0) split = tuning(5);
+  if (allow_split && tuning(GFLA_TUNE_SPLIT) > 0) split = tuning(GFLA_TUNE_SPLIT);
   g.split = split;
   g.per = (int)ceil_div(work_items, split);
   g.lds_bytes = (unsigned)(G * per_channel);

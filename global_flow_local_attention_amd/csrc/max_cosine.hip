@@ -313,8 +313,8 @@ static int max_cosine(const float *source, const float *target, void *workspace,
   // several units per workgroup slot (2 per CU) so that the tail of the launch is short
   int64_t splitM = 1;
   const int64_t slots = 2 * kNumCU;
-  if (tuning(5) > 0)
-    splitM = tuning(5);
+  if (tuning(GFLA_TUNE_SPLIT) > 0)
+    splitM = tuning(GFLA_TUNE_SPLIT);
   else
     splitM = ceil_div(8 * slots, B * tilesN);  // workgroups start as slots free up: many short units pack best
   if (splitM > nM) splitM = nM;
@@ -618,7 +618,7 @@ static int max_cosine16(const uint16_t *source, const uint16_t *target, void *wo
   const int64_t tilesN = ceil_div(Nt, TN), nM = ceil_div(Ns, kTM16);
   // one workgroup per CU while the target tile fills the LDS: several units per slot keep the tail of the launch short,
   // few enough that the one-off load of the resident tile stays small beside the source tiles streamed past it
-  int64_t splitM = tuning(5) > 0 ? tuning(5) : ceil_div(4 * (int64_t)kNumCU, B * tilesN);
+  int64_t splitM = tuning(GFLA_TUNE_SPLIT) > 0 ? tuning(GFLA_TUNE_SPLIT) : ceil_div(4 * (int64_t)kNumCU, B * tilesN);
   if (splitM > nM) splitM = nM;
   if (splitM < 1) splitM = 1;
   const int64_t total = B * tilesN * splitM;

@@ -586,10 +586,10 @@ struct PmGeo {
 };
 static PmGeo pm_geometry(int64_t B, int64_t C, int Hs, int Ws, int W, int patch) {
   (void)B, (void)C, (void)W, (void)patch;
-  int R = tuning(13) > 0 ? tuning(13) : 96 / Ws;
+  int R = tuning(GFLA_TUNE_PM_BAND_ROWS) > 0 ? tuning(GFLA_TUNE_PM_BAND_ROWS) : 96 / Ws;
   // planes wider than 48: one row would be a band of two blocks -- too little work per tile pass, and no skipping of its zero
   // slices; up to six blocks instead (aggregation backward at 64x64: 501 us with one row per band, 428 with two, 415 with three)
-  if (tuning(13) <= 0 && R < 2) R = (kPmMaxNB * 32) / Ws;
+  if (tuning(GFLA_TUNE_PM_BAND_ROWS) <= 0 && R < 2) R = (kPmMaxNB * 32) / Ws;
   if (R < 1) R = 1;
   if (R > Hs) R = Hs;
   while (R > 1 && R * Ws > kPmMaxNB * 32) --R;
@@ -599,7 +599,7 @@ static PmGeo pm_geometry(int64_t B, int64_t C, int Hs, int Ws, int W, int patch)
 
 // tuning key 14: 0 = where it measured faster (pm_auto), 1 = never, 2 = wherever the shape is supported
 static bool pm_auto(bool aggregate, int64_t Ws) {
-  if (tuning(14) == 2) return true;
+  if (tuning(GFLA_TUNE_PM) == 2) return true;
   // bench shapes, smooth / coherent flows, with the all-zero K slices skipped (profiles/r4_scatter_paths_after_zero_skip.jsonl,
   // r4_scatter_paths_mfma_everywhere.jsonl): aggregation 64x44 376 -> 153 us, 32x22 95 -> 69 (round 3, without the skipping:
   // 90..100, and the LDS-atomic kernel was kept there); resample2d 32x22 138 -> 91, 64x44 210 (LDS planes fed from tap
@@ -614,7 +614,7 @@ static int64_t pm_lds_bytes(int NB, int64_t ntiles) {
 
 static bool pm_supported(int64_t B, int64_t C, int64_t H, int64_t W, int64_t Hs, int64_t Ws) {
   if (!(B > 0 && B <= 65535 && C > 0 && Hs >= 2 && Ws >= 2 && Ws <= kPmMaxNB * 32 && Hs < 32768 && Ws < 32768 &&
-        H * W <= (int64_t)kPmTile * 65535 && ceil_div(C, kPmChannels) <= 65535 && tuning(14) != 1))
+        H * W <= (int64_t)kPmTile * 65535 && ceil_div(C, kPmChannels) <= 65535 && tuning(GFLA_TUNE_PM) != 1))
     return false;
   // the per-tile row table lives in LDS: a flow field with more tiles than fit the 64 KB launch limit is UNSUPPORTED
   // here (the callers fall back to the LDS-atomic kernels) instead of failing at launch
@@ -657,9 +657,9 @@ static int pm_scatter(const float *G, float *dS, const PatchEntry *table, const 
 // limit_rows (tuning key 15, in rows per tile; 0 = default 2.6 x the rows a tile reaches under a constant flow;
 // >= 100000 = always the matrix-core path).
 static unsigned pm_limit(int64_t B, int64_t ntiles, int W, int patch, bool adaptive) {
-  if (!adaptive || tuning(15) >= 100000) return 0xffffffffu;
+  if (!adaptive || tuning(GFLA_TUNE_PM_LIMIT_ROWS) >= 100000) return 0xffffffffu;
   const double still = (double)kPmTile / W + 1.0 + patch;  // rows reached with a constant flow
-  const double per_tile = tuning(15) > 0 ? (double)tuning(15) : 2.6 * still;
+  const double per_tile = tuning(GFLA_TUNE_PM_LIMIT_ROWS) > 0 ? (double)tuning(GFLA_TUNE_PM_LIMIT_ROWS) : 2.6 * still;
   const double total = per_tile * (double)B * (double)ntiles;
   return total >= 4.0e9 ? 0xffffffffu : (unsigned)total;
 }

@@ -188,7 +188,7 @@ inline unsigned tile_lds_request(int th, int tw, int span, int G, int bytes_per_
 // default build ignores the key -- no user-reachable path that computes wrong results.
 inline int tile_probe_bits() {
 #ifdef GFLA_PROBES
-  return tuning(39);
+  return tuning(GFLA_TUNE_TILE_PROBE);
 #else
   return 0;
 #endif
@@ -200,13 +200,13 @@ struct TileGeo {
 };
 inline TileGeo tile_geometry(int64_t H, int64_t W, int dflt_th = 16, int dflt_tw = 32) {
   TileGeo g;
-  int tw = tuning(32) > 0 ? tuning(32) : dflt_tw;
+  int tw = tuning(GFLA_TUNE_TILE_COLS) > 0 ? tuning(GFLA_TUNE_TILE_COLS) : dflt_tw;
   if (tw > W) tw = (int)W;
   if (tw > 512) tw = 512;
   // NOT split evenly (176 -> 6 tiles of 30): tiles of 32 columns start on 128-byte lines of every per-pixel tensor, and what a
   // wave writes per row is then a whole line, not the tail of one and the head of the next (5 tiles of 32 and one of 16)
   const int ntx = (int)ceil_div(W, tw);
-  int th = tuning(31) > 0 ? tuning(31) : dflt_th;
+  int th = tuning(GFLA_TUNE_TILE_ROWS) > 0 ? tuning(GFLA_TUNE_TILE_ROWS) : dflt_th;
   if (th * tw > 512) th = 512 / tw;
   if (th > H) th = (int)H;
   if (th < 1) th = 1;
@@ -224,10 +224,10 @@ inline TileGeo tile_geometry(int64_t H, int64_t W, int dflt_th = 16, int dflt_tw
 // (profiles/r5_config2_sweeps.txt).  tuning keys 35 / 36.
 inline TileGeo row_tile_geometry(int64_t H, int64_t W) {
   TileGeo g;
-  int tw = tuning(36) > 0 ? tuning(36) : 32;
+  int tw = tuning(GFLA_TUNE_BE_FWD_TILE_COLS) > 0 ? tuning(GFLA_TUNE_BE_FWD_TILE_COLS) : 32;
   if (tw > W) tw = (int)W;
   const int ntx = (int)ceil_div(W, tw);
-  int th = tuning(35) > 0 ? tuning(35) : 8;
+  int th = tuning(GFLA_TUNE_BE_FWD_TILE_ROWS) > 0 ? tuning(GFLA_TUNE_BE_FWD_TILE_ROWS) : 8;
   if (th * tw > 512) th = 512 / tw;
   if (th > H) th = (int)H;
   if (th < 1) th = 1;
@@ -241,7 +241,7 @@ inline TileGeo row_tile_geometry(int64_t H, int64_t W) {
 
 // channels per workgroup of a tile kernel: `dflt` (tuning key `key` overrides) unless that leaves the launch under three
 // workgroups per CU
-inline int tile_channels(int key, int dflt, int64_t tiles, int64_t C) {
+inline int tile_channels(gfla_tuning_key key, int dflt, int64_t tiles, int64_t C) {
   int G = tuning(key) > 0 ? tuning(key) : dflt;
   if (tuning(key) <= 0)
     while (G > 1 && tiles * ceil_div(C, G) < 3 * kNumCU) G /= 2;
@@ -268,8 +268,10 @@ inline BigGeo big_geometry(int op, int64_t B, int64_t C, int64_t H, int64_t W, i
   const int64_t tiles = B * g.tg.nty * g.tg.ntx;
   // (block_extractor's backward at k >= 5 -- span 6: windows of ~13 KB per channel -- measured 168 -> 153 us with 4 channels
   // per workgroup instead of 8: twice the workgroups, each with one channel round instead of two; profiles/r5_config2_sweeps.txt)
-  g.G = op == 0 ? tile_channels(37, 8, tiles, C) : op == 2 ? tile_channels(37, 8, tiles, C) : op == 4 ? tile_channels(37, 16, tiles, C)
-                                                            : tile_channels(34, op == 1 && span >= 6 ? 4 : 8, tiles, C);
+  g.G = op == 0   ? tile_channels(GFLA_TUNE_GATHER_TILE_CHANNELS, 8, tiles, C)
+        : op == 2 ? tile_channels(GFLA_TUNE_GATHER_TILE_CHANNELS, 8, tiles, C)
+        : op == 4 ? tile_channels(GFLA_TUNE_GATHER_TILE_CHANNELS, 16, tiles, C)
+                  : tile_channels(GFLA_TUNE_SCATTER_TILE_CHANNELS, op == 1 && span >= 6 ? 4 : 8, tiles, C);
   g.ngroups = (int)ceil_div(C, g.G);
   g.nwg = tiles * g.ngroups;
   g.lds_bytes = tile_lds_request(g.tg.th, g.tg.tw, span, g.G, bytes_per_elem, lds_budget());

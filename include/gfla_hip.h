@@ -61,7 +61,7 @@ typedef void *gfla_stream_t; /* hipStream_t */
  *   1: round 1 (the three ops + aggregate)   2: round 2 (fc_*, *_ws, bf16 backward, max_cosine, correctness_map)
  *   3: round 3 (gfla_path_count, process-global tuning, arithmetic mode 4)
  *   4: round 3 (gfla_fc_kernel_f32 which = 6 / 7; the scatter workspace also carries resample2d's tap records)
- *   5: round 4 (gfla_aggregate_bwd_supported, gfla_mask_blend_*; tuning keys 24-27; path id GFLA_PATH_BE_FWD_PIX)
+ *   5: round 4 (gfla_aggregate_bwd_supported, gfla_mask_blend_*; tuning keys 24, 25 and 27; path id GFLA_PATH_BE_FWD_PIX)
  *   6: round 4 (gfla_convert_multi)
  *   7: round 5 (path ids 13-17, tuning keys 30-41: the big-plane kernels of csrc/tile_map.h; gfla_big_plane_geometry,
  *      gfla_xcd_swizzle)
@@ -74,47 +74,154 @@ typedef void *gfla_stream_t; /* hipStream_t */
 int gfla_abi_version(void);
 const char *gfla_status_string(int status);
 
-/* Tuning knobs (benchmarks/tests only; defaults are chosen per shape).  Returns the old value.
- *   key 0: block_extractor forward   0 auto (planes in LDS when they fit: flow rows of up to 64 pixels -> the
- *          wave-per-flow-row kernel, csrc/be_fwd_wrow.h; wider -> the lane-per-pixel kernel, csrc/be_fwd_pix.h),
- *          1 force the global-gather kernel, 2 force round 1's planes-in-LDS kernel (lane = four consecutive outputs),
- *          3 force the lane-per-pixel kernel, 4 force the wave-per-flow-row kernel
- *   key 1: channels per thread of the global kernels (0 auto)
- *   key 2: block_extractor backward  0 auto, 1 force global-atomics kernel
- *   key 3: aggregate fwd/bwd         0 auto, 1 force global kernels
- *   key 4: cap on G, the channel planes one workgroup keeps in LDS (0 auto)
- *   key 5: split, workgroups sharing one (b, channel group) (0 auto).  Ignored where a kernel cannot split: the 16-bit
- *          backward kernels flush each plane from one owner (block_extractor / aggregation / unfold backward, resample2d
- *          d/d input1), so they keep split = 1
- *   key 6: resample2d fwd/bwd        0 auto, 1 force global kernels
- *   key 7: row windows for planes larger than the LDS budget   0 on, 1 off (use global kernels)
- *   key 10: LDS budget per workgroup in KB (0 = 64; up to 160)
- *   keys 19, 43, 49, 52: retired -- accepted and ignored.  They selected FC kernels that later rounds measured and replaced
- *           (the direct weight gradient in mode 4; in mode 5 the two-term f16 Winograd kernels for the k = 3 data gradient and
- *           for every convolution, the float32 k = 5 weight gradient).  The FC kernel plan is a function of the call's
- *           shape and mode alone (csrc/fc_block.hip: fc_plan)
- *   key 20: timing ablations of the Winograd kernels -- only in `make PROBES=1` builds (results are garbage;
- *           tools/probe_wino.py); a default build ignores the key
- *   key 21: Winograd convolutions   1 single raw buffer, 2 one launch per half instead of both halves in one (also
- *           separates the two weight-gradient kernels of a layer again)
- *   key 23: resample2d d/d input1 LDS planes   0 fixed point + tap records (with scratch), 1 double planes (round 1)
- *   key 24: be_fwd_pix_kernel / be_fwd_wrow_kernel: threads per workgroup (0 auto; multiples of 64 up to 1024)
- *   key 25: be_fwd_pix_kernel: 1 = non-temporal output stores (A/B only: half the rate)
- *   key 27: (make PROBES=1 builds) timing ablations of the two round-4 block_extractor forward kernels
- *   key 29: Winograd-domain weight gradient: 1 = units of one tile row everywhere (round 3); 0 = whole tile rows per unit
- *           on maps whose tile rows fill at most half a unit (csrc/fc_wino_wgrad.h: MR)
- *   key 30: big-plane kernels (few planes, each beyond the LDS budget: csrc/tile_map.h)   0 auto, 1 never (round 1's
- *           row-window kernels), 2 always (tests drive them at small shapes)
- *   key 31 / 32: rows / columns of a tile (0 auto: 16 x 32)   key 35 / 36: the same for block_extractor's forward (0 auto:
- *           8 x 32)   key 34 / 37: channels per workgroup of the scatter / gather tiles (0 auto: 8 / 8-16)
- *   key 39: timing ablations of the tile kernels -- only in `make PROBES=1` builds (results are garbage); a default build
- *           ignores the key
- *   key 40: channels per pixel chunk of block_extractor's forward tiles (0 auto)
- *   key 41: 1 = block_extractor's backward tiles without the cross-lane fold of the patch rows (csrc/be_tile.h: BeLinks)
- *   key 46: 1 = gfla_fc_backward_f32 scatters the gradient of the convolved source map with global float atomics (round 2)
- *           instead of the owner-computes kernel of round 6 (csrc/fc_sample.hip: fc_scatter_own_kernel)
- *   key 38: 1 = the first version of the gathers (taps read from global memory, no LDS window); key 33 = its channels per wave
- * (the other keys select experiments of individual kernels; see the tuning(...) calls in csrc/)                  */
+/* Tuning knobs (benchmarks / tests only; defaults are chosen per shape).  Process-global.  gfla_set_tuning returns the
+ * old value; a key that is no enumerator is accepted and changes nothing (no kernel reads it; outside 0 .. 63 it is not
+ * even stored and 0 comes back).  Every key defaults to 0.  The kernels read a key by its name (csrc:
+ * tuning(GFLA_TUNE_X)); Python sees TUNE_X and refuses a number that is no enumerator.  Each entry: what it selects, its
+ * values, [who reads it]. */
+enum gfla_tuning_key {
+  /* block_extractor forward kernel.  0 auto (few planes beyond the LDS budget -> the tile kernels, see BIG_PLANE; planes
+   * in LDS when they fit: flow rows of up to 64 pixels -> the wave-per-flow-row kernel, csrc/be_fwd_wrow.h, small output
+   * planes and wider rows -> the lane-per-pixel kernel, csrc/be_fwd_pix.h), 1 force the global-gather kernel, 2 force
+   * round 1's planes-in-LDS kernel (lane = four consecutive outputs), 3 force the lane-per-pixel kernel, 4 force the
+   * wave-per-flow-row kernel.  [gs_route.h: be_fwd_route] */
+  GFLA_TUNE_BE_FWD = 0,
+  /* channels per thread of the global-memory kernels (0 auto).  [gs_route.h: chunk_geometry] */
+  GFLA_TUNE_GLOBAL_CPT = 1,
+  /* block_extractor backward.  0 auto, 1 force the global-atomics kernel (16-bit storage has none and keeps the
+   * planes-in-LDS kernel).  [gs_route.h: be_bwd_fixed_k_route] */
+  GFLA_TUNE_BE_BWD = 2,
+  /* local_attn_aggregate forward / backward.  0 auto, 1 force the global kernels: no stream kernels, no matrix-core
+   * product (16-bit storage keeps the planes-in-LDS backward).  [gs_route.h: agg_stream_enabled, agg_fwd_route,
+   * agg_bwd_route] */
+  GFLA_TUNE_AGG = 3,
+  /* cap on G, the channel planes one workgroup keeps in LDS (0 auto).  [lds_plane.h: plane_geometry -- every
+   * planes-in-LDS kernel; be_fwd_pix.h: pix_geometry; be_fwd_wrow.h: wrow_geometry; agg_stream.h: agg_stream_geometry,
+   * where it caps CH, the planes of one staged chunk] */
+  GFLA_TUNE_G_CAP = 4,
+  /* split (0 auto).  [lds_plane.h: plane_geometry and be_fwd_pix.h: pix_geometry -- workgroups sharing one (b, channel
+   * group); ignored where a kernel cannot split: the 16-bit backward kernels flush each plane from one owner
+   * (block_extractor / aggregation / unfold backward, resample2d d/d input1) and keep split = 1.  max_cosine.hip: splitM,
+   * the units the source positions of one (b, target tile) are cut into.  agg_stream.h: agg_stream_geometry -- ns, the
+   * channel ranges] */
+  GFLA_TUNE_SPLIT = 5,
+  /* resample2d forward / backward.  0 auto, 1 force the global kernels: no tile kernels, no matrix-core product (16-bit
+   * storage keeps the planes-in-LDS backward).  [gs_route.h: rs_fwd_route, rs_bwd_route] */
+  GFLA_TUNE_RS = 6,
+  /* row windows for planes larger than the LDS budget.  0 on, 1 off (the global kernels).  [gs_route.h: lds_geometry] */
+  GFLA_TUNE_NO_WINDOWS = 7,
+  /* aggregation stream kernels (csrc/agg_stream.h).  0 auto (the aggregation from k = 5; resample2d d/d input2 at k = 4),
+   * 1 off (round 1's kernels: the tests' reference), 2 the aggregation takes them for every odd k.  [gs_route.h:
+   * agg_stream_enabled, agg_stream_wanted] */
+  GFLA_TUNE_AGG_STREAM = 8,
+  /* stream kernels: threads per workgroup, 64 per tile (0 auto; multiples of 64 up to 64 x kAggStreamWaves).
+   * [agg_stream.h: agg_stream_geometry] */
+  GFLA_TUNE_AGG_STREAM_THREADS = 9,
+  /* LDS budget per workgroup in KB (0 = 64; 16 .. 160).  [lds_plane.h: lds_budget -- every planes-in-LDS / window / tile
+   * geometry and the big-plane regime.  be_fwd_wrow.h: wrow_geometry keeps its own 78 KB (two workgroups per CU) unless
+   * the key is >= 16, then takes this budget] */
+  GFLA_TUNE_LDS_KB = 10,
+  /* direct FC convolutions: row blocks of 32 output pixels per tile (0 auto; kFcMinRowBlocks .. kFcMaxRowBlocks).
+   * [fc_conv_impl.h: pick_conv_tiling] */
+  GFLA_TUNE_FC_ROW_BLOCKS = 11,
+  /* FC weight gradients: partial sums (workgroups) per input chunk (0 auto).  [fc_gemm.hip: fc_wgrad_splits;
+   * fc_wino.hip: fc_wino_wgrad_splits] */
+  GFLA_TUNE_FC_WGRAD_SPLITS = 12,
+  /* matrix-core scatter: source rows per band (0 auto: 96 / Ws, up to six 32-column blocks for wide planes).
+   * [patch_mfma.hip: pm_geometry] */
+  GFLA_TUNE_PM_BAND_ROWS = 13,
+  /* matrix-core scatter (d/d source of the aggregation, resample2d d/d input1).  0 where it measured faster, 1 never
+   * (the LDS-atomic kernels), 2 wherever the shape is supported.  [patch_mfma.hip: pm_auto, pm_supported] */
+  GFLA_TUNE_PM = 14,
+  /* matrix-core scatter, adaptive dispatch: source rows a flow tile may reach on average before the LDS-atomic fallback
+   * takes over (0 = 2.6 x the rows reached under a constant flow; >= 100000 = always the matrix-core path).
+   * [patch_mfma.hip: pm_limit] */
+  GFLA_TUNE_PM_LIMIT_ROWS = 15,
+  /* stream kernels: tile width 8, 16 or 32 (anything else: the width that wastes the fewest lanes).  [agg_stream.h:
+   * agg_stream_geometry] */
+  GFLA_TUNE_AGG_STREAM_TILE_W = 16,
+  /* stream kernels, experiment: pitch of a staged row pair in words (a multiple of 4, >= 2 Ws; anything else: auto).
+   * [agg_stream.h: agg_stream_geometry] */
+  GFLA_TUNE_AGG_STREAM_PITCH = 17,
+  /* Retired -- accepted and ignored.  Keys 19, 43, 49 and 52 selected FC kernels that later rounds measured and
+   * replaced (the direct weight gradient in mode 4; in mode 5 the two-term f16 Winograd kernels for the k = 3 data
+   * gradient and for every convolution, the float32 k = 5 weight gradient).  The FC kernel plan is a function of the
+   * call's shape and mode alone (csrc/fc_block.hip: fc_plan). */
+  GFLA_TUNE_RETIRED_19 = 19,
+  /* timing ablations of the Winograd kernels -- only in `make PROBES=1` builds (results are garbage;
+   * tools/probe_wino.py); a default build ignores the key.  Bits 1 .. 16: the float32 k = 5 convolution; 32 + bits: the
+   * float32 k = 5 weight gradient; 64 + bits: the two-term f16 k = 5 weight gradient.  [fc_wino.hip: wn_launch,
+   * fc_wino_wgrad_jobs; fc_wino16.hip: fc_wino16_wgrad_jobs] */
+  GFLA_TUNE_WINO_PROBE = 20,
+  /* Winograd convolutions.  1 a single raw buffer in LDS, never two; 2 one launch per half instead of both halves in
+   * one, which also separates the two weight-gradient kernels of a layer again.  [fc_wino_shared.h: wn_plan;
+   * fc_wino.hip: fc_wino_conv_jobs; fc_wino16.hip: fc_wino16_conv_jobs; fc_block.hip: fc_plan] */
+  GFLA_TUNE_WINO_LAUNCH = 21,
+  /* resample2d d/d input2 at k = 4.  0 the stream kernel, 1 the planes-in-LDS gather.  [gs_route.h: rs_bwd_route] */
+  GFLA_TUNE_RS_BWD2_NO_STREAM = 22,
+  /* resample2d d/d input1, planes-in-LDS scatter (float32).  0 fixed point + tap records (with scratch), 1 double planes
+   * (round 1), 2 fixed point without the table.  [gs_route.h: rs_bwd_route] */
+  GFLA_TUNE_RS_BWD1_PLANES = 23,
+  /* be_fwd_pix_kernel / be_fwd_wrow_kernel: threads per workgroup (0 auto; multiples of 64 up to 1024; a count the
+   * wave-per-flow-row kernel's LDS cannot hold sends the call to the next kernel).  [be_fwd_pix.h: pix_geometry;
+   * be_fwd_wrow.h: wrow_geometry] */
+  GFLA_TUNE_BE_FWD_THREADS = 24,
+  /* be_fwd_pix_kernel: 1 = non-temporal output stores (A/B only: half the rate).  [be_fwd_pix.h: launch_fwd_pix] */
+  GFLA_TUNE_BE_FWD_PIX_NT = 25,
+  /* timing ablations of the two round-4 block_extractor forward kernels -- only in `make PROBES=1` builds (results are
+   * garbage); a default build ignores the key.  Bit 0 = no patch reads, bit 1 = no output stores.  [be_fwd_pix.h:
+   * launch_fwd_pix; be_fwd_wrow.h: launch_fwd_wrow] */
+  GFLA_TUNE_BE_FWD_PROBE = 27,
+  /* Winograd-domain weight gradient, work units.  0 whole tile rows per unit where that needs fewer 16-tile steps
+   * (csrc/fc_wino_wgrad.h: MR), 1 one tile row per unit everywhere (round 3), 2 whole tile rows of at most 16 tiles.
+   * [fc_wino.hip: ww_geometry] */
+  GFLA_TUNE_WINO_WGRAD_UNITS = 29,
+  /* big-plane kernels (few planes, each beyond the LDS budget: csrc/tile_map.h).  0 auto, 1 never (round 1's row-window
+   * kernels), 2 always (tests drive them at small shapes).  [gs_route.h: big_plane_regime] */
+  GFLA_TUNE_BIG_PLANE = 30,
+  /* rows of a tile of the big-plane kernels but block_extractor's forward (0 auto: 16; resample2d d/d input2 8; rows x
+   * columns at most 512 pixels).  [tile_map.h: tile_geometry] */
+  GFLA_TUNE_TILE_ROWS = 31,
+  /* columns of such a tile (0 auto: 32; resample2d forward 16; at most 512).  [tile_map.h: tile_geometry] */
+  GFLA_TUNE_TILE_COLS = 32,
+  /* first-version gathers of the big-plane regime (BIG_GATHER_V1): channels per wave / thread (0 auto).  [be_tile.h:
+   * big_channels_per_wave; gs_route.h: big_gather_geometry] */
+  GFLA_TUNE_BIG_GATHER_CPW = 33,
+  /* channels per workgroup of the scatter tiles -- block_extractor backward, resample2d d/d input1 (0 auto: 8, 4 for
+   * block_extractor at k >= 5, halved while the launch is short of workgroups).  [tile_map.h: big_geometry through
+   * tile_channels] */
+  GFLA_TUNE_SCATTER_TILE_CHANNELS = 34,
+  /* rows of a tile of block_extractor's forward (0 auto: 8; rows x columns at most 512 pixels).  [tile_map.h:
+   * row_tile_geometry] */
+  GFLA_TUNE_BE_FWD_TILE_ROWS = 35,
+  /* columns of such a tile (0 auto: 32).  [tile_map.h: row_tile_geometry] */
+  GFLA_TUNE_BE_FWD_TILE_COLS = 36,
+  /* channels per workgroup of the gather tiles -- block_extractor forward, resample2d forward and d/d input2 (0 auto:
+   * 8, 8, 16, halved while the launch is short of workgroups).  [tile_map.h: big_geometry through tile_channels] */
+  GFLA_TUNE_GATHER_TILE_CHANNELS = 37,
+  /* 1 = the first version of the big-plane gathers (taps read from global memory, no LDS window): block_extractor
+   * forward, resample2d forward and d/d input2.  [gs_route.h: be_fwd_route, rs_fwd_route, rs_bwd_route] */
+  GFLA_TUNE_BIG_GATHER_V1 = 38,
+  /* timing ablations of the tile kernels -- only in `make PROBES=1` builds (results are garbage); a default build
+   * ignores the key.  [tile_map.h: tile_probe_bits] */
+  GFLA_TUNE_TILE_PROBE = 39,
+  /* block_extractor's forward tiles, float arithmetic: channels evaluated together per pixel, 1, 2 or 4 (anything else:
+   * auto).  [be_tile.h: launch_fwd_tile] */
+  GFLA_TUNE_BE_FWD_TILE_CHUNK = 40,
+  /* 1 = block_extractor's backward tiles without the cross-lane fold of the patch rows (csrc/be_tile.h: BeLinks).
+   * [be_tile.h: launch_be_bwd_tile] */
+  GFLA_TUNE_BE_BWD_TILE_NO_FOLD = 41,
+  GFLA_TUNE_RETIRED_43 = 43, /* retired, see RETIRED_19: accepted and ignored */
+  /* Winograd convolutions: 1 = groups of 32 tiles always, never whole tile rows on narrow maps.  [fc_wino_shared.h:
+   * wn_geometry] */
+  GFLA_TUNE_WINO_GROUP_32 = 44,
+  /* 1 = gfla_fc_backward_f32 scatters the gradient of the convolved source map with global float atomics (round 2)
+   * instead of the owner-computes kernel of round 6 (csrc/fc_sample.hip: fc_scatter_own_kernel).  [fc_block.hip:
+   * fc_plan] */
+  GFLA_TUNE_FC_SCATTER_ATOMICS = 46,
+  GFLA_TUNE_RETIRED_49 = 49, /* retired, see RETIRED_19: accepted and ignored */
+  GFLA_TUNE_RETIRED_52 = 52  /* retired, see RETIRED_19: accepted and ignored */
+};
 int gfla_set_tuning(int key, int value);
 
 /* Dispatch trace (tests): number of times a kernel path has been enqueued by this process, from any host thread

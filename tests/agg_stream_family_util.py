@@ -64,19 +64,10 @@ def geometry(shape, k):
     return list(out) if st == 0 else None
 
 
-class _Tuning:
-    """tuning key 8 = 2 (the streaming kernels for every odd k) and key 5 = ranges, restored on exit"""
-
-    def __init__(self, key5):
-        self.key5 = key5
-
-    def __enter__(self):
-        _lib.set_tuning(8, 2)
-        _lib.set_tuning(5, self.key5)
-
-    def __exit__(self, *exc):
-        _lib.set_tuning(8, 0)
-        _lib.set_tuning(5, 0)
+def _Tuning(key5):
+    """the streaming kernels for every odd k and `key5` channel ranges, for a `with` block (the name is the one
+    tests/golden/make_agg_stream_digests.py calls)"""
+    return _lib.tuned({_lib.TUNE_AGG_STREAM: 2, _lib.TUNE_SPLIT: key5})
 
 
 _INPUTS = {}

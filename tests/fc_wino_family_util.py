@@ -58,20 +58,6 @@ def digest(t):
     return hashlib.sha256((t + 0).contiguous().cpu().view(torch.uint8).numpy().tobytes()).hexdigest()
 
 
-class _Tuning:
-    """tuning keys set for a block, restored on exit"""
-
-    def __init__(self, **keys):
-        self.keys = {int(k[1:]): v for k, v in keys.items()}
-
-    def __enter__(self):
-        self.old = {k: _lib.set_tuning(k, v) for k, v in self.keys.items()}
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            _lib.set_tuning(k, v)
-
-
 _INPUTS = {}
 
 
@@ -129,12 +115,12 @@ def half_digests(shape, is_source, mode):
     out, gx, gw = run_half(shape, is_source, mode)
     got[key + "/out"], got[key + "/grad_x"] = digest(out), digest(gx)
     if shape in RAGGED:   # the single-raw-buffer staging forced on
-        with _Tuning(k21=1):
+        with _lib.tuned({_lib.TUNE_WINO_LAUNCH: 1}):
             out, gx, _ = run_half(shape, is_source, mode)
         got[key + "/key21_1/out"], got[key + "/key21_1/grad_x"] = digest(out), digest(gx)
     for k29, k12 in WGRAD_VARIANTS:
         if (k29, k12) != (0, 0):
-            with _Tuning(k29=k29, k12=k12):
+            with _lib.tuned({_lib.TUNE_WINO_WGRAD_UNITS: k29, _lib.TUNE_FC_WGRAD_SPLITS: k12}):
                 _, _, gw = run_half(shape, is_source, mode)
         got[key + "/key29_%d/key12_%d/grad_w0" % (k29, k12)] = digest(gw)
     return got
@@ -162,7 +148,7 @@ def layer_digests(shape, mode):
         return {}
     got = {}
     for k21 in LAYER_KEY21:
-        with _Tuning(k21=k21):
+        with _lib.tuned({_lib.TUNE_WINO_LAUNCH: k21}):
             for name, t in run_layer(shape, mode).items():
                 got["layer/%s/mode%d/key21_%d/%s" % (shape_id(shape), mode, k21, name)] = digest(t)
     return got

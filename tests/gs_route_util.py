@@ -41,9 +41,11 @@ Shapes: the smallest that reach each route through the existing tuning keys (S, 
 pinned revision reached every named route with them, so no case needed a larger one."""
 import ctypes
 import hashlib
-from contextlib import contextmanager
 
 from global_flow_local_attention_amd import _lib
+from global_flow_local_attention_amd._lib import (TUNE_AGG, TUNE_BE_BWD, TUNE_BE_FWD, TUNE_BIG_GATHER_V1, TUNE_BIG_PLANE, TUNE_G_CAP,
+                                                  TUNE_LDS_KB, TUNE_NO_WINDOWS, TUNE_RS, TUNE_RS_BWD1_PLANES, TUNE_RS_BWD2_NO_STREAM,
+                                                  TUNE_SPLIT)
 
 # ------------------------------------------------------------------------------------------------------------ part 1: queries
 # (B, C, Hs, Ws, H, W): from one tiny plane up to the bench shapes, a map whose planes are beyond the default budget with
@@ -53,8 +55,9 @@ SHAPES = [(1, 1, 6, 8, 6, 8), (2, 5, 12, 10, 12, 10), (1, 3, 32, 30, 32, 30), (2
           (1, 64, 256, 176, 256, 176), (1, 3, 256, 256, 256, 256)]
 KS = (1, 2, 3, 4, 5, 6)
 RS_KD = ((2, 1), (4, 1), (4, 2), (5, 1))
-KEY_SETS = [{}, {10: 16}, {10: 160}, {30: 1}, {30: 2}, {2: 1}, {3: 1}, {6: 1}, {4: 1}, {5: 3}, {10: 16, 5: 2}, {10: 16, 30: 1},
-            {10: 16, 30: 2}, {7: 1, 10: 16}]
+KEY_SETS = [{}, {TUNE_LDS_KB: 16}, {TUNE_LDS_KB: 160}, {TUNE_BIG_PLANE: 1}, {TUNE_BIG_PLANE: 2}, {TUNE_BE_BWD: 1}, {TUNE_AGG: 1},
+            {TUNE_RS: 1}, {TUNE_G_CAP: 1}, {TUNE_SPLIT: 3}, {TUNE_LDS_KB: 16, TUNE_SPLIT: 2}, {TUNE_LDS_KB: 16, TUNE_BIG_PLANE: 1},
+            {TUNE_LDS_KB: 16, TUNE_BIG_PLANE: 2}, {TUNE_NO_WINDOWS: 1, TUNE_LDS_KB: 16}]
 LDS_OPS = range(8)
 WINDOW_OPS = (0, 5, 6, 7)   # the ops of gfla_lds_plane_geometry whose kernels can keep a row window
 CLASSES = ("not_taken", "whole", "window", "split")   # split: whole planes shared by split > 1 workgroups
@@ -62,17 +65,6 @@ CLASSES = ("not_taken", "whole", "window", "split")   # split: whole planes shar
 
 def key_set_id(keys):
     return ",".join("%d=%d" % kv for kv in sorted(keys.items())) or "default"
-
-
-@contextmanager
-def tuning(keys):
-    """the tuning keys of `keys` set, and restored on exit"""
-    old = {k: _lib.set_tuning(k, v) for k, v in keys.items()}
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            _lib.set_tuning(k, v)
 
 
 def _lds(op, shape, k, dil, elem, needs):
@@ -144,7 +136,7 @@ def sweep():
     """{group: {"sha256": ..., "classes": {class: count}, "queries": n}} over KEY_SETS, and the rows per group"""
     groups, all_rows = {}, {}
     for keys in KEY_SETS:
-        with tuning(keys):
+        with _lib.tuned(keys):
             rows = query_rows()
         for (query, op), r in rows.items():
             classes = {}
@@ -185,38 +177,38 @@ def _be_cases():
     c = []
     fwd = ("out",)
     # forward: lane-per-pixel (f32 / f64), round 1's planes-in-LDS kernel (16-bit storage); ragged last channel group
-    for keys in ({}, {4: 2}):
+    for keys in ({}, {TUNE_G_CAP: 2}):
         c.append(_case("be_fwd", S, (F32, F64), keys, paths={12: 1}, digest=fwd))
         c.append(_case("be_fwd", S, HALVES, keys, digest=fwd))
     c.append(_case("be_fwd", R, (F32, F64), paths={12: 1}, digest=fwd))                       # wave per flow row
     for width in (10, 11, 12):                                                                # V = 2, 1, 4 outputs per lane
         c.append(_case("be_fwd", _w(width), (BF16,), digest=fwd))
-        c.append(_case("be_fwd", _w(width), (F32,), {0: 2}, digest=fwd))                      # round 1's planes in LDS
-        c.append(_case("be_fwd", _w(width), (F32,), {0: 1}, digest=fwd))                      # global gathers
-    c.append(_case("be_fwd", S, (F32,), {0: 4}, paths={12: 1}, digest=fwd))
-    c.append(_case("be_fwd", S, (F32, F64), {0: 2}, digest=fwd))
+        c.append(_case("be_fwd", _w(width), (F32,), {TUNE_BE_FWD: 2}, digest=fwd))   # round 1's planes in LDS
+        c.append(_case("be_fwd", _w(width), (F32,), {TUNE_BE_FWD: 1}, digest=fwd))   # global gathers
+    c.append(_case("be_fwd", S, (F32,), {TUNE_BE_FWD: 4}, paths={12: 1}, digest=fwd))
+    c.append(_case("be_fwd", S, (F32, F64), {TUNE_BE_FWD: 2}, digest=fwd))
     c.append(_case("be_fwd", S, (F32, BF16), k=1, digest=fwd))                                # no compile-time kernel size
     c.append(_case("be_fwd", S, (F32,), k=6, digest=fwd))
-    c.append(_case("be_fwd", W, (F32, BF16), {10: 16, 30: 1}, digest=fwd))                    # row windows
-    c.append(_case("be_fwd", W, (F32, F64), {10: 16}, paths={13: 1}, digest=fwd))             # tiles
-    c.append(_case("be_fwd", W, (F32,), {10: 16, 38: 1}, paths={13: 1}, digest=fwd))          # the tiles' first version
-    c.append(_case("be_fwd", S, (F32,), {30: 2}, paths={13: 1}, digest=fwd))
+    c.append(_case("be_fwd", W, (F32, BF16), {TUNE_LDS_KB: 16, TUNE_BIG_PLANE: 1}, digest=fwd))   # row windows
+    c.append(_case("be_fwd", W, (F32, F64), {TUNE_LDS_KB: 16}, paths={13: 1}, digest=fwd))   # tiles
+    c.append(_case("be_fwd", W, (F32,), {TUNE_LDS_KB: 16, TUNE_BIG_GATHER_V1: 1}, paths={13: 1}, digest=fwd))   # the tiles' first version
+    c.append(_case("be_fwd", S, (F32,), {TUNE_BIG_PLANE: 2}, paths={13: 1}, digest=fwd))
     # backward: no gradient is digested (double LDS planes and d/d flow across >= 3 channel groups: free-order atomics)
-    for keys in ({}, {4: 2}):
+    for keys in ({}, {TUNE_G_CAP: 2}):
         c.append(_case("be_bwd", S, ALL, keys, paths={0: 1}, lds=(0, "whole")))
-    c.append(_case("be_bwd", W, (F32,), {10: 16, 30: 1}, paths={0: 1}, lds=(0, "window")))
-    c.append(_case("be_bwd", W, (F32, F64), {10: 16}, paths={14: 1}, lds=(0, "not_taken")))
-    c.append(_case("be_bwd", S, (F32,), {30: 2}, paths={14: 1}, lds=(0, "not_taken")))
-    c.append(_case("be_bwd", S, (F32, F64), {2: 1}, paths={1: 1}, lds=(0, "not_taken")))
-    c.append(_case("be_bwd", S, HALVES, {2: 1}, paths={0: 1}, lds=(0, "whole")))               # 16-bit storage ignores key 2
+    c.append(_case("be_bwd", W, (F32,), {TUNE_LDS_KB: 16, TUNE_BIG_PLANE: 1}, paths={0: 1}, lds=(0, "window")))
+    c.append(_case("be_bwd", W, (F32, F64), {TUNE_LDS_KB: 16}, paths={14: 1}, lds=(0, "not_taken")))
+    c.append(_case("be_bwd", S, (F32,), {TUNE_BIG_PLANE: 2}, paths={14: 1}, lds=(0, "not_taken")))
+    c.append(_case("be_bwd", S, (F32, F64), {TUNE_BE_BWD: 1}, paths={1: 1}, lds=(0, "not_taken")))
+    c.append(_case("be_bwd", S, HALVES, {TUNE_BE_BWD: 1}, paths={0: 1}, lds=(0, "whole")))   # 16-bit storage ignores key 2
     c.append(_case("be_bwd", S, (F32,), k=6, lds=(0, "not_taken")))                            # the per-element kernel
     c.append(_case("be_bwd", S, HALVES, k=6, status=UNSUPPORTED, lds=(0, "not_taken")))
-    c.append(_case("be_bwd", W, HALVES, {10: 16}, status=UNSUPPORTED, lds=(0, "not_taken")))   # beyond the LDS budget
+    c.append(_case("be_bwd", W, HALVES, {TUNE_LDS_KB: 16}, status=UNSUPPORTED, lds=(0, "not_taken")))   # beyond the LDS budget
     for layout in (0, 1):
         c.append(_case("unfold_fwd", S, ALL, layout=layout, lds=(4, "whole"), digest=fwd))
         c.append(_case("unfold_bwd", S, ALL, layout=layout, lds=(2, "whole")))
-    c.append(_case("unfold_fwd", S, (F32,), {4: 2}, layout=0, lds=(4, "whole"), digest=fwd))
-    c.append(_case("unfold_bwd", W, (BF16, F32), {10: 16}, layout=0, status=UNSUPPORTED, lds=(2, "not_taken")))
+    c.append(_case("unfold_fwd", S, (F32,), {TUNE_G_CAP: 2}, layout=0, lds=(4, "whole"), digest=fwd))
+    c.append(_case("unfold_bwd", W, (BF16, F32), {TUNE_LDS_KB: 16}, layout=0, status=UNSUPPORTED, lds=(2, "not_taken")))
     c.append(_case("unfold_bwd", S, (BF16,), k=6, layout=0, status=UNSUPPORTED, lds=(2, "not_taken")))
     for mode, op in (("unfold", 2), ("attn", 1), ("both", 3)):
         c.append(_case("source_bwd", S, (F32, F64, BF16), mode=mode, layout=0, lds=(op, "whole")))
@@ -228,14 +220,14 @@ def _rs_cases():
     c = []
     fwd, g1, g2 = ("out",), ("grad_in1",), ("grad_in2",)
     c.append(_case("rs_fwd", S, ALL, k=4, lds=(5, "whole"), digest=fwd))
-    c.append(_case("rs_fwd", S, (F32,), {4: 2}, k=4, lds=(5, "whole"), digest=fwd))
+    c.append(_case("rs_fwd", S, (F32,), {TUNE_G_CAP: 2}, k=4, lds=(5, "whole"), digest=fwd))
     for k, dil in ((2, 1), (4, 2), (5, 1)):
         c.append(_case("rs_fwd", S, (F32,), k=k, dil=dil, lds=(5, "whole"), digest=fwd))
-    c.append(_case("rs_fwd", S, (F32, F64), {6: 1}, k=4, lds=(5, "not_taken"), digest=fwd))                 # global kernel
-    c.append(_case("rs_fwd", W, (F32, BF16), {10: 16, 30: 1}, k=4, lds=(5, "window"), digest=fwd))
-    c.append(_case("rs_fwd", W, (F32, F64), {10: 16}, k=4, paths={15: 1}, lds=(5, "not_taken"), digest=fwd))  # gather tiles
-    c.append(_case("rs_fwd", S, (F32, BF16), {30: 2}, k=4, paths={15: 1}, lds=(5, "not_taken"), digest=fwd))  # bf16: global gathers
-    c.append(_case("rs_fwd", S, (F32,), {30: 2, 38: 1}, k=4, paths={15: 1}, lds=(5, "not_taken"), digest=fwd))
+    c.append(_case("rs_fwd", S, (F32, F64), {TUNE_RS: 1}, k=4, lds=(5, "not_taken"), digest=fwd))   # global kernel
+    c.append(_case("rs_fwd", W, (F32, BF16), {TUNE_LDS_KB: 16, TUNE_BIG_PLANE: 1}, k=4, lds=(5, "window"), digest=fwd))
+    c.append(_case("rs_fwd", W, (F32, F64), {TUNE_LDS_KB: 16}, k=4, paths={15: 1}, lds=(5, "not_taken"), digest=fwd))  # gather tiles
+    c.append(_case("rs_fwd", S, (F32, BF16), {TUNE_BIG_PLANE: 2}, k=4, paths={15: 1}, lds=(5, "not_taken"), digest=fwd))  # bf16: global gathers
+    c.append(_case("rs_fwd", S, (F32,), {TUNE_BIG_PLANE: 2, TUNE_BIG_GATHER_V1: 1}, k=4, paths={15: 1}, lds=(5, "not_taken"), digest=fwd))
     c.append(_case("rs_fwd", S, (F32, BF16), k=10, status=UNSUPPORTED))
     # d/d input1.  Digested: fixed-point planes flushed by their sole owner (module docstring)
     for trunc in (0, 1, 2, 3):
@@ -245,25 +237,25 @@ def _rs_cases():
         c.append(_case("rs_bwd", S, (F32,), k=4, dil=2, trunc=trunc, want=(1, 0), ws=True, lds=(6, "whole"), digest=g1))  # tap records
         c.append(_case("rs_bwd", S, HALVES, k=4, trunc=trunc, want=(1, 0), lds=(6, "whole"), digest=g1))
         c.append(_case("rs_bwd", S, (F64,), k=4, trunc=trunc, want=(1, 0), lds=(6, "whole")))
-        c.append(_case("rs_bwd", S, (F32,), {23: 1}, k=4, trunc=trunc, want=(1, 0), lds=(6, "whole")))       # double planes
-        c.append(_case("rs_bwd", S, (F32,), {23: 2}, k=4, dil=2, trunc=trunc, want=(1, 0), ws=True, lds=(6, "whole"), digest=g1))
-    c.append(_case("rs_bwd", S, (F32,), {23: 2}, k=4, trunc=2, want=(1, 0), ws=True, lds=(6, "whole")))
-    c.append(_case("rs_bwd", S, (F32,), {5: 3}, k=4, trunc=2, want=(1, 0), lds=(6, "split")))                # zero-filled first
-    c.append(_case("rs_bwd", S, (F32,), {5: 3}, k=4, trunc=2, want=(1, 0), ws=True, lds=(6, "split")))
-    c.append(_case("rs_bwd", S, (F32, F64), {6: 1}, k=4, trunc=2, want=(1, 1), lds=(6, "not_taken")))         # global kernels
-    c.append(_case("rs_bwd", S, HALVES, {6: 1}, k=4, trunc=2, want=(1, 1), lds=(6, "whole")))                # ignore key 6
-    c.append(_case("rs_bwd", W, (F32,), {10: 16, 30: 1}, k=4, trunc=2, want=(1, 1), lds=(6, "window")))
-    c.append(_case("rs_bwd", W, (F32,), {10: 16, 30: 1}, k=4, trunc=2, want=(1, 0), ws=True, lds=(6, "window")))
-    c.append(_case("rs_bwd", W, (F32, F64), {10: 16}, k=4, trunc=2, want=(1, 1), paths={16: 1, 17: 1}, lds=(6, "not_taken")))
-    c.append(_case("rs_bwd", W, (F32,), {10: 16}, k=4, trunc=2, want=(1, 1), ws=True, paths={16: 1, 17: 1}, lds=(6, "not_taken")))
-    c.append(_case("rs_bwd", W, (F32,), {10: 16, 38: 1}, k=4, trunc=0, want=(0, 1), paths={17: 1}, lds=(7, "not_taken")))
-    c.append(_case("rs_bwd", S, (F32,), {30: 2}, k=4, trunc=2, want=(1, 0), paths={16: 1}, lds=(6, "not_taken")))
-    c.append(_case("rs_bwd", W, HALVES, {10: 16}, k=4, trunc=0, want=(1, 1), status=UNSUPPORTED, lds=(6, "not_taken")))
+        c.append(_case("rs_bwd", S, (F32,), {TUNE_RS_BWD1_PLANES: 1}, k=4, trunc=trunc, want=(1, 0), lds=(6, "whole")))   # double planes
+        c.append(_case("rs_bwd", S, (F32,), {TUNE_RS_BWD1_PLANES: 2}, k=4, dil=2, trunc=trunc, want=(1, 0), ws=True, lds=(6, "whole"), digest=g1))
+    c.append(_case("rs_bwd", S, (F32,), {TUNE_RS_BWD1_PLANES: 2}, k=4, trunc=2, want=(1, 0), ws=True, lds=(6, "whole")))
+    c.append(_case("rs_bwd", S, (F32,), {TUNE_SPLIT: 3}, k=4, trunc=2, want=(1, 0), lds=(6, "split")))   # zero-filled first
+    c.append(_case("rs_bwd", S, (F32,), {TUNE_SPLIT: 3}, k=4, trunc=2, want=(1, 0), ws=True, lds=(6, "split")))
+    c.append(_case("rs_bwd", S, (F32, F64), {TUNE_RS: 1}, k=4, trunc=2, want=(1, 1), lds=(6, "not_taken")))   # global kernels
+    c.append(_case("rs_bwd", S, HALVES, {TUNE_RS: 1}, k=4, trunc=2, want=(1, 1), lds=(6, "whole")))   # ignore key 6
+    c.append(_case("rs_bwd", W, (F32,), {TUNE_LDS_KB: 16, TUNE_BIG_PLANE: 1}, k=4, trunc=2, want=(1, 1), lds=(6, "window")))
+    c.append(_case("rs_bwd", W, (F32,), {TUNE_LDS_KB: 16, TUNE_BIG_PLANE: 1}, k=4, trunc=2, want=(1, 0), ws=True, lds=(6, "window")))
+    c.append(_case("rs_bwd", W, (F32, F64), {TUNE_LDS_KB: 16}, k=4, trunc=2, want=(1, 1), paths={16: 1, 17: 1}, lds=(6, "not_taken")))
+    c.append(_case("rs_bwd", W, (F32,), {TUNE_LDS_KB: 16}, k=4, trunc=2, want=(1, 1), ws=True, paths={16: 1, 17: 1}, lds=(6, "not_taken")))
+    c.append(_case("rs_bwd", W, (F32,), {TUNE_LDS_KB: 16, TUNE_BIG_GATHER_V1: 1}, k=4, trunc=0, want=(0, 1), paths={17: 1}, lds=(7, "not_taken")))
+    c.append(_case("rs_bwd", S, (F32,), {TUNE_BIG_PLANE: 2}, k=4, trunc=2, want=(1, 0), paths={16: 1}, lds=(6, "not_taken")))
+    c.append(_case("rs_bwd", W, HALVES, {TUNE_LDS_KB: 16}, k=4, trunc=0, want=(1, 1), status=UNSUPPORTED, lds=(6, "not_taken")))
     c.append(_case("rs_bwd", S, (F32, BF16), k=10, trunc=0, want=(1, 1), status=UNSUPPORTED))
     # d/d input2 at kernel_size 4, dilation 1: the streaming kernel (digested where it has at most two channel ranges), and
     # rs_lds_kernel under key 22 = 1 and for f64 / dilation 2 (three atomics per lane and channel group: not digested)
     c.append(_case("rs_bwd", S, (F32, BF16, F16), k=4, want=(0, 1), lds=(7, "whole"), digest=g2, stream_ranges=True))
-    c.append(_case("rs_bwd", S, (F32, BF16), {22: 1}, k=4, want=(0, 1), lds=(7, "whole")))
+    c.append(_case("rs_bwd", S, (F32, BF16), {TUNE_RS_BWD2_NO_STREAM: 1}, k=4, want=(0, 1), lds=(7, "whole")))
     c.append(_case("rs_bwd", S, (F64,), k=4, want=(0, 1), lds=(7, "whole")))
     c.append(_case("rs_bwd", S, (F32,), k=4, dil=2, want=(0, 1), lds=(7, "whole")))
     c.append(_case("rs_bwd", S, (F32, BF16), k=4, want=(1, 1), lds=(7, "whole")))
@@ -276,17 +268,17 @@ def _agg_cases():
     for k in (3, 5):
         c.append(_case("agg_fwd", S, (F32, BF16, F16), k=k, ws=True, digest=fwd, stream=k == 5))   # k = 5: table + streaming kernel
         c.append(_case("agg_fwd", S, (F32, F64, BF16), k=k, digest=fwd))
-        c.append(_case("agg_fwd", S, (F32,), {3: 1}, k=k, ws=True, digest=fwd))       # global kernel
-        c.append(_case("agg_fwd", S, (F32,), {4: 2}, k=k, digest=fwd))
+        c.append(_case("agg_fwd", S, (F32,), {TUNE_AGG: 1}, k=k, ws=True, digest=fwd))   # global kernel
+        c.append(_case("agg_fwd", S, (F32,), {TUNE_G_CAP: 2}, k=k, digest=fwd))
         # backward: d/d logits is digested where it comes from the streaming kernel with at most two channel ranges
         c.append(_case("agg_bwd", S, (F32,), k=k, ws=True, digest=("grad_logits",) if k == 5 else (), stream_ranges=k == 5))
         c.append(_case("agg_bwd", S, (F32, BF16, F16), k=k, digest=("grad_logits",) if k == 5 else (), stream_ranges=k == 5))
         c.append(_case("agg_bwd", S, (F64,), k=k))
-        c.append(_case("agg_bwd", S, (F32,), {3: 1}, k=k, ws=True))                    # global kernel
-        c.append(_case("agg_bwd", S, (BF16,), {3: 1}, k=k))                            # 16-bit storage ignores key 3
-    c.append(_case("agg_bwd", W, HALVES, {10: 16}, status=UNSUPPORTED))
-    c.append(_case("agg_bwd", W, (F32,), {10: 16}))                                    # the global kernel behind the LDS ones
-    c.append(_case("agg_bwd", W, (F32,), {10: 16}, ws=True))
+        c.append(_case("agg_bwd", S, (F32,), {TUNE_AGG: 1}, k=k, ws=True))   # global kernel
+        c.append(_case("agg_bwd", S, (BF16,), {TUNE_AGG: 1}, k=k))   # 16-bit storage ignores key 3
+    c.append(_case("agg_bwd", W, HALVES, {TUNE_LDS_KB: 16}, status=UNSUPPORTED))
+    c.append(_case("agg_bwd", W, (F32,), {TUNE_LDS_KB: 16}))   # the global kernel behind the LDS ones
+    c.append(_case("agg_bwd", W, (F32,), {TUNE_LDS_KB: 16}, ws=True))
     return c
 
 
@@ -406,7 +398,7 @@ def run_gpu_case(case):
     channel ranges of the streaming kernel (where a digest depends on them) and the digests of the case's order-independent
     outputs (only where the call succeeded)."""
     records = {}
-    with tuning(case["keys"]):
+    with _lib.tuned(case["keys"]):
         for name in case["dtypes"]:
             elem = {F32: 4, F64: 8, BF16: 2, F16: 2}[name]
             before = [_lib.path_count(i) for i in PATH_IDS]

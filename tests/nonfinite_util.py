@@ -632,11 +632,8 @@ def max_cosine_cases(rows=COSINE_ROWS):
 
                 def run(gfla, inp, shape=shape, split=split):
                     s, t = _leaf(inp["source"]), _leaf(inp["target"])
-                    old = gfla.set_tuning(5, split)
-                    try:
+                    with gfla.tuned({gfla.TUNE_SPLIT: split}):
                         best, index = gfla.max_cosine_similarity(s, t, return_index=True)
-                    finally:
-                        gfla.set_tuning(5, old)
                     # ORDER MATTERS: the backward gathers and scatters at `index` on the device.  It runs only behind this
                     # assertion, made on the host
                     host = index.cpu()

@@ -51,6 +51,7 @@ flow comparison only.  Forward results and feature-map gradients are compared ev
 import torch
 import torch.nn.functional as F
 
+from global_flow_local_attention_amd import TUNE_BIG_PLANE, TUNE_LDS_KB, TUNE_RS, TUNE_RS_BWD1_PLANES
 from util import make_flow, rand, randn
 
 CLEAR = 1e-3
@@ -348,7 +349,8 @@ def rs_fixed_point_term(cnt, up, dtype):
 # atomics: at most the float32 sum the bar allows.  Since the product decides on the device whether the fixed-point scatter
 # behind it runs instead, the float32 cases keep rs_fixed_point_term under every key set but 23 = 1 and 6 = 1.
 def rs_input1_term(cnt, up, dtype, keys):
-    if dtype == torch.float32 and (keys.get(23) == 1 or keys.get(6) == 1):      # (16-bit storage ignores both keys)
+    # (16-bit storage ignores both keys)
+    if dtype == torch.float32 and (keys.get(TUNE_RS_BWD1_PLANES) == 1 or keys.get(TUNE_RS) == 1):
         return torch.zeros_like(cnt)
     return rs_fixed_point_term(cnt, up, dtype)
 
@@ -458,25 +460,9 @@ def patches_from_unfold(t, k):
 
 
 # ------------------------------------------------------------------------------------------------- tuning keys, the query
-class Tuning(object):
-    """Process-global tuning keys for the duration of a `with` block; the old values come back on every exit path."""
-
-    def __init__(self, gfla, keys):
-        self.gfla, self.keys, self.old = gfla, dict(keys), {}
-
-    def __enter__(self):
-        for key, value in self.keys.items():
-            self.old[key] = self.gfla.set_tuning(key, value)
-        return self
-
-    def __exit__(self, *exc):
-        for key, value in self.old.items():
-            self.gfla.set_tuning(key, value)
-
-
 # key 10 = 16 (KB of LDS) alone hands few large planes to the tile kernels of csrc/tile_map.h; key 30 = 1 keeps them out, so
 # planes beyond 16 KB run as row windows of this family
-WINDOWS = {10: 16, 30: 1}
+WINDOWS = {TUNE_LDS_KB: 16, TUNE_BIG_PLANE: 1}
 QUERY_OPS = {"be_bwd": 0, "agg_bwd": 1, "unfold_bwd": 2, "unfold_attn_bwd": 3, "unfold_fwd": 4, "rs_fwd": 5, "rs_bwd1": 6, "rs_bwd2": 7}
 
 

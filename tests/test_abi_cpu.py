@@ -299,3 +299,119 @@ def test_big_plane_tile_geometry_and_xcd_remap_invariants(gfla):
             mine = [img[b] for b in range(x, nwg, 8)]
             assert mine == list(range(mine[0], mine[0] + len(mine))), (nwg, x)      # contiguous, in launch order
         assert L.gfla_xcd_swizzle(nwg, nwg) == -1 and L.gfla_xcd_swizzle(-1, nwg) == -1
+
+
+# ------------------------------------------------------------------------------------------------------- tuning keys
+CSRC = os.path.join(ROOT, "global_flow_local_attention_amd", "csrc")
+RETIRED_KEYS = (19, 43, 49, 52)
+
+
+def _header_tuning_keys():
+    """{GFLA_TUNE_X: value} read from the header's text, not through the parser under test"""
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "gfla_hip.h")).read(), flags=re.S)
+    body = re.search(r"enum gfla_tuning_key \{(.*?)\}", text, flags=re.S).group(1)
+    items = [item.strip() for item in body.split(",") if item.strip()]
+    assert all(re.fullmatch(r"GFLA_TUNE_\w+ = \d+", item) for item in items), items
+    return dict((item.split(" = ")[0], int(item.split(" = ")[1])) for item in items)
+
+
+def _csrc_without_comments():
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".hip", ".h", ".inc")):
+            text = open(os.path.join(CSRC, name)).read()
+            yield name, re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
+
+
+def test_tuning_keys_of_header_and_sources_agree():
+    keys = _header_tuning_keys()
+    assert len(set(keys.values())) == len(keys) >= 40 and all(0 <= v < 64 for v in keys.values())     # kTuningKeys = 64
+    retired = {name for name in keys if name.startswith("GFLA_TUNE_RETIRED_")}
+    assert sorted(keys[name] for name in retired) == list(RETIRED_KEYS)
+    assert all(name == "GFLA_TUNE_RETIRED_%d" % keys[name] for name in retired)
+    read, calls = set(), 0
+    for name, text in _csrc_without_comments():
+        if name == "abi.hip":
+            assert "constexpr int kTuningKeys = 64;" in text
+        for arg in re.findall(r"\btuning\(([^()]*)\)", text):
+            if arg == "int key":       # the declaration (gfla_common.h) and the definition (abi.hip)
+                assert name in ("gfla_common.h", "abi.hip")
+            elif arg == "key":         # tile_channels' parameter; its call sites are checked below
+                assert name == "tile_map.h"
+            else:
+                assert arg in keys, "%s: tuning(%s) does not name an enumerator" % (name, arg)
+                read.add(arg)
+                calls += 1
+        if name == "tile_map.h":
+            assert "inline int tile_channels(gfla_tuning_key key," in text
+            passed = re.findall(r"\btile_channels\((\w+),", text)
+            assert len(passed) == 4 and set(passed) <= set(keys), passed
+            read.update(passed)
+    assert calls > 80
+    assert read == set(keys) - retired, (sorted(set(keys) - retired - read), sorted(read & retired))
+
+
+def test_set_tuning_rejects_what_is_no_enumerator(gfla):
+    from global_flow_local_attention_amd import _lib
+    keys = _header_tuning_keys()
+    assert {"GFLA_" + name: value for name, value in _lib.TUNING_KEYS.items()} == keys
+    for name, value in keys.items():
+        assert getattr(gfla, name[len("GFLA_"):]) == getattr(_lib, name[len("GFLA_"):]) == value
+    for key in (18, 63, 26, 64, -1):
+        assert key not in keys.values()
+        with pytest.raises(ValueError):
+            gfla.set_tuning(key, 1)
+    c_set = _lib.lib().gfla_set_tuning          # the C entry point takes any number: nothing reads 18, nothing stores 64
+    assert (c_set(18, 1), c_set(18, 0), c_set(64, 1), c_set(64, 0)) == (0, 1, 0, 0)
+    for key in RETIRED_KEYS:
+        gfla.set_tuning(key, gfla.set_tuning(key, 1))
+    assert gfla.set_tuning(gfla.TUNE_SPLIT, 3) == 0
+    assert gfla.set_tuning(gfla.TUNE_SPLIT, 0) == 3
+    assert gfla.set_tuning(gfla.TUNE_SPLIT, 0) == 0
+
+
+def test_tuned_restores_the_previous_values(gfla):
+    G, S = gfla.TUNE_G_CAP, gfla.TUNE_SPLIT
+
+    def now(key):
+        value = gfla.set_tuning(key, 0)
+        gfla.set_tuning(key, value)
+        return value
+
+    assert (now(G), now(S)) == (0, 0)
+    with gfla.tuned({G: 2, S: 3}):                      # a normal exit
+        assert (now(G), now(S)) == (2, 3)
+    assert (now(G), now(S)) == (0, 0)
+    with pytest.raises(RuntimeError):                   # an exception inside the block
+        with gfla.tuned({G: 2, S: 3}):
+            raise RuntimeError("a failing case")
+    assert (now(G), now(S)) == (0, 0)
+    with pytest.raises(ValueError):                     # a key that is no enumerator: the keys set before it come back too
+        with gfla.tuned({G: 2, 18: 1}):
+            pass
+    assert now(G) == 0
+    with gfla.tuned({G: 2}):                            # two blocks that set the same key
+        with gfla.tuned({G: 5, S: 1}):
+            assert (now(G), now(S)) == (5, 1)
+        assert (now(G), now(S)) == (2, 0)
+    assert (now(G), now(S)) == (0, 0)
+    assert gfla.set_tuning(G, 7) == 0                   # a key that is not 0 on entry
+    try:
+        with gfla.tuned({G: 1}):
+            assert now(G) == 1
+        assert now(G) == 7
+    finally:
+        gfla.set_tuning(G, 0)
+
+
+def test_no_numeric_tuning_key_in_tests_and_tools():
+    """every set_tuning call of tests/ and tools/ names its key (this file passes numbers on purpose)"""
+    found = []
+    for top in ("tests", "tools"):
+        for folder, _, files in os.walk(os.path.join(ROOT, top)):
+            for name in files:
+                path = os.path.join(folder, name)
+                if name.endswith(".py") and path != os.path.abspath(__file__):
+                    for n, line in enumerate(open(path), 1):
+                        if re.search(r"set_tuning\(\s*\d", line):
+                            found.append("%s:%d" % (os.path.relpath(path, ROOT), n))
+    assert not found, found

@@ -14,6 +14,7 @@ kernel family that serves it (round 5: few planes, each far beyond the LDS budge
 import pytest
 import torch
 
+import global_flow_local_attention_amd as T
 from test_bench_shapes_gpu import _ref
 from test_default_path_gpu import KINDS, flow_of, rel_err
 from util import assert_close, make_flow, rand, randn
@@ -106,28 +107,24 @@ def test_config2_resample2d_all_flows_vs_reference_kernels(gfla, kind):
 
 
 # ------------------------------------------------------------------------------------------ 2. forced, small shapes
-# tuning keys: 30 = 2 force the family; 31 / 32 tile rows / columns; 33 channels per wave / thread of the first-version gathers;
-# 34 channels per workgroup of the scatter tiles; 10 LDS budget in KB (16 KB: several channel rounds, tiles on global memory)
-# 35 / 36 tile of block_extractor's forward; 37 channels per workgroup of the gather tiles; 38 = 1 the first version of the
-# gathers (taps read from global memory: the bodies every window kernel falls back to per tile); 40 channels per pixel chunk;
-# 41 = 1 block_extractor's source scatter without the cross-lane fold of the patch rows (be_tile.h: BeLinks)
-GEOS = [{}, {31: 3, 32: 5, 34: 1, 33: 1, 35: 3, 36: 5, 37: 1}, {31: 16, 32: 32, 34: 7, 33: 3, 35: 2, 36: 48, 37: 7, 40: 1, 41: 1},
-        {31: 4, 32: 64, 34: 3, 10: 16, 33: 2, 35: 16, 36: 32, 37: 5}, {31: 32, 32: 16, 34: 5, 10: 16, 38: 1, 41: 1},
-        {31: 1, 32: 512, 34: 2, 35: 1, 36: 512, 37: 2, 40: 2}, {38: 1, 33: 2}]
+# T.TUNE_BIG_PLANE = 2 forces the family; the geometries: tile sizes, channels per workgroup, 16 KB of LDS (several channel
+# rounds, tiles on global memory), the first version of the gathers (the bodies every window kernel falls back to per tile),
+# block_extractor's source scatter without the cross-lane fold (include/gfla_hip.h: enum gfla_tuning_key)
+GEOS = [{},
+        {T.TUNE_TILE_ROWS: 3, T.TUNE_TILE_COLS: 5, T.TUNE_SCATTER_TILE_CHANNELS: 1, T.TUNE_BIG_GATHER_CPW: 1,
+         T.TUNE_BE_FWD_TILE_ROWS: 3, T.TUNE_BE_FWD_TILE_COLS: 5, T.TUNE_GATHER_TILE_CHANNELS: 1},
+        {T.TUNE_TILE_ROWS: 16, T.TUNE_TILE_COLS: 32, T.TUNE_SCATTER_TILE_CHANNELS: 7, T.TUNE_BIG_GATHER_CPW: 3,
+         T.TUNE_BE_FWD_TILE_ROWS: 2, T.TUNE_BE_FWD_TILE_COLS: 48, T.TUNE_GATHER_TILE_CHANNELS: 7, T.TUNE_BE_FWD_TILE_CHUNK: 1,
+         T.TUNE_BE_BWD_TILE_NO_FOLD: 1},
+        {T.TUNE_TILE_ROWS: 4, T.TUNE_TILE_COLS: 64, T.TUNE_SCATTER_TILE_CHANNELS: 3, T.TUNE_LDS_KB: 16, T.TUNE_BIG_GATHER_CPW: 2,
+         T.TUNE_BE_FWD_TILE_ROWS: 16, T.TUNE_BE_FWD_TILE_COLS: 32, T.TUNE_GATHER_TILE_CHANNELS: 5},
+        {T.TUNE_TILE_ROWS: 32, T.TUNE_TILE_COLS: 16, T.TUNE_SCATTER_TILE_CHANNELS: 5, T.TUNE_LDS_KB: 16, T.TUNE_BIG_GATHER_V1: 1,
+         T.TUNE_BE_BWD_TILE_NO_FOLD: 1},
+        {T.TUNE_TILE_ROWS: 1, T.TUNE_TILE_COLS: 512, T.TUNE_SCATTER_TILE_CHANNELS: 2, T.TUNE_BE_FWD_TILE_ROWS: 1,
+         T.TUNE_BE_FWD_TILE_COLS: 512, T.TUNE_GATHER_TILE_CHANNELS: 2, T.TUNE_BE_FWD_TILE_CHUNK: 2},
+        {T.TUNE_BIG_GATHER_V1: 1, T.TUNE_BIG_GATHER_CPW: 2}]
 SHAPES = [  # B, C, Hs, Ws, Hf, Wf
     (2, 5, 21, 17, 21, 17), (1, 9, 40, 60, 40, 60), (2, 3, 12, 20, 9, 14), (1, 6, 7, 5, 11, 3), (1, 4, 64, 48, 64, 48)]
-
-
-class _Tuning(object):
-    def __init__(self, gfla, keys):
-        self.gfla, self.keys = gfla, dict(keys)
-
-    def __enter__(self):
-        self.old = {k: self.gfla.set_tuning(k, v) for k, v in self.keys.items()}
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            self.gfla.set_tuning(k, v)
 
 
 @pytest.mark.parametrize("geo", range(len(GEOS)))
@@ -135,8 +132,8 @@ class _Tuning(object):
 def test_block_extractor_big_plane_kernels_forced(gfla, oracle, k, geo):
     from global_flow_local_attention_amd import _lib
     keys = dict(GEOS[geo])
-    keys[30] = 2
-    with _Tuning(gfla, keys):
+    keys[T.TUNE_BIG_PLANE] = 2
+    with gfla.tuned(keys):
         for (B, C, Hs, Ws, Hf, Wf) in SHAPES:
             for dtype, tf, tg in ((torch.float32, 2e-6, 2e-5), (torch.float64, 1e-12, 1e-11)):
                 for kind, scale in (("wild", 0.6), ("wild", 3.0), ("smooth", 1.0)):
@@ -174,9 +171,9 @@ def test_block_extractor_big_plane_kernels_forced(gfla, oracle, k, geo):
 def test_resample2d_big_plane_kernels_forced(gfla, oracle, k, dil, geo):
     from global_flow_local_attention_amd import _lib
     keys = dict(GEOS[geo])
-    keys[30] = 2
+    keys[T.TUNE_BIG_PLANE] = 2
     ids = (_lib.PATH_RS_FWD_BIG, _lib.PATH_RS_BWD1_TILE, _lib.PATH_RS_BWD2_BIG)
-    with _Tuning(gfla, keys):
+    with gfla.tuned(keys):
         for (B, C, Hi, Wi, H, W) in SHAPES:
             for dtype, tf, tg in ((torch.float32, 4e-6, 3e-5), (torch.float64, 1e-12, 1e-10)):
                 for kind, scale in (("wild", 0.6), ("wild", 3.0), ("smooth", 1.0)):
@@ -204,8 +201,8 @@ def test_resample2d_big_plane_forward_bf16_forced(gfla, oracle, geo):
     float32 oracle, 2^-7 of the largest entry (the bf16 bar of tests/test_gpu_parity.py)."""
     from global_flow_local_attention_amd import _lib
     keys = dict(GEOS[geo])
-    keys[30] = 2
-    with _Tuning(gfla, keys):
+    keys[T.TUNE_BIG_PLANE] = 2
+    with gfla.tuned(keys):
         for (B, C, Hi, Wi, H, W) in SHAPES:
             for kind, scale in (("wild", 3.0), ("smooth", 1.0)):
                 i1 = randn((B, C, Hi, Wi), seed=13).bfloat16()
@@ -260,7 +257,7 @@ def test_resample2d_tile_scatter_trunc_compat_both_ways(gfla, oracle):
     left / top border.  The tile scatter reproduces it by default and gives the forward's true gradient with it off."""
     from global_flow_local_attention_amd import resample2d as rs
     B, C, H, W = 2, 6, 24, 36
-    with _Tuning(gfla, {30: 2}):
+    with gfla.tuned({T.TUNE_BIG_PLANE: 2}):
         for dtype, tol in ((torch.float64, 1e-11), (torch.float32, 2e-5)):
             i1 = randn((B, C, H, W), dtype, seed=19)
             i2 = torch.cat((make_flow("wild", B, H, W, dtype, seed=20), rand((B, 1, H, W), dtype, seed=21) * 3 + 0.3), 1).contiguous()
@@ -307,7 +304,7 @@ def test_config2_round1_row_window_kernels_still_agree(gfla, oracle, k):
     """tuning key 30 = 1: the configuration on round 1's row-window kernels (what serves planes beyond the LDS budget when
     there are MANY of them, B*C >= 1024) -- kept under test now that the default dispatch at this shape has moved on."""
     from global_flow_local_attention_amd import _lib
-    with _Tuning(gfla, {30: 1}):
+    with gfla.tuned({T.TUNE_BIG_PLANE: 1}):
         s, f = randn((1, 16, 256, 176), seed=34), make_flow("smooth", 1, 256, 176, seed=35)
         sd, fd = s.to(DEV).requires_grad_(), f.to(DEV).requires_grad_()
         n_f, n_b = _lib.path_count(_lib.PATH_BE_FWD_GPIX), _lib.path_count(_lib.PATH_BE_BWD_TILE)

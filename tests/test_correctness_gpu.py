@@ -49,11 +49,8 @@ def test_max_cosine_matches_host_bmm_max(gfla, B, C, Ns, Nt):
 def test_max_cosine_source_range_split(gfla, split):
     """units over ranges of source tiles merge through the packed atomic max (tuning key 5 forces the split)"""
     src, tgt = features((2, 32, 1000), 11), features((2, 32, 260), 12)
-    old = gfla.set_tuning(5, split)
-    try:
+    with gfla.tuned({gfla.TUNE_SPLIT: split}):
         best, index = gfla.max_cosine_similarity(src.to(DEV), tgt.to(DEV), return_index=True)
-    finally:
-        gfla.set_tuning(5, old)
     check_best(best, index, src, tgt)
 
 

@@ -63,11 +63,8 @@ def test_max_cosine_half_matches_host_bmm_max(gfla, dtype, B, C, Ns, Nt):
 def test_max_cosine_half_source_range_split(gfla, dtype, split):
     """units over ranges of source tiles merge through the packed atomic max (tuning key 5 forces the split)"""
     src, tgt = features((2, 32, 1000), 11, dtype), features((2, 32, 260), 12, dtype)
-    old = gfla.set_tuning(5, split)
-    try:
+    with gfla.tuned({gfla.TUNE_SPLIT: split}):
         best, index = gfla.max_cosine_similarity(src.to(DEV), tgt.to(DEV), return_index=True)
-    finally:
-        gfla.set_tuning(5, old)
     check_best(best, index, src, tgt)
 
 
@@ -222,8 +219,7 @@ def test_loss_default_is_the_float32_upcast_bit_for_bit(gfla, dtype):
     plain.source_vgg = {k: v.float() for k, v in mod.source_vgg.items()}
     plain.target_vgg = {k: v.float() for k, v in mod.target_vgg.items()}
     mask = (randn((2, 1, 24, 20), seed=51) > -0.3).float().to(DEV)
-    old = gfla.set_tuning(6, 1), gfla.set_tuning(1, 4096)
-    try:
+    with gfla.tuned({gfla.TUNE_RS: 1, gfla.TUNE_GLOBAL_CPT: 4096}):
         for layer, (h, w), seed in (("relu3_1", (12, 10), 61), ("relu4_1", (6, 5), 62)):
             for m in (None, mask):
                 f1 = make_flow("coherent", 2, h, w, seed=seed).to(DEV).requires_grad_()
@@ -236,9 +232,6 @@ def test_loss_default_is_the_float32_upcast_bit_for_bit(gfla, dtype):
                       % (layer, a.item(), b.item(), (f1.grad - f2.grad).abs().max().item()))
                 assert a.dtype == torch.float32 and torch.equal(a, b)
                 assert torch.equal(f1.grad, f2.grad)
-    finally:
-        gfla.set_tuning(6, old[0])
-        gfla.set_tuning(1, old[1])
     with pytest.raises(ValueError):
         gfla.PerceptualCorrectness(half_features="bfloat16")
 

@@ -23,6 +23,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import global_flow_local_attention_amd as T
 from test_bench_shapes_gpu import BENCH_SHAPES, NAMES, _ref, reference_extractor_attn, run_module
 from util import assert_close, make_flow, randn
 
@@ -167,22 +168,22 @@ def test_block_extractor_forward_kernels_agree(gfla):
             f = (flow_of(kind, B, H, W, 2) if kind in KINDS else make_flow(kind, B, H, W, seed=2)).to(DEV)
             outs = []
             for key0 in (4, 3, 2, 1):
-                old = gfla.set_tuning(0, key0)
-                try:
+                with gfla.tuned({gfla.TUNE_BE_FWD: key0}):
                     o = torch.empty(B, C, k * H, k * W, device=DEV)
                     _lib.call("gfla_block_extractor_fwd_f32", s, _lib.ptr(s), _lib.ptr(f), _lib.ptr(o), B, C, H, W, H, W, k)
                     outs.append(o)
-                finally:
-                    gfla.set_tuning(0, old)
             assert torch.equal(outs[0], outs[1]), ((B, C, H, W, k), kind, "wave-per-row vs pixel kernel (same arithmetic: identical bits)")
             for o in outs[2:]:
                 d = (outs[0] - o).abs().max().item()
                 assert d <= 1e-6, ((B, C, H, W, k), kind, d)
 
 
-GEOMETRIES = [("wrow", {0: 4, 4: 1, 24: 64}), ("wrow", {0: 4, 4: 3, 24: 192}), ("wrow", {0: 4, 4: 8, 24: 1024}), ("wrow", {0: 4, 10: 24}),
-              ("pix", {0: 3, 4: 1, 5: 1, 24: 64}), ("pix", {0: 3, 4: 4, 5: 3, 24: 256}), ("pix", {0: 3, 4: 7, 5: 2, 24: 704}),
-              ("pix", {0: 3, 4: 16, 5: 1, 24: 1024}), ("pix", {0: 3, 25: 1})]
+_FWD, _G, _SPLIT, _THREADS = T.TUNE_BE_FWD, T.TUNE_G_CAP, T.TUNE_SPLIT, T.TUNE_BE_FWD_THREADS
+GEOMETRIES = [("wrow", {_FWD: 4, _G: 1, _THREADS: 64}), ("wrow", {_FWD: 4, _G: 3, _THREADS: 192}), ("wrow", {_FWD: 4, _G: 8, _THREADS: 1024}),
+              ("wrow", {_FWD: 4, T.TUNE_LDS_KB: 24}),
+              ("pix", {_FWD: 3, _G: 1, _SPLIT: 1, _THREADS: 64}), ("pix", {_FWD: 3, _G: 4, _SPLIT: 3, _THREADS: 256}),
+              ("pix", {_FWD: 3, _G: 7, _SPLIT: 2, _THREADS: 704}), ("pix", {_FWD: 3, _G: 16, _SPLIT: 1, _THREADS: 1024}),
+              ("pix", {_FWD: 3, T.TUNE_BE_FWD_PIX_NT: 1})]
 
 
 @pytest.mark.parametrize("kernel,keys", GEOMETRIES)
@@ -193,8 +194,7 @@ def test_block_extractor_forward_kernel_geometries(gfla, oracle, kernel, keys):
     waves, plain and non-temporal stores) -- against the CPU oracle, f32 and f64, Hs != Hf, odd widths (16-byte phase of
     the band's piece of the output plane: head / tail elements of the copy)."""
     from global_flow_local_attention_amd import _lib
-    olds = {kk: gfla.set_tuning(kk, v) for kk, v in keys.items()}
-    try:
+    with gfla.tuned(keys):
         for (B, C, Hs, Ws, Hf, Wf, k) in ((2, 10, 21, 17, 21, 17, 3), (1, 6, 12, 20, 9, 14, 5), (2, 5, 8, 8, 11, 3, 4),
                                           (1, 3, 7, 5, 7, 5, 5), (1, 9, 16, 12, 16, 12, 2)):
             for dtype, tol_ in ((torch.float32, 2e-6), (torch.float64, 1e-12)):
@@ -211,9 +211,6 @@ def test_block_extractor_forward_kernel_geometries(gfla, oracle, kernel, keys):
                 assert _lib.path_count(_lib.PATH_BE_FWD_PIX) == before + 1
                 assert torch.isnan(buf[0]).item()
                 assert_close(got.cpu(), want, tol_, "%s kernel %s keys %s" % (kernel, (B, C, Hs, Ws, Hf, Wf, k), keys))
-    finally:
-        for kk, v in olds.items():
-            gfla.set_tuning(kk, v)
 
 
 # ------------------------------------------------------------------------------------------------ Resample2d
@@ -259,8 +256,7 @@ def test_resample2d_tiny_sigma_fixed_point_planes(gfla, oracle):
     B, C, H, W = 2, 6, 24, 20
     i1 = randn((B, C, H, W), seed=1)
     go = randn((B, C, H, W), seed=2)
-    o14 = gfla.set_tuning(14, 1)
-    try:
+    with gfla.tuned({gfla.TUNE_PM: 1}):
         for sigma in (0.5, 0.09, 0.06, 0.045):
             flow = make_flow("smooth", B, H, W, seed=3) * 0.3
             i2 = torch.cat((flow, torch.full((B, 1, H, W), sigma)), 1).contiguous()
@@ -268,16 +264,13 @@ def test_resample2d_tiny_sigma_fixed_point_planes(gfla, oracle):
             i1d, i2d, god = i1.to(DEV), i2.to(DEV), go.to(DEV)     # (kept alive across the asynchronous calls)
             res = []
             for key23 in (0, 1):
-                old = gfla.set_tuning(23, key23)
-                try:
+                with gfla.tuned({gfla.TUNE_RS_BWD1_PLANES: key23}):
                     g1 = torch.full((B, C, H, W), float("nan"), device=DEV)
                     ws = _lib.scatter_workspace(g1, B, H, W, 16)
                     _lib.call("gfla_resample2d_bwd_ws_f32", g1, _lib.ptr(i1d), _lib.ptr(i2d), _lib.ptr(god),
                               _lib.ptr(g1), None, _lib.ptr(ws), B, C, H, W, H, W, 4, 1, 3)
                     torch.cuda.synchronize()
                     res.append(g1.cpu())
-                finally:
-                    gfla.set_tuning(23, old)
             scale = max(want[torch.isfinite(want)].abs().max().item(), 1e-3)
             bad = [int((~torch.isfinite(r)).sum()) for r in res] + [int((~torch.isfinite(want)).sum())]
             print("sigma %.3f: non-finite entries fixed / double / oracle %s; fixed vs double %.2e, fixed vs float32 oracle %.2e "
@@ -290,8 +283,6 @@ def test_resample2d_tiny_sigma_fixed_point_planes(gfla, oracle):
             if sigma >= 0.06:   # below, the normalising sum sits in float32's denormal range: the host keeps denormals that
                                 # the GPU's exp / multiply flush, and "the reference's float arithmetic" stops being one function
                 assert (res[0] - want)[ok].abs().max().item() <= 1e-4 * scale, sigma
-    finally:
-        gfla.set_tuning(14, o14)
 
 
 def test_resample2d_forward_small_sigma_stays_finite(gfla, oracle):
@@ -331,12 +322,8 @@ SCATTER_MODES = {           # tuning key 14 (0 auto, 1 never, 2 wherever support
 
 def _with_scatter_mode(gfla, mode, fn):
     k14, k15 = SCATTER_MODES[mode]
-    o14, o15 = gfla.set_tuning(14, k14), gfla.set_tuning(15, k15)
-    try:
+    with gfla.tuned({gfla.TUNE_PM: k14, gfla.TUNE_PM_LIMIT_ROWS: k15}):
         return fn()
-    finally:
-        gfla.set_tuning(14, o14)
-        gfla.set_tuning(15, o15)
 
 
 @pytest.mark.parametrize("mode", list(SCATTER_MODES))

@@ -390,11 +390,8 @@ def test_owner_computes_scatter_equals_the_atomics(lib, gfla, mode, k, C, H, W, 
     names = ("logits", "source", "target", "flow", "w0", "b0", "w1", "b1")
     own = _fc_backward_raw(lib, mode, s, t, f, w0, b0, w1, b1, up, k)
     again = _fc_backward_raw(lib, mode, s, t, f, w0, b0, w1, b1, up, k)
-    old = gfla.set_tuning(46, 1)
-    try:
+    with gfla.tuned({gfla.TUNE_FC_SCATTER_ATOMICS: 1}):
         atom = _fc_backward_raw(lib, mode, s, t, f, w0, b0, w1, b1, up, k)
-    finally:
-        gfla.set_tuning(46, old)
     for n_, a, b_, c_ in zip(names, own, atom, again):
         assert torch.isfinite(a).all(), n_
         e = rel_err(a.cpu(), b_.cpu())

@@ -151,11 +151,8 @@ def test_exact_scatter_owner_computes_and_atomics(gfla, shape):
     _assert_mode(c, 0)
     want = U.layer_reference(c)
     own = _layer(0, c)
-    old = gfla.set_tuning(46, 1)
-    try:
+    with gfla.tuned({gfla.TUNE_FC_SCATTER_ATOMICS: 1}):
         atom = _layer(0, c)
-    finally:
-        gfla.set_tuning(46, old)
     for n in NAMES:
         _same(atom[n], own[n], "%s %s: atomics vs owner-computes" % (shape, n))
         _same(atom[n], want[n].reshape(atom[n].shape), "%s %s: atomics vs float64" % (shape, n))

@@ -66,12 +66,9 @@ def test_winograd_half_on_ragged_shapes(gfla, k, B, C, H, W, is_source, wmode):
     if wmode == 4 or wmode == 5:
         _ragged(gfla, k, B, C, H, W, is_source, wmode)
         return
-    old = {key: gfla.set_tuning(key, 1) for key in ((52,) if wmode == 52 else (19, 43, 49, 52))}
-    try:
+    retired = (gfla.TUNE_RETIRED_19, gfla.TUNE_RETIRED_43, gfla.TUNE_RETIRED_49, gfla.TUNE_RETIRED_52)
+    with gfla.tuned({key: 1 for key in (retired[3:] if wmode == 52 else retired)}):
         got = _ragged(gfla, k, B, C, H, W, is_source, 5)
-    finally:
-        for key, value in old.items():
-            gfla.set_tuning(key, value)
     want = _ragged(gfla, k, B, C, H, W, is_source, 5)
     for a, b in zip(got, want):
         assert torch.equal(a, b)
@@ -213,11 +210,8 @@ def test_two_job_launch_equals_one_launch_per_half(gfla, k, B, C, H, W, mode):
         return logits, gs, gt, gw0
 
     merged = run()
-    old = gfla.set_tuning(21, 2)
-    try:
+    with gfla.tuned({gfla.TUNE_WINO_LAUNCH: 2}):
         separate = run()
-    finally:
-        gfla.set_tuning(21, old)
     for name, a, b in zip(("logits", "grad_source", "grad_target", "grad_w0"), merged, separate):
         if name in ("grad_source", "grad_w0"):  # behind the splat into the source map's gradient: float atomics, whose
             assert rel_err(a, b) < 1e-5, name   # order moves the last bits from run to run (1.2e-6 seen)
@@ -241,12 +235,9 @@ def test_winograd_domain_weight_gradient_forms(gfla, k, B, C, H, W, is_source, f
     w0 = (randn((128, 2 * C, k, k), seed=6) * 0.05).to(DEV)
     g = fc_mfma.geometry(H, W, k, is_source)
     dG = (randn((B, 128, g["Ho"], g["Wo"]), seed=7) * 1e-3).to(DEV)
-    old29 = gfla.set_tuning(29, {"winograd": 0, "winograd_units_of_16_tiles": 2, "winograd_single_row_units": 1}[form])
-    try:
+    with gfla.tuned({gfla.TUNE_WINO_WGRAD_UNITS: {"winograd": 0, "winograd_units_of_16_tiles": 2, "winograd_single_row_units": 1}[form]}):
         _, _, gw, _ = _run_half(B, C, H, W, k, is_source, 4, x, w0, dG)
         torch.cuda.synchronize()
-    finally:
-        gfla.set_tuning(29, old29)
     x64 = x.cpu().double()
     wh = (w0[:, C:] if is_source else w0[:, :C]).cpu().double().clone().requires_grad_()
     F.conv2d(F.pad(x64, _pads(k, is_source), mode="replicate"), wh).backward(dG.cpu().double())

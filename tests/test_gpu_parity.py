@@ -31,13 +31,10 @@ def tol(dtype, grad=False):
 @pytest.fixture(params=["lds", "global"], autouse=True)
 def kernel_variant(request, gfla):
     """Every test runs twice: default dispatch (planes in LDS where they fit) and with the
-    global-memory kernels forced (tuning keys 0,2,3,6 of include/gfla_hip.h)."""
+    global-memory kernels forced (include/gfla_hip.h: enum gfla_tuning_key)."""
     force = 1 if request.param == "global" else 0
-    for key in (0, 2, 3, 6, 7):
-        gfla.set_tuning(key, force)
-    yield request.param
-    for key in (0, 2, 3, 6, 7):
-        gfla.set_tuning(key, 0)
+    with gfla.tuned({key: force for key in (gfla.TUNE_BE_FWD, gfla.TUNE_BE_BWD, gfla.TUNE_AGG, gfla.TUNE_RS, gfla.TUNE_NO_WINDOWS)}):
+        yield request.param
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -832,11 +829,8 @@ def test_aggregate_forward_table_path(gfla, oracle, kernel_variant, shape, kind,
     ref = F.avg_pool2d(F.pixel_shuffle(a, k) * oracle.block_extractor_gather(s.double(), f.double(), k), k, k)
     sd, fd, ld = s.to(DEV), f.to(DEV), lg.to(DEV)
     out, attn = torch.empty_like(sd), torch.empty_like(ld)
-    gfla.set_tuning(8, 2)
-    try:
+    with gfla.tuned({gfla.TUNE_AGG_STREAM: 2}):
         _lib.aggregate_fwd(sd, fd, ld, out, attn, k, True)
-    finally:
-        gfla.set_tuning(8, 0)
     assert_close(attn.cpu(), a.float(), F32_FWD * 2, "attn")
     assert_close(out.cpu(), ref.float(), F32_FWD * 4, "out")
     if W % 2 == 0 and W >= k + 1:   # bf16 storage through the same kernels
@@ -844,11 +838,8 @@ def test_aggregate_forward_table_path(gfla, oracle, kernel_variant, shape, kind,
         ab = torch.softmax(lb.double(), 1)
         refb = F.avg_pool2d(F.pixel_shuffle(ab, k) * oracle.block_extractor_gather(sb.double(), fb.double(), k), k, k)
         ob, atb = torch.empty_like(sb, device=DEV), torch.empty_like(lb, device=DEV)
-        gfla.set_tuning(8, 2)
-        try:
+        with gfla.tuned({gfla.TUNE_AGG_STREAM: 2}):
             _lib.aggregate_fwd(sb.to(DEV), fb.to(DEV), lb.to(DEV), ob, atb, k, True)
-        finally:
-            gfla.set_tuning(8, 0)
         err = max_abs(ob.float().cpu(), refb.float()) / max(1e-30, refb.abs().max().item())
         assert err <= 2 ** -7, err
 
@@ -879,12 +870,9 @@ def test_aggregate_backward_stream_path(gfla, oracle, kernel_variant, shape, kin
     ref.backward(go.double())
     sd, fd, ad, god = s.to(DEV), f.to(DEV), a.detach().float().to(DEV).contiguous(), go.to(DEV)
     gl, gf = torch.zeros_like(ad), torch.zeros_like(fd)
-    gfla.set_tuning(8, 2)
-    try:
+    with gfla.tuned({gfla.TUNE_AGG_STREAM: 2}):
         _lib.call("gfla_local_attn_aggregate_bwd_f32", sd, _lib.ptr(sd), _lib.ptr(fd), _lib.ptr(ad), _lib.ptr(god), None,
                   _lib.ptr(gf), _lib.ptr(gl), B, C, H, W, H, W, k, 1)
-    finally:
-        gfla.set_tuning(8, 0)
     assert_close(gl.cpu(), l64.grad.float(), F32_GRAD, "grad_logits")
     if kind != "near_integer":   # at (near-)integer flows the bilinear kink makes autograd's one-sided choice arbitrary
         assert_close(gf.cpu(), f64.grad.float(), F32_GRAD * 4, "grad_flow")
@@ -936,9 +924,7 @@ def test_streaming_kernels_random_shapes_against_round1_kernels(gfla, kernel_var
         go = torch.randn(B, C, H, W, generator=g).to(DEV)
         res = {}
         for tag, key8 in (("old", 1), ("new", 2)):
-            gfla.set_tuning(8, key8)
-            gfla.set_tuning(22, 1 if tag == "old" else 0)
-            try:
+            with gfla.tuned({gfla.TUNE_AGG_STREAM: key8, gfla.TUNE_RS_BWD2_NO_STREAM: 1 if tag == "old" else 0}):
                 out, attn = torch.empty_like(src), torch.empty_like(lg)
                 _lib.aggregate_fwd(src, flow, lg, out, attn, k, True)
                 gl, gf = torch.zeros_like(attn), torch.zeros_like(flow)
@@ -949,9 +935,6 @@ def test_streaming_kernels_random_shapes_against_round1_kernels(gfla, kernel_var
                 _lib.call("gfla_resample2d_bwd_f32", src, _lib.ptr(src), _lib.ptr(i2), _lib.ptr(go), None, _lib.ptr(g2),
                           B, C, H, W, H, W, 4, 1, 0)
                 res[tag] = (out, attn, gl, gf, g2)
-            finally:
-                gfla.set_tuning(8, 0)
-                gfla.set_tuning(22, 0)
         for name, a, b in zip(("out", "attn", "grad_logits", "grad_flow", "grad_in2"), res["new"], res["old"]):
             scale_ = max(1e-30, b.abs().max().item())
             err = (a - b).abs().max().item() / scale_
@@ -1049,17 +1032,11 @@ def test_resample2d_input1_gradient_fixed_point_planes(gfla, kernel_variant, sha
         a, b = _rs_bwd_in1(gfla, i1, i2, go), _rs_bwd_in1(gfla, i1, i2, go)
         assert torch.equal(a, b), kind
         ws = _lib.scatter_workspace(i1, B, H, W, 16)
-        old = gfla.set_tuning(14, 1)   # key 14 = 1: never the matrix-core scatter -> the LDS kernel reading tap records
-        try:
+        with gfla.tuned({gfla.TUNE_PM: 1}):   # never the matrix-core scatter -> the LDS kernel reading tap records
             c = _rs_bwd_in1(gfla, i1, i2, go, ws)
-        finally:
-            gfla.set_tuning(14, old)
         assert torch.equal(a, c), kind
-        old = gfla.set_tuning(23, 1)
-        try:
+        with gfla.tuned({gfla.TUNE_RS_BWD1_PLANES: 1}):
             d = _rs_bwd_in1(gfla, i1, i2, go)
-        finally:
-            gfla.set_tuning(23, old)
         assert max_abs(a, d) <= 2e-6 * d.abs().max().item(), kind
 
 

@@ -25,12 +25,9 @@ COSINE_CASES = [(s, d) for s in L.COSINE_SHAPES for d in DTYPE_IDS] + [(s, d) fo
 
 def _cosine(gfla, case, dtype, split):
     src, tgt = case["src"].to(dtype).to(DEV), case["tgt"].to(dtype).to(DEV)
-    old = gfla.set_tuning(5, split)
-    try:
+    with gfla.tuned({gfla.TUNE_SPLIT: split}):
         best, index = gfla.max_cosine_similarity(src, tgt, return_index=True)
         torch.cuda.synchronize()
-    finally:
-        gfla.set_tuning(5, old)
     assert index.dtype == torch.int32
     return best.cpu(), index.cpu()
 

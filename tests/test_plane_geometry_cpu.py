@@ -374,28 +374,28 @@ def test_query_reports_the_forced_geometries_and_key_5_respects_allow_split(gfla
         assert g["G"] == 1 and g["ngroups"] == 8 and g["split"] == 1 and g["margin"] < 0, (op, g)
     g = q(0, (32, 256, 32, 22, 32, 22), 3)                          # a bench shape: the heuristic's own G, ragged
     assert g["G"] > 1 and 256 % g["G"] != 0 and g["ngroups"] == -(-256 // g["G"])
-    with pu.Tuning(gfla, {4: 3}):
+    with gfla.tuned({gfla.TUNE_G_CAP: 3}):
         for op in range(8):
             for elem in (2, 4, 8):
                 g = q(op, pu.SHAPES[0], 4 if op >= 5 else 3, elem=elem)
                 assert (g["G"], g["ngroups"]) == (3, 3), (op, elem, g)           # C = 7: groups of 3, 3, 1
-    with pu.Tuning(gfla, {5: 3}):
+    with gfla.tuned({gfla.TUNE_SPLIT: 3}):
         for op in range(8):
             for elem in (2, 4, 8):
                 g = q(op, pu.SHAPES[0], 4 if op >= 5 else 3, elem=elem)
                 want = 1 if (elem == 2 and op in OPS_BWD16_NO_SPLIT) else 3
                 assert g["split"] == want and g["per"] == -(-140 // want), (op, elem, g)
     # the two callers the issue names, once more by name: 16-bit block_extractor backward and resample2d d/d input1
-    with pu.Tuning(gfla, {5: 3}):
+    with gfla.tuned({gfla.TUNE_SPLIT: 3}):
         assert q(0, pu.SHAPES[3], 3, elem=2)["split"] == 1 and q(0, pu.SHAPES[3], 3, elem=4)["split"] == 3
         assert q(6, pu.SHAPES[3], 4, elem=2)["split"] == 1 and q(6, pu.SHAPES[3], 4, elem=4)["split"] == 3
         assert q(0, pu.SHAPES[3], 3, elem=4)["per"] == 703            # 2109 = 3 x 703 = 19 rows of 37: ends inside a flow row
     # key 10 = 16: 48 x 32 x 12 B > 16 KB.  With only 8 such planes the tile kernels of csrc/tile_map.h take the call first
     # (B C < 4 workgroups per CU: gfla_big_plane_geometry's regime), so the family reports G = 0; key 30 = 1 switches those
     # off and the same planes run as ROW WINDOWS
-    with pu.Tuning(gfla, {10: 16}):
+    with gfla.tuned({gfla.TUNE_LDS_KB: 16}):
         assert q(0, pu.SHAPES[2], 3, elem=4)["G"] == 0
-    with pu.Tuning(gfla, pu.WINDOWS):
+    with gfla.tuned(pu.WINDOWS):
         # block_extractor backward (12 B per element) at 48 x 32, resample2d d/d input1 (8 B) at 57 x 37; resample2d's gather
         # planes (4 B) fit 16 KB at every shape of the GPU file and stay whole
         for op, k, shape in ((0, 3, pu.SHAPES[2]), (0, 5, pu.SHAPES[2]), (0, 3, pu.SHAPES[3]), (6, 4, pu.SHAPES[3])):
@@ -421,9 +421,10 @@ def test_query_reports_the_forced_geometries_and_key_5_respects_allow_split(gfla
 
 
 def test_tuning_context_restores_keys_on_every_exit_path(gfla):
-    before = [gfla.set_tuning(key, 0) for key in (4, 5, 10)]
+    keys = (gfla.TUNE_G_CAP, gfla.TUNE_SPLIT, gfla.TUNE_LDS_KB)
+    before = [gfla.set_tuning(key, 0) for key in keys]
     assert before == [0, 0, 0]
     with pytest.raises(RuntimeError):
-        with pu.Tuning(gfla, {4: 2, 5: 3, 10: 16}):
+        with gfla.tuned(dict(zip(keys, (2, 3, 16)))):
             raise RuntimeError("a failing case")
-    assert [gfla.set_tuning(key, 0) for key in (4, 5, 10)] == [0, 0, 0]
+    assert [gfla.set_tuning(key, 0) for key in keys] == [0, 0, 0]

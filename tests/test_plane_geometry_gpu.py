@@ -20,14 +20,17 @@ the few planes of these shapes would go to the tile kernels of csrc/tile_map.h i
 import pytest
 import torch
 
+from global_flow_local_attention_amd import (TUNE_AGG, TUNE_BE_FWD, TUNE_BIG_PLANE, TUNE_G_CAP, TUNE_LDS_KB, TUNE_PM, TUNE_RS,
+                                             TUNE_RS_BWD1_PLANES, TUNE_RS_BWD2_NO_STREAM, TUNE_SPLIT)
 import plane_util as pu
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F32, F64, F16, BF16 = torch.float32, torch.float64, torch.float16, torch.bfloat16
 NAMES = {F32: "f32", F64: "f64", F16: "f16", BF16: "bf16"}
-GEOS_WIDE = [{}, {4: 2}, {4: 3}, {4: 2, 5: 2}, {4: 3, 5: 3}, dict(pu.WINDOWS), dict(list(pu.WINDOWS.items()) + [(4, 2)])]
-GEOS_HALF = [{}, {4: 2}, {4: 3}, dict(pu.WINDOWS)]       # never key 5: the 16-bit backward cannot split
+GEOS_WIDE = [{}, {TUNE_G_CAP: 2}, {TUNE_G_CAP: 3}, {TUNE_G_CAP: 2, TUNE_SPLIT: 2}, {TUNE_G_CAP: 3, TUNE_SPLIT: 3}, dict(pu.WINDOWS),
+             dict(list(pu.WINDOWS.items()) + [(TUNE_G_CAP, 2)])]
+GEOS_HALF = [{}, {TUNE_G_CAP: 2}, {TUNE_G_CAP: 3}, dict(pu.WINDOWS)]       # never key 5: the 16-bit backward cannot split
 CASES = [(dt, g) for dt in (F32, F64) for g in range(len(GEOS_WIDE))] + [(dt, g) for dt in (F16, BF16) for g in range(len(GEOS_HALF))]
 CASE_IDS = ["%s-geo%d" % (NAMES[dt], g) for dt, g in CASES]
 NO_SPLIT_16 = (0, 1, 2, 3, 6)          # query ops whose 16-bit kernels own their planes
@@ -154,22 +157,22 @@ def check_geometry(_lib, qop, shape, k, dil, dtype, keys, needs=3):
     g = pu.query(_lib, qop, shape, k, dil, elem, needs)
     half_owner = elem == 2 and qop in NO_SPLIT_16
     if g["G"] == 0:      # only under the forced budget, and only kernels that need whole planes: the factored / unfold forms
-        assert 10 in keys and (qop in (1, 2, 3, 4) or elem == 2), (qop, shape, keys, g)          # and 16-bit backwards
+        assert TUNE_LDS_KB in keys and (qop in (1, 2, 3, 4) or elem == 2), (qop, shape, keys, g)          # and 16-bit backwards
         return g
     if g["margin"] >= 0:             # row windows: only under the forced budget, never the 16-bit owner kernels
-        assert 10 in keys and not half_owner and g["lds"] <= 16 * 1024 and g["split"] > 1, (qop, shape, keys, g)
+        assert TUNE_LDS_KB in keys and not half_owner and g["lds"] <= 16 * 1024 and g["split"] > 1, (qop, shape, keys, g)
         return g
     per_channel = g["lds"] // g["G"]
-    budget = (16 if 10 in keys else 64) * 1024
+    budget = (16 if TUNE_LDS_KB in keys else 64) * 1024
     assert g["lds"] <= budget
-    if 4 in keys:
-        want = min(keys[4], C, budget // per_channel)
+    if TUNE_G_CAP in keys:
+        want = min(keys[TUNE_G_CAP], C, budget // per_channel)
         assert g["G"] == want and g["ngroups"] == -(-C // want), (qop, shape, keys, g)
         assert g["ragged"] == (C % want if C % want else 0)
     else:
         assert g["G"] == 1 and g["ngroups"] == C and g["ragged"] == 0, (qop, shape, keys, g)    # the heuristics at these sizes
-    if 5 in keys:
-        assert elem != 2 and g["split"] == keys[5] and g["per"] == -(-Hf * Wf // keys[5]), (qop, shape, keys, g)
+    if TUNE_SPLIT in keys:
+        assert elem != 2 and g["split"] == keys[TUNE_SPLIT] and g["per"] == -(-Hf * Wf // keys[TUNE_SPLIT]), (qop, shape, keys, g)
     else:
         assert g["split"] == (2 if Hf * Wf >= 2048 and not half_owner else 1), (qop, shape, keys, g)
     return g
@@ -190,8 +193,8 @@ def default_forward(gfla, key, run, kernel=None):
     the call to another kernel of the library: bit-identity is a property of one kernel over its geometries, so the result
     is then compared with that same kernel's at the default geometry."""
     def make():
-        with pu.Tuning(gfla, {4: 0, 5: 0, 10: 0, 30: 0}):
-            with pu.Tuning(gfla, kernel or {}):
+        with gfla.tuned({TUNE_G_CAP: 0, TUNE_SPLIT: 0, TUNE_LDS_KB: 0, TUNE_BIG_PLANE: 0}):
+            with gfla.tuned(kernel or {}):
                 out = run()
         return [o.detach().cpu() for o in (out if isinstance(out, tuple) else (out,))]
     return cached(("default", tuple(sorted((kernel or {}).items()))) + key, make)
@@ -203,7 +206,7 @@ def test_block_extractor_over_geometries(gfla, dtype, geo):
     from global_flow_local_attention_amd import _lib
     keys = geo_of(dtype, geo)
     rep = Report("block_extractor %s %s" % (NAMES[dtype], keys))
-    with pu.Tuning(gfla, keys):
+    with gfla.tuned(keys):
         for si, shape in enumerate(pu.SHAPES):
             for k in ((2, 3, 4, 5) if si == 0 else (3, 5)):
                 for kind in kinds_of(dtype):
@@ -217,7 +220,7 @@ def test_block_extractor_over_geometries(gfla, dtype, geo):
                     n_b, n_f = _lib.path_count(_lib.PATH_BE_BWD_LDS), _lib.path_count(_lib.PATH_BE_FWD_PIX)
                     out, (gs, gf) = grads(mod, (s, f), up, (0, 1))
                     assert _lib.path_count(_lib.PATH_BE_BWD_LDS) == n_b + 1, "backward left the planes-in-LDS family: " + tag
-                    if elem_of(dtype) >= 4 and 10 not in keys:
+                    if elem_of(dtype) >= 4 and TUNE_LDS_KB not in keys:
                         assert _lib.path_count(_lib.PATH_BE_FWD_PIX) == n_f + 1, "forward left the planes-in-LDS family: " + tag
                     rep.compare("out", out, c["ref"]["out"], c["P"], dtype, tag=tag)
                     rep.compare("g_source", gs, c["ref"]["g_source"], c["P"], dtype, tag=tag)
@@ -225,8 +228,9 @@ def test_block_extractor_over_geometries(gfla, dtype, geo):
                     # beyond the forced budget the padded planes of the lane-per-pixel / wave-per-row kernels do not fit and
                     # round 1's kernel (key 0 = 2) takes the forward, on row windows
                     other = elem_of(dtype) >= 4 and _lib.path_count(_lib.PATH_BE_FWD_PIX) == n_f
-                    assert not other or 10 in keys
-                    want = default_forward(gfla, ("be", shape, dtype, kind, k), lambda: mod(s.to(DEV), f.to(DEV)), {0: 2} if other else None)
+                    assert not other or TUNE_LDS_KB in keys
+                    want = default_forward(gfla, ("be", shape, dtype, kind, k), lambda: mod(s.to(DEV), f.to(DEV)),
+                                           {TUNE_BE_FWD: 2} if other else None)
                     rep.same_bits("out", out.detach().cpu(), want[0], tag)
                     if kind == "wild":      # each gradient alone: the NEED_SRC / NEED_FLOW instantiations
                         _, (gs1, _) = grads(mod, (s, f), up, (0,))
@@ -236,9 +240,10 @@ def test_block_extractor_over_geometries(gfla, dtype, geo):
                         assert _lib.path_count(_lib.PATH_BE_BWD_LDS) == n_b + 3
                     if si < 2 and kind == "wild":    # the forward kernels behind key 0
                         for variant in (2, 3, 4):
-                            with pu.Tuning(gfla, {0: variant}):
+                            with gfla.tuned({TUNE_BE_FWD: variant}):
                                 got = mod(s.to(DEV), f.to(DEV))
-                                ref0 = default_forward(gfla, ("be", shape, dtype, kind, k), lambda: mod(s.to(DEV), f.to(DEV)), {0: variant})
+                                ref0 = default_forward(gfla, ("be", shape, dtype, kind, k), lambda: mod(s.to(DEV), f.to(DEV)),
+                                                       {TUNE_BE_FWD: variant})
                             rep.compare("out", got, c["ref"]["out"], c["P"], dtype, tag=tag + " key0=%d" % variant)
                             rep.same_bits("out", got.cpu(), ref0[0], tag + " key0=%d" % variant)
     rep.finish()
@@ -251,7 +256,7 @@ def test_block_extractor_unfold_over_geometries(gfla, dtype, geo):
     from global_flow_local_attention_amd import extractor_attn as ea
     keys = geo_of(dtype, geo)
     rep = Report("unfold %s %s" % (NAMES[dtype], keys))
-    with pu.Tuning(gfla, keys):
+    with gfla.tuned(keys):
         for shape in pu.SHAPES:
             B, C, Hs, Ws, Hf, Wf = shape
             for k in (3, 5):
@@ -265,7 +270,7 @@ def test_block_extractor_unfold_over_geometries(gfla, dtype, geo):
                     if check_geometry(_lib, 4, shape, k, 1, dtype, keys)["G"] == 0:
                         continue
                     backward = bool(_lib.lib().gfla_unfold_supported(Hs, Ws, k, elem_of(dtype)))
-                    assert backward or 10 in keys
+                    assert backward or TUNE_LDS_KB in keys
                     if backward:
                         assert check_geometry(_lib, 2, shape, k, 1, dtype, keys)["margin"] < 0
                         out, (gs, gf) = grads(fn, (s, f), up, (0, 1))
@@ -291,7 +296,7 @@ def test_softmax_aggregate_over_geometries(gfla, dtype, geo):
     from global_flow_local_attention_amd import extractor_attn as ea
     keys = geo_of(dtype, geo)
     rep = Report("aggregate %s %s" % (NAMES[dtype], keys))
-    with pu.Tuning(gfla, keys):
+    with gfla.tuned(keys):
         for shape in pu.SHAPES:
             B, C, Hs, Ws, Hf, Wf = shape
             for k in (3, 5):
@@ -301,9 +306,9 @@ def test_softmax_aggregate_over_geometries(gfla, dtype, geo):
                     tag = "%s k%d %s" % (shape, k, kind)
                     fn = lambda a, b, l: ea.LocalAttnAggregateFunction.apply(a, b, l, k, True)
                     # float64 planes of 57 x 37 are beyond the forced 16 KB: the global-memory kernels (key 3 = 1) take the call
-                    beyond = 10 in keys and Hs * Ws * max(4, elem_of(dtype)) > 16 * 1024
+                    beyond = TUNE_LDS_KB in keys and Hs * Ws * max(4, elem_of(dtype)) > 16 * 1024
                     want = default_forward(gfla, ("agg", shape, dtype, kind, k), lambda: fn(s.to(DEV), f.to(DEV), lg.to(DEV)),
-                                           {3: 1} if beyond else None)
+                                           {TUNE_AGG: 1} if beyond else None)
                     # the gradients are evaluated with the attention map the forward stored (the backward kernels read it)
                     bwd = cached(("agg bwd", shape, dtype, kind, k), lambda: pu.aggregate_backward(s, f, want[1], up, k))
                     g = check_geometry(_lib, 1, shape, k, 1, dtype, keys)
@@ -332,7 +337,7 @@ def test_resample2d_over_geometries(gfla, dtype, geo):
     from global_flow_local_attention_amd import _lib
     keys = geo_of(dtype, geo)
     rep = Report("resample2d %s %s" % (NAMES[dtype], keys))
-    with pu.Tuning(gfla, keys):
+    with gfla.tuned(keys):
         for shape in pu.SHAPES:
             for k, dil in ((4, 1), (2, 1), (4, 2)):
                 for kind in kinds_of(dtype):
@@ -420,7 +425,7 @@ def test_resample2d_sigma_field_over_geometries(gfla, dtype, geo):
     from global_flow_local_attention_amd import _lib
     keys = geo_of(dtype, geo)
     rep = Report("resample2d sigma field %s %s" % (NAMES[dtype], keys))
-    with pu.Tuning(gfla, keys):
+    with gfla.tuned(keys):
         for si, shape in enumerate(pu.SHAPES):
             for ki, (k, dil) in enumerate(RS_FIELD_KD):
                 fn = lambda a, b: gfla.Resample2dFunction.apply(a, b, k, dil)
@@ -449,12 +454,12 @@ def test_resample2d_sigma_field_over_geometries(gfla, dtype, geo):
 
 # the routes the geometry keys do not select (csrc/gs_route.h: rs_fwd_route / rs_bwd_route; key 14: csrc/patch_mfma.hip)
 ROUTES = [({}, (F32, F64, F16, BF16)),     # coefficient table + fixed point, streaming d/d input2, the product where it pays
-          ({23: 1}, (F32,)),               # double planes, no table
-          ({23: 2}, (F32,)),               # fixed point without the table
-          ({22: 1}, (F32, F16, BF16)),     # rs_lds_kernel gathers d/d input2 instead of the streaming kernel
-          ({14: 1}, (F32,)),               # matrix-core product off
-          ({14: 2}, (F32,)),               # ... wherever the shape is supported
-          ({6: 1}, (F32, F64))]            # global kernels (16-bit storage ignores the key)
+          ({TUNE_RS_BWD1_PLANES: 1}, (F32,)),               # double planes, no table
+          ({TUNE_RS_BWD1_PLANES: 2}, (F32,)),               # fixed point without the table
+          ({TUNE_RS_BWD2_NO_STREAM: 1}, (F32, F16, BF16)),  # rs_lds_kernel gathers d/d input2 instead of the streaming kernel
+          ({TUNE_PM: 1}, (F32,)),                           # matrix-core product off
+          ({TUNE_PM: 2}, (F32,)),                           # ... wherever the shape is supported
+          ({TUNE_RS: 1}, (F32, F64))]                       # global kernels (16-bit storage ignores the key)
 ROUTE_CASES = [(keys, dt) for keys, dts in ROUTES for dt in dts]
 ROUTE_IDS = ["%s-%s" % (",".join("%d=%d" % kv for kv in sorted(keys.items())) or "default", NAMES[dt]) for keys, dt in ROUTE_CASES]
 
@@ -469,9 +474,9 @@ def test_resample2d_sigma_field_over_routes(gfla, keys, dtype):
     import gs_route_util
     from global_flow_local_attention_amd import _lib
     rep = Report("resample2d sigma field routes %s %s" % (NAMES[dtype], keys))
-    is_global = keys.get(6) == 1 and dtype in (F32, F64)
+    is_global = keys.get(TUNE_RS) == 1 and dtype in (F32, F64)
     big = [_lib.path_count(i) for i in (15, 16, 17)]
-    with pu.Tuning(gfla, keys):
+    with gfla.tuned(keys):
         for shape in (pu.SHAPES[0], pu.SHAPES[1], gs_route_util.S):
             for k, dil in ((4, 1), (4, 2), (2, 1)):
                 fn = lambda a, b: gfla.Resample2dFunction.apply(a, b, k, dil)
@@ -499,7 +504,7 @@ def test_resample2d_sigma_field_through_the_widened_16_bit_backward(gfla):
     shape, dtype, k, dil = gs_route_util.W, BF16, 4, 1
     B, C, Hi, Wi, H, W = shape
     rep = Report("resample2d sigma field widened bf16")
-    with pu.Tuning(gfla, {10: 16}):
+    with gfla.tuned({TUNE_LDS_KB: 16}):
         for field in pu.SIGMA_FIELDS:
             c = rs_sigma_case(shape, dtype, "wild", k, dil, field)
             (a, b), g = device_leaves(c, ())
@@ -530,9 +535,9 @@ def test_float32_forwards_on_row_windows(gfla):
             mod = gfla.BlockExtractor(k)
             for variant in (0, 2):     # by default dispatch and forced: under this budget both are round 1's kernel (key 0 = 2)
                 tag = "%s k%d %s key0=%d" % (shape, k, kind, variant)
-                want = default_forward(gfla, ("be", shape, dtype, kind, k), lambda: mod(s.to(DEV), f.to(DEV)), {0: 2})
+                want = default_forward(gfla, ("be", shape, dtype, kind, k), lambda: mod(s.to(DEV), f.to(DEV)), {TUNE_BE_FWD: 2})
                 n_f = _lib.path_count(_lib.PATH_BE_FWD_PIX)
-                with pu.Tuning(gfla, dict(list(pu.WINDOWS.items()) + [(0, variant)])):
+                with gfla.tuned(dict(list(pu.WINDOWS.items()) + [(TUNE_BE_FWD, variant)])):
                     got = mod(s.to(DEV), f.to(DEV))
                 assert _lib.path_count(_lib.PATH_BE_FWD_PIX) == n_f
                 rep.compare("out", got, c["ref"]["out"], c["P"], dtype, tag=tag)
@@ -543,7 +548,7 @@ def test_float32_forwards_on_row_windows(gfla):
             mod = gfla.Resample2d(k, dil, sigma=pu.SIGMA)
             tag = "%s k%d d%d %s" % (shape, k, dil, kind)
             want = default_forward(gfla, ("rs", shape, dtype, kind, k, dil), lambda: mod(s.to(DEV), f.to(DEV)))
-            with pu.Tuning(gfla, pu.WINDOWS):
+            with gfla.tuned(pu.WINDOWS):
                 g = pu.query(_lib, 5, shape, k, dil, 4)
                 assert g["G"] >= 1 and g["margin"] >= 0 and g["split"] > 1, g
                 got = mod(s.to(DEV), f.to(DEV))
@@ -561,7 +566,7 @@ def test_case_table_reaches_every_geometry(gfla):
     seen = set()
     for dtype, geo in CASES:
         keys = geo_of(dtype, geo)
-        with pu.Tuning(gfla, keys):
+        with gfla.tuned(keys):
             for shape in pu.SHAPES:
                 for qop, k, dil, direction in ((0, 3, 1, "bwd"), (2, 3, 1, "bwd"), (1, 5, 1, "bwd"), (6, 4, 2, "bwd"), (7, 4, 2, "bwd"),
                                                (4, 3, 1, "fwd"), (5, 4, 1, "fwd")):
@@ -576,5 +581,5 @@ def test_case_table_reaches_every_geometry(gfla):
             for what in ("G1", "G2", "G3", "split1"):
                 assert (half, direction, what, True) in seen, (half, direction, what)
     assert ("f32", "bwd", "window", True) in seen and ("f64", "bwd", "window", True) in seen and ("f64", "fwd", "window", True) in seen
-    with pu.Tuning(gfla, pu.WINDOWS):       # float32 forward windows: test_float32_forwards_on_row_windows
+    with gfla.tuned(pu.WINDOWS):       # float32 forward windows: test_float32_forwards_on_row_windows
         assert pu.query(_lib, 5, pu.WINDOW_FWD_SHAPE, 4, 1, 4)["margin"] >= 0

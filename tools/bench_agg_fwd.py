@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Local-attention forward (softmax + aggregate) at the attention-layer shapes: the paired-read kernel
-(agg_fwd_pk_kernel, default) next to round 1's ds_read_b32 kernel (tuning key 8 = 1), HIP-event timed, with the
+(agg_fwd_pk_kernel, default) next to round 1's ds_read_b32 kernel (tuning key 8, TUNE_AGG_STREAM, = 1), HIP-event timed, with the
 fraction of the HBM roofline (algorithmic bytes / time / 8 TB/s) and the max abs difference between the two.
 
     python tools/bench_agg_fwd.py [--iters 20] [--flows smooth,coherent,wild] [--g 0,4,8] [--face]
---g: channels per workgroup to try (tuning key 4; 0 = the library's choice)."""
+--g: channels per workgroup to try (tuning key 4, TUNE_G_CAP; 0 = the library's choice)."""
 import argparse
 import json
 import os
@@ -27,22 +27,19 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--flows", default="smooth,coherent,wild")
     ap.add_argument("--g", default="0")
-    ap.add_argument("--pitch", type=int, default=0, help="tuning key 17: LDS row-pair pitch in words (experiment)")
+    ap.add_argument("--pitch", type=int, default=0, help="TUNE_AGG_STREAM_PITCH: LDS row-pair pitch in words (experiment)")
     ap.add_argument("--wide-tail", type=int, default=0)
-    ap.add_argument("--dbg", type=int, default=0)
-    ap.add_argument("--ns", type=int, default=0, help="tuning key 5: channel ranges per sample")
-    ap.add_argument("--tile", type=int, default=0, help="tuning key 16: tile width 8 / 16 / 32 (0 = library choice)")
-    ap.add_argument("--threads", type=int, default=0, help="tuning key 9: workgroup size cap of the paired-read kernel")
+    ap.add_argument("--ns", type=int, default=0, help="TUNE_SPLIT: channel ranges per sample")
+    ap.add_argument("--tile", type=int, default=0, help="TUNE_AGG_STREAM_TILE_W: tile width 8 / 16 / 32 (0 = library choice)")
+    ap.add_argument("--threads", type=int, default=0, help="TUNE_AGG_STREAM_THREADS: workgroup size cap of the paired-read kernel")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--face", action="store_true", help="256x256 image shapes instead of 256x176")
     ap.add_argument("--dtype", default="f32", choices=("f32", "bf16"))
     args = ap.parse_args()
-    lib = _lib.lib()
-    lib.gfla_set_tuning(9, args.threads)
-    lib.gfla_set_tuning(17, args.pitch)
-    lib.gfla_set_tuning(16, args.tile)
-    lib.gfla_set_tuning(5, args.ns)
-    lib.gfla_set_tuning(18, args.dbg)
+    _lib.set_tuning(_lib.TUNE_AGG_STREAM_THREADS, args.threads)
+    _lib.set_tuning(_lib.TUNE_AGG_STREAM_PITCH, args.pitch)
+    _lib.set_tuning(_lib.TUNE_AGG_STREAM_TILE_W, args.tile)
+    _lib.set_tuning(_lib.TUNE_SPLIT, args.ns)
     B = args.batch
     shapes = (("attn2", 128, 64, 64 if args.face else 44, 5), ("attn3", 256, 32, 32 if args.face else 22, 3))
     dt = torch.float32 if args.dtype == "f32" else torch.bfloat16
@@ -58,21 +55,19 @@ def main():
             def run():
                 _lib.aggregate_fwd(src, flow, logits, out, attn, k, True)
             row = {"op": "local-attn forward", "shape": name, "dims": [B, C, H, W, k], "flow": kind, "alg_MB": round(nbytes / 1e6, 1)}
-            lib.gfla_set_tuning(8, 1)
-            us = time_fn(run, args.iters)
-            ref_out, ref_attn = out.clone(), attn.clone()
+            with _lib.tuned({_lib.TUNE_AGG_STREAM: 1}):
+                us = time_fn(run, args.iters)
+                ref_out, ref_attn = out.clone(), attn.clone()
             row["b32_kernel_us"] = round(us, 1)
             row["b32_frac_hbm"] = round(nbytes / us / 1e6 / 8, 3)
-            lib.gfla_set_tuning(8, 0)
             for g in args.g.split(","):
-                lib.gfla_set_tuning(4, int(g))
-                us = time_fn(run, args.iters)
+                with _lib.tuned({_lib.TUNE_G_CAP: int(g)}):
+                    us = time_fn(run, args.iters)
                 tag = "pk_G%s" % g if int(g) else "pk"
                 row[tag + "_us"] = round(us, 1)
                 row[tag + "_frac_hbm"] = round(nbytes / us / 1e6 / 8, 3)
                 row[tag + "_maxdiff"] = float((out.float() - ref_out.float()).abs().max())
                 row[tag + "_attn_equal"] = bool(torch.equal(attn, ref_attn))
-            lib.gfla_set_tuning(4, 0)
             print(json.dumps(row), flush=True)
 
 

@@ -16,7 +16,7 @@ from global_flow_local_attention_amd import _lib  # noqa: E402
 DEV = torch.device("cuda", 0)
 torch.cuda.set_device(0)
 B, C, H, k = 32, 128, 64, 5
-VARIANTS = [("quad (round 1)", {0: 2}), ("wrow", {0: 4}), ("pix direct", {0: 3}), ("auto", {})]
+VARIANTS = [("quad (round 1)", {gfla.TUNE_BE_FWD: 2}), ("wrow", {gfla.TUNE_BE_FWD: 4}), ("pix direct", {gfla.TUNE_BE_FWD: 3}), ("auto", {})]
 stream = torch.cuda.current_stream(DEV)
 for W in (32, 40, 44, 48, 52, 56, 60, 64, 72, 80, 96):
     gen = torch.Generator(device=DEV).manual_seed(3)
@@ -26,19 +26,16 @@ for W in (32, 40, 44, 48, 52, 56, 60, 64, 72, 80, 96):
     nbytes = 4 * (B * C * H * W + 2 * B * H * W + B * C * k * k * H * W)
     row = {"W": W, "row_bytes": 4 * k * W, "alg_MB": round(nbytes / 1e6, 1)}
     for name, keys in VARIANTS:
-        for kk, v in keys.items():
-            gfla.set_tuning(kk, v)
         fn = lambda: _lib.call("gfla_block_extractor_fwd_f32", src, _lib.ptr(src), _lib.ptr(flow), _lib.ptr(out), B, C, H, W, H, W, k)
-        for _ in range(3):
-            fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(10):
-            fn()
-        e1.record(stream)
-        torch.cuda.synchronize()
+        with gfla.tuned(keys):
+            for _ in range(3):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(10):
+                fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
         us = e0.elapsed_time(e1) / 10 * 1e3
-        for kk in keys:
-            gfla.set_tuning(kk, 0)
         row[name] = {"us": round(us, 1), "TBps": round(nbytes / us / 1e6, 2)}
     print(json.dumps(row), flush=True)

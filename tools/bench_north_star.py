@@ -23,6 +23,7 @@ import global_flow_local_attention_amd as gfla  # noqa: E402
 from global_flow_local_attention_amd import _lib  # noqa: E402
 
 DEV = torch.device("cuda", 0)
+FWD = gfla.TUNE_BE_FWD
 
 
 def be_check(layers, B):
@@ -34,11 +35,10 @@ def be_check(layers, B):
         flow = bench.smooth_flow(B, H, W, DEV, gen)
         outs = []
         for key0 in (2, 0):
-            gfla.set_tuning(0, key0)
             o = torch.empty(B, C, k * H, k * W, device=DEV)
-            _lib.call("gfla_block_extractor_fwd_f32", src, _lib.ptr(src), _lib.ptr(flow), _lib.ptr(o), B, C, H, W, H, W, k)
+            with gfla.tuned({gfla.TUNE_BE_FWD: key0}):
+                _lib.call("gfla_block_extractor_fwd_f32", src, _lib.ptr(src), _lib.ptr(flow), _lib.ptr(o), B, C, H, W, H, W, k)
             outs.append(o)
-        gfla.set_tuning(0, 0)
         res[name] = float((outs[0] - outs[1]).abs().max())
     return res
 
@@ -56,11 +56,8 @@ def main():
     B = args.batch
 
     def run(tag, keys):
-        for kk, v in keys.items():
-            gfla.set_tuning(kk, v)
-        r = bench.op_roofline(DEV, B=B, iters=args.iters, layers=layers, flow_kind=args.flow)
-        for kk in keys:
-            gfla.set_tuning(kk, 0)
+        with gfla.tuned(keys):
+            r = bench.op_roofline(DEV, B=B, iters=args.iters, layers=layers, flow_kind=args.flow)
         line = {"tag": tag, "keys": {str(a): b for a, b in keys.items()}}
         for name, d in r["layers"].items():
             line[name] = {"be_us": d["block_extractor_fwd"]["us"], "be_frac": d["block_extractor_fwd"]["frac"],
@@ -69,33 +66,33 @@ def main():
         print(json.dumps(line), flush=True)
 
     print(json.dumps({"check_max_abs_vs_round1_kernel": be_check(layers, B)}), flush=True)
-    run("round-1 kernel (lane = output quad)", {0: 2})
+    run("round-1 kernel (lane = output quad)", {FWD: 2})
     run("default", {})
     if args.sweep == "be":
-        run("pix direct stores (key 0 = 3)", {0: 3})
-        run("wave-per-flow-row (key 0 = 4)", {0: 4})
+        run("pix direct stores (key 0 = 3)", {FWD: 3})
+        run("wave-per-flow-row (key 0 = 4)", {FWD: 4})
         for G in (1, 2, 3, 4, 8):
             for thr in (256, 384, 512, 704, 1024):
-                run("wrow G=%d threads=%d" % (G, thr), {0: 4, 4: G, 24: thr})
+                run("wrow G=%d threads=%d" % (G, thr), {FWD: 4, gfla.TUNE_G_CAP: G, gfla.TUNE_BE_FWD_THREADS: thr})
         for kb in (52, 64, 100, 150):
-            run("wrow LDS budget %d KB" % kb, {0: 4, 10: kb})
-            run("wrow LDS budget %d KB threads=1024" % kb, {0: 4, 10: kb, 24: 1024})
+            run("wrow LDS budget %d KB" % kb, {FWD: 4, gfla.TUNE_LDS_KB: kb})
+            run("wrow LDS budget %d KB threads=1024" % kb, {FWD: 4, gfla.TUNE_LDS_KB: kb, gfla.TUNE_BE_FWD_THREADS: 1024})
     if args.sweep == "agg":   # softmax + aggregate forward: workgroup size, planes per chunk, channel ranges, tile width
         for thr in (768, 704, 512, 384, 256):
             for ch in (0, 2):
                 for ns in (0, 1, 2, 4, 8):
-                    run("agg threads=%d CH=%d ranges=%d" % (thr, ch, ns), {9: thr, 4: ch, 5: ns})
+                    run("agg threads=%d CH=%d ranges=%d" % (thr, ch, ns), {gfla.TUNE_AGG_STREAM_THREADS: thr, gfla.TUNE_G_CAP: ch, gfla.TUNE_SPLIT: ns})
         for tw in (8, 16, 32):
-            run("agg tile width %d" % tw, {16: tw})
-            run("agg tile width %d threads=384" % tw, {16: tw, 9: 384})
-        run("agg k=3 on the record/stream path (key 8 = 2)", {8: 2})
+            run("agg tile width %d" % tw, {gfla.TUNE_AGG_STREAM_TILE_W: tw})
+            run("agg tile width %d threads=384" % tw, {gfla.TUNE_AGG_STREAM_TILE_W: tw, gfla.TUNE_AGG_STREAM_THREADS: 384})
+        run("agg k=3 on the record/stream path (key 8 = 2)", {gfla.TUNE_AGG_STREAM: 2})
         for thr in (384, 512, 704):
-            run("agg k=3 stream path threads=%d" % thr, {8: 2, 9: thr})
+            run("agg k=3 stream path threads=%d" % thr, {gfla.TUNE_AGG_STREAM: 2, gfla.TUNE_AGG_STREAM_THREADS: thr})
     if args.sweep == "abl":   # needs a `make PROBES=1` library
         for abl in (0, 1, 2, 3):
-            run("wave-per-flow-row, ablation %d (1 = no patch reads, 2 = no stores)" % abl, {0: 4, 27: abl})
+            run("wave-per-flow-row, ablation %d (1 = no patch reads, 2 = no stores)" % abl, {FWD: 4, gfla.TUNE_BE_FWD_PROBE: abl})
         for abl in (0, 2):
-            run("pix direct, ablation %d" % abl, {0: 3, 27: abl})
+            run("pix direct, ablation %d" % abl, {FWD: 3, gfla.TUNE_BE_FWD_PROBE: abl})
 
 
 if __name__ == "__main__":

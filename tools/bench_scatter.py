@@ -2,7 +2,7 @@
 """Matrix-core scatter paths (csrc/patch_mfma.hip) vs the LDS-atomic kernels at the bench shapes, HIP-event timed.
 
     python tools/bench_scatter.py [--iters 20] [--rows 0,1,2,3,4] [--flows smooth,coherent,wild]
-Band height R = tuning key 13 (0 = the library's choice)."""
+Band height R = tuning key 13, TUNE_PM_BAND_ROWS (0 = the library's choice)."""
 import argparse
 import json
 import os
@@ -28,8 +28,7 @@ def main():
     ap.add_argument("--tuning", default="", help="key=value,... applied before anything runs")
     args = ap.parse_args()
     for kv in filter(None, args.tuning.split(",")):
-        _lib.lib().gfla_set_tuning(int(kv.split("=")[0]), int(kv.split("=")[1]))
-    lib = _lib.lib()
+        _lib.set_tuning(int(kv.split("=")[0]), int(kv.split("=")[1]))
     B = 32
     for kind in args.flows.split(","):
         for (name, C, H, W, k) in (("attn2", 128, 64, 44, 5), ("attn3", 256, 32, 22, 3)):
@@ -47,12 +46,9 @@ def main():
             row = {"op": "aggregate d/d source", "shape": name, "flow": kind, "lds_atomic_us": round(time_fn(lambda: run(None), args.iters), 1)}
             row["adaptive_us"] = round(time_fn(lambda: run(ws), args.iters), 1)
             torch.cuda.synchronize()
-            lib.gfla_set_tuning(15, 100000)  # always the matrix-core path
-            for r in args.rows.split(","):
-                lib.gfla_set_tuning(13, int(r))
-                row["mfma_R%s_us" % r] = round(time_fn(lambda: run(ws), args.iters), 1)
-            lib.gfla_set_tuning(13, 0)
-            lib.gfla_set_tuning(15, 0)
+            for r in args.rows.split(","):   # always the matrix-core path
+                with _lib.tuned({_lib.TUNE_PM_LIMIT_ROWS: 100000, _lib.TUNE_PM_BAND_ROWS: int(r)}):
+                    row["mfma_R%s_us" % r] = round(time_fn(lambda: run(ws), args.iters), 1)
             print(json.dumps(row), flush=True)
         for (name, C, H, W) in (("relu3_1", 256, 64, 44), ("relu4_1", 512, 32, 22)):
             i1 = torch.randn(B, C, H, W, device=DEV)
@@ -70,23 +66,19 @@ def main():
             run(None)
             g_fix = g1.clone()
             row = {"op": "resample2d d/d input1", "shape": name, "flow": kind, "lds_atomic_us": round(time_fn(lambda: run(None), args.iters), 1)}
-            lib.gfla_set_tuning(23, 1)      # round 1's double planes instead of the fixed-point ones
-            g1.zero_()
-            run(None)
-            row["fix_vs_f64_maxdiff"] = float((g1 - g_fix).abs().max() / g1.abs().max())
-            row["lds_atomic_f64_us"] = round(time_fn(lambda: run(None), args.iters), 1)
-            lib.gfla_set_tuning(23, 0)
+            with _lib.tuned({_lib.TUNE_RS_BWD1_PLANES: 1}):      # round 1's double planes instead of the fixed-point ones
+                g1.zero_()
+                run(None)
+                row["fix_vs_f64_maxdiff"] = float((g1 - g_fix).abs().max() / g1.abs().max())
+                row["lds_atomic_f64_us"] = round(time_fn(lambda: run(None), args.iters), 1)
             g1.zero_()
             run(ws)
             row["ws_vs_nows_maxdiff"] = float((g1 - g_fix).abs().max() / g_fix.abs().max())
             row["adaptive_us"] = round(time_fn(lambda: run(ws), args.iters), 1)
             torch.cuda.synchronize()
-            lib.gfla_set_tuning(15, 100000)
             for r in args.rows.split(","):
-                lib.gfla_set_tuning(13, int(r))
-                row["mfma_R%s_us" % r] = round(time_fn(lambda: run(ws), args.iters), 1)
-            lib.gfla_set_tuning(13, 0)
-            lib.gfla_set_tuning(15, 0)
+                with _lib.tuned({_lib.TUNE_PM_LIMIT_ROWS: 100000, _lib.TUNE_PM_BAND_ROWS: int(r)}):
+                    row["mfma_R%s_us" % r] = round(time_fn(lambda: run(ws), args.iters), 1)
             print(json.dumps(row), flush=True)
 
 

@@ -21,7 +21,7 @@ _lib.call("gfla_fc_forward_f32", s, p(s), p(t), p(f), p(w0), None, p(w1), None, 
 _lib.call("gfla_fc_backward_f32", s, p(ws), p(f), p(w1), p(gl), p(sc), p(gs), p(gt), p(gf), p(gw0), None, None, None, B, C, H, W, k, 0.1, mode, 0)
 stamps = torch.zeros(4096, 8, 6, dtype=torch.int64, device=DEV)
 _lib.lib().gfla_fc_wino_debug_buffer(p(stamps))
-_lib.set_tuning(20, 16)
+_lib.set_tuning(_lib.TUNE_WINO_PROBE, 16)
 for which in (0,):
     for _ in range(2):
         stamps.zero_()
@@ -36,5 +36,5 @@ for which in (0,):
         m = sel.mean((0, 1))
         print("  waves xh=%d (first half = %s): prologue %.0f  first %.0f/step  second %.0f/step  barrier wait %.0f/step  epilogue %.0f   total %.0f" %
               (xh, "multiply" if xh == 0 else "transform", m[0], m[1] / 16, m[2] / 16, m[3] / 16, m[4], m[0] + m[1] + m[2] + m[3] + m[4]))
-_lib.set_tuning(20, 0)
+_lib.set_tuning(_lib.TUNE_WINO_PROBE, 0)
 _lib.lib().gfla_fc_wino_debug_buffer(None)
