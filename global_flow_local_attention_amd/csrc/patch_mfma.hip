@@ -45,6 +45,7 @@ constexpr int kPmSub = 8;       // threads sharing the entries of one pixel
 constexpr int kPmChannels = 128;  // channels per workgroup
 constexpr int kPmMaxNB = 6;     // 32-column blocks of a band (<= 192 source positions)
 constexpr int kPmGPitch = 33;   // floats; LDS pitch of a channel row of the G tile (odd: conflict-free column reads)
+constexpr int kPmEntrySlots = 40;  // entries the scatter kernel reads per pixel: 8 threads x ceil(36 / 8)
 
 struct PmLayout {
   int64_t ntiles, table_bytes, rows_bytes, total;  // the last 256 bytes of the workspace hold the dispatch statistic
@@ -52,7 +53,9 @@ struct PmLayout {
 static PmLayout pm_layout(int64_t B, int64_t HW, int entries) {
   PmLayout L;
   L.ntiles = ceil_div(HW, kPmTile);
-  L.table_bytes = ((B * L.ntiles * kPmTile * entries * (int64_t)sizeof(PatchEntry)) + 255) & ~(int64_t)255;
+  // + kPmEntrySlots entries of slack: the scatter kernel reads kPmEntrySlots entries per pixel whatever `entries` is
+  // (pm_fetch_entries), so behind the last pixel it reads up to that many past the table proper
+  L.table_bytes = (((B * L.ntiles * kPmTile * entries + kPmEntrySlots) * (int64_t)sizeof(PatchEntry)) + 255) & ~(int64_t)255;
   L.rows_bytes = ((B * L.ntiles * (int64_t)sizeof(int2)) + 255) & ~(int64_t)255;
   L.total = L.table_bytes + L.rows_bytes + 256;
   return L;
@@ -375,49 +378,107 @@ __global__ __launch_bounds__(256) void rs_patch_table_kernel(const float *__rest
 // dS[b, c, band rows] (+)= sum over the tiles reaching the band of G[b, c, tile pixels] * W[tile pixels -> band]
 // grid (bands, B, ceil(C / 128)); 256 threads = 4 waves, wave w owns channels 32w..32w+31 of the slice.
 constexpr int kPmMaxEntriesPerThread = 5;  // ceil(36 / 8)
+constexpr int kPmListBatch = 4;            // 64-tile groups of row ranges requested together while the tile list is built
 
 typedef float pm_f32x4 __attribute__((ext_vector_type(4)));
 
-// global -> registers for one tile: this thread's 16 pixels of one channel of G and its patch-table entries
-__device__ __forceinline__ void pm_fetch(pm_f32x4 (&gv)[4], int (&peq)[kPmMaxEntriesPerThread],
-                                         float (&pev)[kPmMaxEntriesPerThread], int tile, const float *g_row, bool g_ok,
-                                         bool g_vec, int gh, int HW, const PatchEntry *tab, int sub, int E) {
+// The prefetch of a tile, global -> registers.  Both halves are BRANCH-FREE: every address lies inside its tensor and the
+// masks (channel beyond C, pixel beyond HW, entry beyond E) are applied where the values are USED.  A load inside a
+// conditional block makes the compiler end the block with s_waitcnt vmcnt(0) and copy the results into the loop-carried
+// registers: the "prefetch" then waited a full round trip in front of the MFMAs it was meant to fly behind.
+//
+// This thread's 16 pixels of one channel of G.  g_chan = the channel's plane (channel clamped to the last one of the
+// tensor).  VEC: HW % 4 == 0 and G is 16-byte aligned, so a group of four pixels lies inside the plane or wholly past it.
+template <bool VEC>
+__device__ __forceinline__ void pm_fetch_g(pm_f32x4 (&gv)[4], int tile, const float *g_chan, int gh, int HW) {
   const int pbase = tile * kPmTile + gh * 16;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int p = pbase + 4 * q;
-    pm_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (g_ok) {
-      const float *src = g_row + (int64_t)tile * kPmTile + 4 * q;
-      if (g_vec && p + 3 < HW) {
-        v = *reinterpret_cast<const pm_f32x4 *>(src);
-      } else {
-        if (p < HW) v[0] = src[0];
-        if (p + 1 < HW) v[1] = src[1];
-        if (p + 2 < HW) v[2] = src[2];
-        if (p + 3 < HW) v[3] = src[3];
-      }
+    if constexpr (VEC) {
+      gv[q] = *reinterpret_cast<const pm_f32x4 *>(g_chan + min(p, HW - 4));
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) gv[q][i] = g_chan[min(p + i, HW - 1)];
     }
-    gv[q] = v;
   }
-  const unsigned long long *tp = reinterpret_cast<const unsigned long long *>(tab + (int64_t)tile * kPmTile * E);
+}
+
+// This thread's patch-table entries of the tile: always kPmMaxEntriesPerThread of them, at constant offsets from one address.
+// A slot beyond E holds an entry of the following pixels (the table holds all 32 pixels of every tile and ends in
+// kPmEntrySlots entries of slack, pm_layout) and is ignored where the entries are used.
+static_assert(kPmMaxEntriesPerThread * kPmSub <= kPmEntrySlots, "the slack behind the patch table covers every slot read");
+__device__ __forceinline__ void pm_fetch_entries(int (&peq)[kPmMaxEntriesPerThread], float (&pev)[kPmMaxEntriesPerThread],
+                                                 int tile, const PatchEntry *tab, int sub, int E) {
+  const unsigned long long *tp = reinterpret_cast<const unsigned long long *>(tab + (int64_t)tile * kPmTile * E) + sub;
 #pragma unroll
   for (int m = 0; m < kPmMaxEntriesPerThread; ++m) {
-    const int e = sub + kPmSub * m;
-    unsigned long long raw = 0xffffffffull;  // q = -1
-    if (e < E) raw = tp[e];
+    const unsigned long long raw = tp[kPmSub * m];
     peq[m] = (int)(unsigned)(raw & 0xffffffffull);
     pev[m] = __uint_as_float((unsigned)(raw >> 32));
   }
 }
 
-template <int NB>
-__global__ __launch_bounds__(256, 2) void patch_scatter_mfma_kernel(const float *__restrict__ G, float *__restrict__ dS,
-                                                                   const PatchEntry *__restrict__ table,
-                                                                   const int2 *__restrict__ tile_rows, int C, int HW,
-                                                                   int Hs, int Ws, int R, int ntiles, int E,
-                                                                   int accumulate, const unsigned *__restrict__ stat,
-                                                                   unsigned limit) {
+// Band height: the largest R with R * Ws <= 96 positions (three 32-column blocks), one row for wider planes.  Measured
+// at the bench shapes with the zero slices skipped and the tile prefetch in flight (tools/bench_scatter.py, smooth flows,
+// profiles/patch_scatter_prefetch_bench.jsonl), aggregation / resample2d (tuning key 14 = 2): 64x44 planes 1 row 217 / 334 us,
+// 2 rows 139 / 187, 3 rows 155 / 222, 4 rows 161 / 242; 32x22 planes 2 rows 69 / 111 us, 3 rows 58 / 90, 4 rows 57 / 72,
+// 6 rows 73 / 79, 8 rows 79 / 88.  Taller bands make fewer passes, but at five and six blocks the kernel holds three
+// workgroups per CU instead of four and multiplies more zeros per pass: that costs more than the passes saved.
+struct PmGeo {
+  int R, NB, bands;
+};
+static PmGeo pm_geometry(int64_t B, int64_t C, int Hs, int Ws, int W, int patch) {
+  (void)B, (void)C, (void)W, (void)patch;
+  int R = tuning(GFLA_TUNE_PM_BAND_ROWS) > 0 ? tuning(GFLA_TUNE_PM_BAND_ROWS) : 96 / Ws;
+  // planes wider than 48: one row would be a band of two blocks -- too little work per tile pass, and no skipping of its zero
+  // slices; up to six blocks instead (aggregation backward at 64x64: 501 us with one row per band, 428 with two, 415 with three)
+  if (tuning(GFLA_TUNE_PM_BAND_ROWS) <= 0 && R < 2) R = (kPmMaxNB * 32) / Ws;
+  if (R < 1) R = 1;
+  if (R > Hs) R = Hs;
+  while (R > 1 && R * Ws > kPmMaxNB * 32) --R;
+  if (R * Ws > kPmMaxNB * 32) return PmGeo{0, 0, 0};
+  return PmGeo{R, (int)ceil_div((int64_t)R * Ws, 32), (int)ceil_div(Hs, R)};
+}
+
+// tuning key 14: 0 = where it measured faster (pm_auto), 1 = never, 2 = wherever the shape is supported
+static bool pm_auto(bool aggregate, int64_t Ws) {
+  if (tuning(GFLA_TUNE_PM) == 2) return true;
+  // bench shapes, smooth / coherent flows, with the all-zero K slices skipped (profiles/r4_scatter_paths_after_zero_skip.jsonl,
+  // r4_scatter_paths_mfma_everywhere.jsonl): aggregation 64x44 376 -> 153 us, 32x22 95 -> 69 (round 3, without the skipping:
+  // 90..100, and the LDS-atomic kernel was kept there); resample2d 32x22 138 -> 91, 64x44 210 (LDS planes fed from tap
+  // records) vs 214 (coherent: 194 vs 229).  Re-measured with the tile prefetch in flight and one sample's bands on one XCD
+  // (profiles/patch_scatter_prefetch_bench.jsonl): resample2d 64x44 smooth 195 us (LDS planes 211), coherent 212 (LDS
+  // planes 174) -- the product still loses on coherent flows there, so the threshold stays
+  return aggregate ? true : Ws <= 24;
+}
+
+// dynamic LDS of patch_scatter_mfma_kernel: the W / G tiles plus 2 bytes per flow tile; plain <<<>>> launches get 64 KB
+static int64_t pm_lds_bytes(int NB, int64_t ntiles) {
+  return (int64_t)(kPmTile * NB * 32 + kPmChannels * kPmGPitch) * (int64_t)sizeof(float) + ((ntiles + 7) & ~(int64_t)7) * 2;
+}
+
+static bool pm_supported(int64_t B, int64_t C, int64_t H, int64_t W, int64_t Hs, int64_t Ws) {
+  if (!(B > 0 && B <= 65535 && C > 0 && Hs >= 2 && Ws >= 2 && Ws <= kPmMaxNB * 32 && Hs < 32768 && Ws < 32768 &&
+        H * W <= (int64_t)kPmTile * 65535 && ceil_div(C, kPmChannels) <= 65535 && tuning(GFLA_TUNE_PM) != 1))
+    return false;
+  // the per-tile row table lives in LDS: a flow field with more tiles than fit the 64 KB launch limit is UNSUPPORTED
+  // here (the callers fall back to the LDS-atomic kernels) instead of failing at launch
+  const PmGeo g = pm_geometry(B, C, (int)Hs, (int)Ws, (int)W, 0);
+  return g.R > 0 && pm_lds_bytes(g.NB, ceil_div(H * W, kPmTile)) <= 64 * 1024;
+}
+
+static bool pm_g_vec(const float *G, int64_t HW) {  // 16-byte loads of G: groups of four pixels are aligned, inside one plane
+  return (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(G) & 15) == 0;
+}
+
+// VEC: G is read with 16-byte loads (pm_g_vec); the launcher decides (a runtime flag inside the tile loop would put the
+// loads back into branches).  Register budget: four waves per SIMD (128 VGPRs) up to three blocks, three (168) beyond.
+template <int NB, bool VEC>
+__global__ __launch_bounds__(256, NB <= 3 ? 4 : 3) void patch_scatter_mfma_kernel(
+    const float *__restrict__ G, float *__restrict__ dS, const PatchEntry *__restrict__ table,
+    const int2 *__restrict__ tile_rows, int C, int HW, int Hs, int Ws, int R, int ntiles, int E, int accumulate,
+    const unsigned *__restrict__ stat, unsigned limit) {
   constexpr int NQ = NB * 32;
   // all-zero (K step, block) pairs are skipped where a band has three or more blocks; with two (64-wide planes: one row per
   // band) the bookkeeping cost more than the MFMAs it saved (aggregation backward at 64x64: 490 -> 570 us)
@@ -433,26 +494,37 @@ __global__ __launch_bounds__(256, 2) void patch_scatter_mfma_kernel(const float 
   // and their MFMAs (64 cycles each) are skipped
   __shared__ unsigned s_mask[3];   // 16 K steps x NB <= 6 blocks = up to 96 bits
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, kh = lane >> 5;
-  const int band = blockIdx.x;
-  const int64_t b = blockIdx.y;
-  const int c0 = blockIdx.z * kPmChannels;
+  // Workgroups are dealt round-robin over the eight XCDs, so the bands of one sample -- which read the same tiles of G --
+  // landed on eight different L2s and each fetched them for itself.  Renumbered (a bijection for any grid size; 32 bits: a
+  // gradient of 2^32 bands x 128 channels fits no memory) so that consecutive bands share an XCD.  Placement is a matter of
+  // speed only: every workgroup owns its band.
+  const unsigned nwg = gridDim.x * gridDim.y * gridDim.z, lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  const unsigned xq = nwg >> 3, xr = nwg & 7u, xcd = lin & 7u;
+  const unsigned id = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
+  const int band = (int)(id % gridDim.x);
+  const int64_t b = (id / gridDim.x) % gridDim.y;
+  const int c0 = (int)(id / (gridDim.x * gridDim.y)) * kPmChannels;
   const int by0 = band * R, by1 = min(Hs, by0 + R) - 1;
   const int nq = (by1 - by0 + 1) * Ws;
 
-  // ascending list of the tiles whose patches reach rows [by0, by1]: built by wave 0, 64 tiles per step
+  // ascending list of the tiles whose patches reach rows [by0, by1]: built by wave 0.  The row ranges of kPmListBatch x 64
+  // tiles are requested together (clamped index, no branch around the loads) before the first ballot: one exposed round
+  // trip per 256 tiles -- for every plane up to 8192 flow pixels, both bench shapes among them, one in all (it was one per 64)
   if (wave == 0) {
     const int2 *tr = tile_rows + b * ntiles;
     int n = 0;
-    for (int base = 0; base < ntiles; base += 64) {
-      const int tile = base + lane;
-      bool f = false;
-      if (tile < ntiles) {
-        const int2 rr = tr[tile];
-        f = rr.x <= by1 && rr.y >= by0;
+    for (int base = 0; base < ntiles; base += 64 * kPmListBatch) {
+      int2 rr[kPmListBatch];
+#pragma unroll
+      for (int u = 0; u < kPmListBatch; ++u) rr[u] = tr[min(base + 64 * u + lane, ntiles - 1)];
+#pragma unroll
+      for (int u = 0; u < kPmListBatch; ++u) {
+        const int tile = base + 64 * u + lane;
+        const bool f = tile < ntiles && rr[u].x <= by1 && rr[u].y >= by0;
+        const unsigned long long m = __ballot(f);
+        if (f) list[n + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)tile;
+        n += __popcll(m);
       }
-      const unsigned long long m = __ballot(f);
-      if (f) list[n + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)tile;
-      n += __popcll(m);
     }
     if (lane == 0) s_nlist = n;
   }
@@ -468,15 +540,19 @@ __global__ __launch_bounds__(256, 2) void patch_scatter_mfma_kernel(const float 
   // staging roles: G tile -- thread = (channel t >> 1, 16-pixel half t & 1); W tile -- thread = (pixel t >> 3, slot t & 7)
   const int gc = t >> 1, gh = t & 1;
   const bool g_ok = c0 + gc < C;
-  const float *g_row = G + (b * C + (g_ok ? c0 + gc : 0)) * (int64_t)HW + gh * 16;
-  const bool g_vec = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(G) & 15) == 0;
+  const float *g_chan = G + (b * C + min(c0 + gc, C - 1)) * (int64_t)HW;
   const int pl = t >> 3, sub = t & (kPmSub - 1);
   const PatchEntry *tab = table + (b * ntiles * kPmTile + pl) * (int64_t)E;
 
+  // The next tile is requested UNCONDITIONALLY (past the end of the list: the last tile again, tile 0 for an empty list),
+  // each half as soon as the registers it lands in are dead, and is first touched at the top of the next pass: the requests
+  // are in flight across the barriers and the whole K loop.  (wave-uniform tile number: scalar address arithmetic)
   pm_f32x4 gv[4];
   int peq[kPmMaxEntriesPerThread];
   float pev[kPmMaxEntriesPerThread];
-  if (nlist > 0) pm_fetch(gv, peq, pev, list[0], g_row, g_ok, g_vec, gh, HW, tab, sub, E);
+  int tile = nlist > 0 ? __builtin_amdgcn_readfirstlane((int)list[0]) : 0;
+  pm_fetch_g<VEC>(gv, tile, g_chan, gh, HW);
+  pm_fetch_entries(peq, pev, tile, tab, sub, E);
   for (int li = 0; li < nlist; ++li) {
     __syncthreads();  // the previous tile's MFMAs are done with wt / gt
 #pragma unroll
@@ -484,19 +560,19 @@ __global__ __launch_bounds__(256, 2) void patch_scatter_mfma_kernel(const float 
     if (kSkip && t < 3) s_mask[t] = 0u;
     {
       float *dst = gt + gc * kPmGPitch + gh * 16;
+      const int nvalid = g_ok ? HW - (tile * kPmTile + gh * 16) : 0;  // of this thread's 16 pixels; the rest are stored as 0
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        dst[4 * q + 0] = gv[q][0];
-        dst[4 * q + 1] = gv[q][1];
-        dst[4 * q + 2] = gv[q][2];
-        dst[4 * q + 3] = gv[q][3];
-      }
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst[4 * q + i] = 4 * q + i < nvalid ? gv[q][i] : 0.f;
     }
+    tile = __builtin_amdgcn_readfirstlane((int)list[li + 1 < nlist ? li + 1 : li]);
+    pm_fetch_g<VEC>(gv, tile, g_chan, gh, HW);
     __syncthreads();  // wt is zero everywhere before any entry lands
     unsigned blocks = 0;   // the column blocks this thread's entries fall into
 #pragma unroll
     for (int m = 0; m < kPmMaxEntriesPerThread; ++m) {
-      const int q = peq[m];
+      const int q = sub + kPmSub * m < E ? peq[m] : -1;
       if (q >= 0) {
         const int ty = q >> 16, tx = q & 0xffff;
         if (ty >= by0 && ty <= by1) {
@@ -506,6 +582,7 @@ __global__ __launch_bounds__(256, 2) void patch_scatter_mfma_kernel(const float 
         }
       }
     }
+    pm_fetch_entries(peq, pev, tile, tab, sub, E);
     // 16 consecutive threads hold the two pixels of ONE K step: their blocks are OR-ed across the 16 lanes and published by
     // one lane (a thread-per-entry atomicOr put ~1000 same-address LDS atomics into every tile pass: at 64-wide planes that
     // cost more than the skipped MFMAs saved)
@@ -520,8 +597,6 @@ __global__ __launch_bounds__(256, 2) void patch_scatter_mfma_kernel(const float 
       atomicOr(&s_mask[w], blocks << sh);
       if (sh + NB > 32) atomicOr(&s_mask[w + 1], blocks >> (32 - sh));
     }
-    if (li + 1 < nlist)  // in flight during the MFMAs
-      pm_fetch(gv, peq, pev, list[li + 1], g_row, g_ok, g_vec, gh, HW, tab, sub, E);
     __syncthreads();
     // D[c][q] += G[c][p] W[p][q]: A = G (rows = channels), B = W (columns = band positions), K = the 32 pixels
     // wave-uniform: scalar registers
@@ -555,71 +630,46 @@ __global__ __launch_bounds__(256, 2) void patch_scatter_mfma_kernel(const float 
     }
   }
   // C/D layout: column = lane & 31 (band position), row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) (channel)
-  // One base pointer per lane, the 16 rows as multiples of the plane pitch; when accumulating, ALL old values are requested
-  // before the first is used (a load + wait + add + store per element was 16 NB dependent round trips per workgroup)
-  const int64_t plane = (int64_t)Hs * Ws;
+  // When accumulating, the 16 old values of a column block are requested together.  The requests are branch-free -- an
+  // element outside the band or beyond C reads the band's first element instead (always inside the tensor) and is never
+  // stored: a per-element `ok ? load : 0` became exec-masked blocks with two to three waits inside each group of 16, and
+  // before that a load + wait + add + store per element was 16 NB dependent round trips per workgroup.
+  // Addresses = the band's first element of channel c0 (wave-uniform) + a 32-bit byte offset per element: at most 128
+  // planes of <= 192 x 32767 floats, below 2^32 bytes (pm_supported).  One register per address instead of two.
+  const unsigned plane_b = (unsigned)(Hs * Ws) * 4u;
   const int cb = c0 + wave * 32 + 4 * kh;
-  float *ob = dS + ((b * C + cb) * (int64_t)Hs + by0) * Ws + l31;
+  char *band0 = reinterpret_cast<char *>(dS + ((b * C + c0) * (int64_t)Hs + by0) * Ws);
+  const unsigned lane_b = (unsigned)(wave * 32 + 4 * kh) * plane_b + (unsigned)l31 * 4u;
+  if (accumulate) {
 #pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const bool col_ok = 32 * j + l31 < nq;
-    float oldv[16];
+    for (int j = 0; j < NB; ++j) {
+      const bool col_ok = 32 * j + l31 < nq;
+      float oldv[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int dc = (r & 3) + 8 * (r >> 2);
-      const bool ok = col_ok && cb + dc < C;
-      oldv[r] = (accumulate && ok) ? ob[dc * plane + 32 * j] : 0.f;
+      for (int r = 0; r < 16; ++r) {
+        const int dc = (r & 3) + 8 * (r >> 2);
+        const unsigned off = (col_ok && cb + dc < C) ? lane_b + (unsigned)dc * plane_b + 128u * j : 0u;
+        oldv[r] = *reinterpret_cast<const float *>(band0 + off);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int dc = (r & 3) + 8 * (r >> 2);
+        if (col_ok && cb + dc < C)
+          *reinterpret_cast<float *>(band0 + (lane_b + (unsigned)dc * plane_b + 128u * j)) = oldv[r] + acc[j][r];
+      }
     }
+  } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int dc = (r & 3) + 8 * (r >> 2);
-      if (col_ok && cb + dc < C) ob[dc * plane + 32 * j] = oldv[r] + acc[j][r];
+    for (int j = 0; j < NB; ++j) {
+      const bool col_ok = 32 * j + l31 < nq;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int dc = (r & 3) + 8 * (r >> 2);
+        if (col_ok && cb + dc < C)
+          *reinterpret_cast<float *>(band0 + (lane_b + (unsigned)dc * plane_b + 128u * j)) = 0.f + acc[j][r];
+      }
     }
   }
-}
-
-// Band height: the largest R with R * Ws <= 96 positions (three 32-column blocks), one row for wider planes.  Measured
-// at the bench shapes (tools/bench_scatter.py, profiles/r2_scatter_paths.jsonl): 64x44 planes 2 rows 256 us,
-// 4 rows 293 us; 32x22 planes 4 rows 128 us, 2 rows 141 us, 1 row 151 us.
-struct PmGeo {
-  int R, NB, bands;
-};
-static PmGeo pm_geometry(int64_t B, int64_t C, int Hs, int Ws, int W, int patch) {
-  (void)B, (void)C, (void)W, (void)patch;
-  int R = tuning(GFLA_TUNE_PM_BAND_ROWS) > 0 ? tuning(GFLA_TUNE_PM_BAND_ROWS) : 96 / Ws;
-  // planes wider than 48: one row would be a band of two blocks -- too little work per tile pass, and no skipping of its zero
-  // slices; up to six blocks instead (aggregation backward at 64x64: 501 us with one row per band, 428 with two, 415 with three)
-  if (tuning(GFLA_TUNE_PM_BAND_ROWS) <= 0 && R < 2) R = (kPmMaxNB * 32) / Ws;
-  if (R < 1) R = 1;
-  if (R > Hs) R = Hs;
-  while (R > 1 && R * Ws > kPmMaxNB * 32) --R;
-  if (R * Ws > kPmMaxNB * 32) return PmGeo{0, 0, 0};
-  return PmGeo{R, (int)ceil_div((int64_t)R * Ws, 32), (int)ceil_div(Hs, R)};
-}
-
-// tuning key 14: 0 = where it measured faster (pm_auto), 1 = never, 2 = wherever the shape is supported
-static bool pm_auto(bool aggregate, int64_t Ws) {
-  if (tuning(GFLA_TUNE_PM) == 2) return true;
-  // bench shapes, smooth / coherent flows, with the all-zero K slices skipped (profiles/r4_scatter_paths_after_zero_skip.jsonl,
-  // r4_scatter_paths_mfma_everywhere.jsonl): aggregation 64x44 376 -> 153 us, 32x22 95 -> 69 (round 3, without the skipping:
-  // 90..100, and the LDS-atomic kernel was kept there); resample2d 32x22 138 -> 91, 64x44 210 (LDS planes fed from tap
-  // records) vs 214 (coherent: 194 vs 229)
-  return aggregate ? true : Ws <= 24;
-}
-
-// dynamic LDS of patch_scatter_mfma_kernel: the W / G tiles plus 2 bytes per flow tile; plain <<<>>> launches get 64 KB
-static int64_t pm_lds_bytes(int NB, int64_t ntiles) {
-  return (int64_t)(kPmTile * NB * 32 + kPmChannels * kPmGPitch) * (int64_t)sizeof(float) + ((ntiles + 7) & ~(int64_t)7) * 2;
-}
-
-static bool pm_supported(int64_t B, int64_t C, int64_t H, int64_t W, int64_t Hs, int64_t Ws) {
-  if (!(B > 0 && B <= 65535 && C > 0 && Hs >= 2 && Ws >= 2 && Ws <= kPmMaxNB * 32 && Hs < 32768 && Ws < 32768 &&
-        H * W <= (int64_t)kPmTile * 65535 && ceil_div(C, kPmChannels) <= 65535 && tuning(GFLA_TUNE_PM) != 1))
-    return false;
-  // the per-tile row table lives in LDS: a flow field with more tiles than fit the 64 KB launch limit is UNSUPPORTED
-  // here (the callers fall back to the LDS-atomic kernels) instead of failing at launch
-  const PmGeo g = pm_geometry(B, C, (int)Hs, (int)Ws, (int)W, 0);
-  return g.R > 0 && pm_lds_bytes(g.NB, ceil_div(H * W, kPmTile)) <= 64 * 1024;
 }
 
 static int pm_scatter(const float *G, float *dS, const PatchEntry *table, const int2 *tile_rows, int64_t B, int64_t C,
@@ -631,10 +681,16 @@ static int pm_scatter(const float *G, float *dS, const PatchEntry *table, const 
   const dim3 grid((unsigned)g.bands, (unsigned)B, (unsigned)ceil_div(C, kPmChannels));
   const unsigned lds = (unsigned)pm_lds_bytes(g.NB, ntiles);
   if (lds > 64 * 1024) return GFLA_ERR_UNSUPPORTED;
-#define GFLA_PM(NB_)                                                                                              \
-  case NB_:                                                                                                       \
-    patch_scatter_mfma_kernel<NB_><<<grid, 256, lds, stream>>>(G, dS, table, tile_rows, (int)C, (int)(H * W), (int)Hs, \
-                                                               (int)Ws, g.R, ntiles, entries, accumulate, stat, limit); \
+  const bool g_vec = pm_g_vec(G, H * W);
+#define GFLA_PM_LAUNCH(NB_, VEC_)                                                                                     \
+  patch_scatter_mfma_kernel<NB_, VEC_><<<grid, 256, lds, stream>>>(G, dS, table, tile_rows, (int)C, (int)(H * W), (int)Hs, \
+                                                                   (int)Ws, g.R, ntiles, entries, accumulate, stat, limit)
+#define GFLA_PM(NB_)                  \
+  case NB_:                           \
+    if (g_vec)                        \
+      GFLA_PM_LAUNCH(NB_, true);      \
+    else                              \
+      GFLA_PM_LAUNCH(NB_, false);     \
     break
   switch (g.NB) {
     GFLA_PM(1);
@@ -646,6 +702,7 @@ static int pm_scatter(const float *G, float *dS, const PatchEntry *table, const 
     default: return GFLA_ERR_UNSUPPORTED;
   }
 #undef GFLA_PM
+#undef GFLA_PM_LAUNCH
   return launch_status();
 }
 
