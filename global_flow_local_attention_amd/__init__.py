@@ -23,8 +23,9 @@ from .head_conv import (HeadConv3x3, HeadConv3x3Function, flow_mask_heads, fuse_
                         patch_reference_flow_heads, torch_head_conv3x3)
 from .gen_conv import (Conv1x1Function, GenConvFunction, InferenceConv, conv1x1, conv3x3, conv4x4_down,  # noqa: F401
                        conv_transpose3x3_up, fuse_inference_convs, patch_reference_convs, torch_conv1x1, torch_gen_conv)
-from .spectral_norm import (AvgPoolFrames, SpectralConv, SpectralConv3d, SpectralNormFunction, fuse_spectral_norm,  # noqa: F401
-                            patch_reference_discriminators, spectral_normalize, torch_spectral_normalize)
+from .spectral_norm import (AvgPoolFrames, SpectralConv, SpectralConv3d, SpectralConvTranspose, SpectralHead,  # noqa: F401
+                            SpectralNormFunction, fuse_spectral_norm, patch_reference_discriminators,
+                            patch_reference_generators, spectral_normalize, torch_spectral_normalize)
 from .conv3d import (AvgPoolFramesFunction, Conv3dFramesFunction, avg_pool_frames, conv3d_frames,  # noqa: F401
                      from_frames_major, to_frames_major, torch_avg_pool_frames, torch_conv3d_frames)
 from .adam import FusedAdam  # noqa: F401

@@ -30,13 +30,14 @@ def plain(module):
     return "weight" in module._parameters and no_hooks(module)
 
 
-def spectral_norm_hook(module):
-    """the SpectralNorm hook object (name "weight", dim 0) of a module that carries exactly that one hook, or None"""
+def spectral_norm_hook(module, dims=(0,)):
+    """the SpectralNorm hook object (name "weight", a dim of `dims`: 0, or 1 as torch picks for a transposed convolution)
+    of a module that carries exactly that one hook, or None"""
     hooks = list(module._forward_pre_hooks.values())
     if len(hooks) != 1 or type(hooks[0]) is not _TorchSpectralNorm or not no_hooks(module, hooks):
         return None
     hook = hooks[0]
-    if hook.name != "weight" or hook.dim != 0 or "weight_orig" not in module._parameters:
+    if hook.name != "weight" or hook.dim not in dims or "weight_orig" not in module._parameters:
         return None
     return hook
 
@@ -47,6 +48,16 @@ def run_with_add(seq, x, add):
     for m in mods[:-1]:
         x = m(x)
     return mods[-1](x, add)
+
+
+def epilogue_slot(seq):
+    """the last module of the nn.Sequential `seq` when it adds a residual in its own epilogue -- its `fuses_add` is true:
+    an InferenceConv, a SpectralConv on a kernel geometry, a SpectralConvTranspose on the transposed 3x3 kernels --, else
+    None.  The residual forwards of every rewrite ask this one question."""
+    if not isinstance(seq, nn.Sequential) or len(seq) == 0:
+        return None
+    last = seq[len(seq) - 1]
+    return last if getattr(last, "fuses_add", False) else None
 
 
 def replace_aliases(net, replaced):

@@ -15,23 +15,20 @@
 // Sums: float32.  A thread adds its strided share in ascending order, a wave combines by xor butterfly, the waves' values
 // are added in wave order.  The order depends on (R, K) alone: bit-identical from call to call, alone or in a batch.
 // No atomics.
+//
+// A matrix normalised along dim 1 (nn.ConvTranspose2d; a 9-word record with inner > 0) runs in the same launches: its
+// workgroups take sn_colsum_dim1 / sn_rowdot_dim1 / sn_scale_dim1 (spectral_norm_dim1.h, with the record and the layout).
 #include <algorithm>
 
-#include "gfla_common.h"
+#include "spectral_norm_dim1.h"
 
 namespace gfla {
 
 constexpr int kSnCols = 64;          // columns per workgroup of the column sums
 constexpr int kSnRows = 4;           // rows per workgroup of the row dots (one wave each)
-constexpr int kSnElems = 4096;       // elements per workgroup of the element-wise passes
 constexpr int64_t kSnMaxDim = (int64_t)1 << 24;
 constexpr int64_t kSnMaxElems = 2147483647;
 constexpr int64_t kSnMaxBatch = 65535;
-
-struct SnRec {
-  int64_t w, u, v, R, K, elem_off, k_off, r_off;
-};
-static_assert(sizeof(SnRec) == 64, "the table is 8 int64 per matrix");
 
 __device__ __forceinline__ float sn_wave_sum(float v) {
 #pragma unroll
@@ -61,11 +58,12 @@ __device__ __forceinline__ float sn_denominator(const float *x, int n, float eps
 }
 
 // t = W^T u.  from_s: u = s / max(||s||, eps) of the iteration before, else the module's buffer.
-__global__ __launch_bounds__(kBlock) void sn_colsum_kernel(const SnRec *__restrict__ table, float *__restrict__ scratch,
-                                                           int from_s, float eps) {
+__global__ __launch_bounds__(kBlock) void sn_colsum_kernel(const int64_t *__restrict__ table, int words, double *__restrict__ wide,
+                                                           float *__restrict__ scratch, int from_s, float eps) {
   __shared__ float red[kBlock / 64];
   __shared__ float part[kBlock / 64][kSnCols];
-  const SnRec rec = table[blockIdx.y];
+  const SnRec rec = sn_rec(table, words, blockIdx.y);
+  if (rec.inner > 0) return sn_colsum_dim1(rec, wide, from_s, eps);
   const int R = (int)rec.R, K = (int)rec.K;
   const int c0 = blockIdx.x * kSnCols;
   if (c0 >= K) return;
@@ -93,10 +91,11 @@ __global__ __launch_bounds__(kBlock) void sn_colsum_kernel(const SnRec *__restri
 }
 
 // s = W v.  from_t: v = t / max(||t||, eps), written to the module's buffer (and `saved`) by slice 0; else the buffer.
-__global__ __launch_bounds__(kBlock) void sn_rowdot_kernel(const SnRec *__restrict__ table, float *__restrict__ scratch,
-                                                           float *__restrict__ saved, int from_t, float eps) {
+__global__ __launch_bounds__(kBlock) void sn_rowdot_kernel(const int64_t *__restrict__ table, int words, double *__restrict__ wide,
+                                                           float *__restrict__ scratch, float *__restrict__ saved, int from_t, float eps) {
   __shared__ float red[kBlock / 64];
-  const SnRec rec = table[blockIdx.y];
+  const SnRec rec = sn_rec(table, words, blockIdx.y);
+  if (rec.inner > 0) return sn_rowdot_dim1(rec, wide, saved, from_t, eps);
   const int R = (int)rec.R, K = (int)rec.K;
   const int r0 = blockIdx.x * kSnRows;
   if (r0 >= R) return;
@@ -126,11 +125,12 @@ __global__ __launch_bounds__(kBlock) void sn_rowdot_kernel(const SnRec *__restri
 
 // sigma = u . s, W_sn = W / sigma.  from_s: u = s / max(||s||, eps), written to the module's buffer (and `saved`) by slice
 // 0; else u is the buffer and slice 0 only copies u and v to `saved`.
-__global__ __launch_bounds__(kBlock) void sn_scale_kernel(const SnRec *__restrict__ table, const float *__restrict__ scratch,
-                                                          float *__restrict__ w_sn, float *__restrict__ sigma_out,
-                                                          float *__restrict__ saved, int from_s, float eps) {
+__global__ __launch_bounds__(kBlock) void sn_scale_kernel(const int64_t *__restrict__ table, int words, const double *__restrict__ wide,
+                                                          const float *__restrict__ scratch, float *__restrict__ w_sn,
+                                                          float *__restrict__ sigma_out, float *__restrict__ saved, int from_s, float eps) {
   __shared__ float red[kBlock / 64];
-  const SnRec rec = table[blockIdx.y];
+  const SnRec rec = sn_rec(table, words, blockIdx.y);
+  if (rec.inner > 0) return sn_scale_dim1(rec, blockIdx.y, wide, w_sn, sigma_out, saved, from_s, eps);
   const int R = (int)rec.R, K = (int)rec.K;
   const int64_t total = rec.R * rec.K;
   const int64_t e0 = (int64_t)blockIdx.x * kSnElems;
@@ -174,10 +174,10 @@ __global__ __launch_bounds__(kBlock) void sn_scale_kernel(const SnRec *__restric
 }
 
 // partial[matrix][slice] = sum over the slice's elements of G W
-__global__ __launch_bounds__(kBlock) void sn_bwd_dot_kernel(const SnRec *__restrict__ table, const float *__restrict__ grad_sn,
+__global__ __launch_bounds__(kBlock) void sn_bwd_dot_kernel(const int64_t *__restrict__ table, int words, const float *__restrict__ grad_sn,
                                                             float *__restrict__ partial, int max_slices) {
   __shared__ float red[kBlock / 64];
-  const SnRec rec = table[blockIdx.y];
+  const SnRec rec = sn_rec(table, words, blockIdx.y);
   const int64_t total = rec.R * rec.K;
   const int64_t e0 = (int64_t)blockIdx.x * kSnElems;
   if (e0 >= total) return;
@@ -221,12 +221,12 @@ __global__ __launch_bounds__(kBlock) void sn_bwd_dot_kernel(const SnRec *__restr
 }
 
 // grad_w = (G - c u v^T) / sigma with c = <G, W> / sigma: the partials of the matrix added in slice order
-__global__ __launch_bounds__(kBlock) void sn_bwd_apply_kernel(const SnRec *__restrict__ table, const float *__restrict__ grad_sn,
-                                                              const float *__restrict__ saved, const float *__restrict__ sigmas,
-                                                              const float *__restrict__ partial, float *__restrict__ grad_w,
-                                                              int max_slices) {
+__global__ __launch_bounds__(kBlock) void sn_bwd_apply_kernel(const int64_t *__restrict__ table, int words,
+                                                              const float *__restrict__ grad_sn, const float *__restrict__ saved,
+                                                              const float *__restrict__ sigmas, const float *__restrict__ partial,
+                                                              float *__restrict__ grad_w, int max_slices) {
   __shared__ float red[kBlock / 64];
-  const SnRec rec = table[blockIdx.y];
+  const SnRec rec = sn_rec(table, words, blockIdx.y);
   const uint32_t K = (uint32_t)rec.K;
   const int64_t total = rec.R * rec.K;
   const int64_t e0 = (int64_t)blockIdx.x * kSnElems;
@@ -253,10 +253,18 @@ __global__ __launch_bounds__(kBlock) void sn_bwd_apply_kernel(const SnRec *__res
     } else {
       for (int i = 0; i < n; ++i) g[i] = G[e + i];
     }
-    uint32_t r = (uint32_t)e / K, col = (uint32_t)e - r * K;      // R K <= 2^31 - 1
-    for (int i = 0; i < n; ++i) {
-      res[i] = (g[i] - c * u[r] * v[col]) / sigma;
-      if (++col == K) col = 0, ++r;
+    if (rec.inner > 0) {                                           // storage (ci, r, tap): column ci inner + tap
+      const uint32_t inner = (uint32_t)rec.inner, slab = (uint32_t)rec.R * inner;
+      for (int i = 0; i < n; ++i) {
+        const uint32_t o = (uint32_t)e + i, ci = o / slab, rem = o - ci * slab, r = rem / inner, j = rem - r * inner;
+        res[i] = (g[i] - c * u[r] * v[ci * inner + j]) / sigma;
+      }
+    } else {
+      uint32_t r = (uint32_t)e / K, col = (uint32_t)e - r * K;      // R K <= 2^31 - 1
+      for (int i = 0; i < n; ++i) {
+        res[i] = (g[i] - c * u[r] * v[col]) / sigma;
+        if (++col == K) col = 0, ++r;
+      }
     }
     if (vec && n == 4) {
       *reinterpret_cast<float4 *>(out + e) = make_float4(res[0], res[1], res[2], res[3]);
@@ -267,38 +275,39 @@ __global__ __launch_bounds__(kBlock) void sn_bwd_apply_kernel(const SnRec *__res
 }
 
 struct SnShape {
-  int64_t max_r = 0, max_k = 0, max_elems = 0;
+  int64_t col_slices = 0, row_slices = 0, max_elems = 0, max_inner = 0, vecs = 0;
 };
 
-// the argument checks every entry point shares; the shape summary the launch geometry needs
-static int sn_check(const int64_t *dims, int64_t n, SnShape *shape) {
+// the argument checks every entry point shares; the shape summary the launch geometry needs.  words_per: 2 (R, K) for
+// the dim-0 entry points, 3 (R, K, inner) for the mixed ones
+static int sn_check(const int64_t *dims, int words_per, int64_t n, SnShape *shape) {
   if (dims == nullptr) return GFLA_ERR_NULL_POINTER;
   if (n <= 0) return GFLA_ERR_BAD_SHAPE;
-  for (int64_t i = 0; i < n; ++i)
-    if (dims[2 * i] <= 0 || dims[2 * i + 1] <= 0) return GFLA_ERR_BAD_SHAPE;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t R = dims[words_per * i], K = dims[words_per * i + 1], inner = words_per > 2 ? dims[words_per * i + 2] : 0;
+    if (R <= 0 || K <= 0 || inner < 0 || (inner > 0 && K % inner != 0)) return GFLA_ERR_BAD_SHAPE;
+  }
   if (n > kSnMaxBatch) return GFLA_ERR_UNSUPPORTED;
   for (int64_t i = 0; i < n; ++i) {
-    const int64_t R = dims[2 * i], K = dims[2 * i + 1];
-    if (R > kSnMaxDim || K > kSnMaxDim || R * K > kSnMaxElems) return GFLA_ERR_UNSUPPORTED;
-    shape->max_r = std::max(shape->max_r, R);
-    shape->max_k = std::max(shape->max_k, K);
+    const int64_t R = dims[words_per * i], K = dims[words_per * i + 1], inner = words_per > 2 ? dims[words_per * i + 2] : 0;
+    if (R > kSnMaxDim || K > kSnMaxDim || R * K > kSnMaxElems || inner > kSnMaxInner) return GFLA_ERR_UNSUPPORTED;
+    shape->col_slices = std::max(shape->col_slices, inner > 0 ? K / inner : ceil_div(K, (int64_t)kSnCols));
+    shape->row_slices = std::max(shape->row_slices, ceil_div(R, (int64_t)(inner > 0 ? sn_rows1((int)inner) : kSnRows)));
     shape->max_elems = std::max(shape->max_elems, R * K);
+    shape->max_inner = std::max(shape->max_inner, inner);
+    shape->vecs += R + K;
   }
   return GFLA_OK;
 }
 
-}  // namespace gfla
-
-using namespace gfla;
-
-extern "C" int gfla_spectral_norm_layout(const int64_t *dims, int64_t n, int64_t *offsets, int64_t *totals) {
+static int sn_layout(const int64_t *dims, int words_per, int64_t n, int64_t *offsets, int64_t *totals) {
   if (offsets == nullptr || totals == nullptr) return GFLA_ERR_NULL_POINTER;
   SnShape shape;
-  const int status = sn_check(dims, n, &shape);
+  const int status = sn_check(dims, words_per, n, &shape);
   if (status != GFLA_OK) return status;
   int64_t elems = 0, vecs = 0;
   for (int64_t i = 0; i < n; ++i) {
-    const int64_t R = dims[2 * i], K = dims[2 * i + 1];
+    const int64_t R = dims[words_per * i], K = dims[words_per * i + 1];
     offsets[3 * i] = elems;
     offsets[3 * i + 1] = vecs;
     offsets[3 * i + 2] = vecs + K;
@@ -310,54 +319,100 @@ extern "C" int gfla_spectral_norm_layout(const int64_t *dims, int64_t n, int64_t
   return GFLA_OK;
 }
 
-extern "C" int64_t gfla_spectral_norm_bwd_scratch_floats(const int64_t *dims, int64_t n) {
+static int64_t sn_bwd_scratch(const int64_t *dims, int words_per, int64_t n) {
   SnShape shape;
-  const int status = sn_check(dims, n, &shape);
+  const int status = sn_check(dims, words_per, n, &shape);
   if (status != GFLA_OK) return status;
-  return n * ceil_div(shape.max_elems, kSnElems);
+  return n * ceil_div(shape.max_elems, (int64_t)kSnElems);
 }
 
-extern "C" int gfla_spectral_norm_fwd_f32(const void *table, const int64_t *dims, int64_t n, float *w_sn, float *sigma,
-                                          float *saved, float *scratch, int power_iterations, double eps,
-                                          gfla_stream_t stream) {
+static int sn_forward(const void *table, int words, const int64_t *dims, int words_per, int64_t n, float *w_sn, float *sigma,
+                      float *saved, float *scratch, int power_iterations, double eps, gfla_stream_t stream) {
   if (table == nullptr || dims == nullptr || w_sn == nullptr || sigma == nullptr || scratch == nullptr)
     return GFLA_ERR_NULL_POINTER;
   if (power_iterations < 0 || !(eps > 0)) return GFLA_ERR_BAD_SHAPE;
   SnShape shape;
-  const int status = sn_check(dims, n, &shape);
+  const int status = sn_check(dims, words_per, n, &shape);
   if (status != GFLA_OK) return status;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const SnRec *recs = static_cast<const SnRec *>(table);
+  const int64_t *recs = static_cast<const int64_t *>(table);
   const float feps = (float)eps;
-  const dim3 cols((unsigned)ceil_div(shape.max_k, kSnCols), (unsigned)n);
-  const dim3 rows((unsigned)ceil_div(shape.max_r, kSnRows), (unsigned)n);
-  const dim3 elems((unsigned)ceil_div(shape.max_elems, kSnElems), (unsigned)n);
+  const dim3 cols((unsigned)shape.col_slices, (unsigned)n);
+  const dim3 rows((unsigned)shape.row_slices, (unsigned)n);
+  const dim3 elems((unsigned)ceil_div(shape.max_elems, (int64_t)kSnElems), (unsigned)n);
+  const size_t bins = (size_t)shape.max_inner * kBlock * sizeof(double);     // 0 for a batch of dim-0 matrices
+  // the float64 t and s of the dim-1 matrices: behind the float32 vector arrays, at the next multiple of 8 bytes; the
+  // dim-0 entry points have neither (their scratch ends with the float32 arrays) and no kernel of theirs looks
+  double *wide = words > kSnWords0
+                     ? reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(scratch + shape.vecs) + 7) & ~(uintptr_t)7)
+                     : nullptr;
   for (int it = 0; it < power_iterations; ++it) {
-    hipLaunchKernelGGL(sn_colsum_kernel, cols, dim3(kBlock), 0, st, recs, scratch, it > 0 ? 1 : 0, feps);
-    hipLaunchKernelGGL(sn_rowdot_kernel, rows, dim3(kBlock), 0, st, recs, scratch, saved, 1, feps);
+    hipLaunchKernelGGL(sn_colsum_kernel, cols, dim3(kBlock), bins, st, recs, words, wide, scratch, it > 0 ? 1 : 0, feps);
+    hipLaunchKernelGGL(sn_rowdot_kernel, rows, dim3(kBlock), 0, st, recs, words, wide, scratch, saved, 1, feps);
   }
   if (power_iterations == 0)
-    hipLaunchKernelGGL(sn_rowdot_kernel, rows, dim3(kBlock), 0, st, recs, scratch, saved, 0, feps);
-  hipLaunchKernelGGL(sn_scale_kernel, elems, dim3(kBlock), 0, st, recs, scratch, w_sn, sigma, saved,
+    hipLaunchKernelGGL(sn_rowdot_kernel, rows, dim3(kBlock), 0, st, recs, words, wide, scratch, saved, 0, feps);
+  hipLaunchKernelGGL(sn_scale_kernel, elems, dim3(kBlock), 0, st, recs, words, wide, scratch, w_sn, sigma, saved,
                      power_iterations > 0 ? 1 : 0, feps);
   return launch_status();
+}
+
+static int sn_backward(const void *table, int words, const int64_t *dims, int words_per, int64_t n, const float *grad_sn,
+                       const float *saved, const float *sigma, float *grad_w, float *scratch, gfla_stream_t stream) {
+  if (table == nullptr || dims == nullptr || grad_sn == nullptr || saved == nullptr || sigma == nullptr ||
+      grad_w == nullptr || scratch == nullptr)
+    return GFLA_ERR_NULL_POINTER;
+  SnShape shape;
+  const int status = sn_check(dims, words_per, n, &shape);
+  if (status != GFLA_OK) return status;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t *recs = static_cast<const int64_t *>(table);
+  const int max_slices = (int)ceil_div(shape.max_elems, (int64_t)kSnElems);
+  const dim3 elems((unsigned)max_slices, (unsigned)n);
+  hipLaunchKernelGGL(sn_bwd_dot_kernel, elems, dim3(kBlock), 0, st, recs, words, grad_sn, scratch, max_slices);
+  hipLaunchKernelGGL(sn_bwd_apply_kernel, elems, dim3(kBlock), 0, st, recs, words, grad_sn, saved, sigma, scratch, grad_w,
+                     max_slices);
+  return launch_status();
+}
+
+}  // namespace gfla
+
+using namespace gfla;
+
+extern "C" int gfla_spectral_norm_layout(const int64_t *dims, int64_t n, int64_t *offsets, int64_t *totals) {
+  return sn_layout(dims, 2, n, offsets, totals);
+}
+
+extern "C" int64_t gfla_spectral_norm_bwd_scratch_floats(const int64_t *dims, int64_t n) { return sn_bwd_scratch(dims, 2, n); }
+
+extern "C" int gfla_spectral_norm_fwd_f32(const void *table, const int64_t *dims, int64_t n, float *w_sn, float *sigma,
+                                          float *saved, float *scratch, int power_iterations, double eps,
+                                          gfla_stream_t stream) {
+  return sn_forward(table, kSnWords0, dims, 2, n, w_sn, sigma, saved, scratch, power_iterations, eps, stream);
 }
 
 extern "C" int gfla_spectral_norm_bwd_f32(const void *table, const int64_t *dims, int64_t n, const float *grad_sn,
                                           const float *saved, const float *sigma, float *grad_w, float *scratch,
                                           gfla_stream_t stream) {
-  if (table == nullptr || dims == nullptr || grad_sn == nullptr || saved == nullptr || sigma == nullptr ||
-      grad_w == nullptr || scratch == nullptr)
-    return GFLA_ERR_NULL_POINTER;
-  SnShape shape;
-  const int status = sn_check(dims, n, &shape);
-  if (status != GFLA_OK) return status;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const SnRec *recs = static_cast<const SnRec *>(table);
-  const int max_slices = (int)ceil_div(shape.max_elems, kSnElems);
-  const dim3 elems((unsigned)max_slices, (unsigned)n);
-  hipLaunchKernelGGL(sn_bwd_dot_kernel, elems, dim3(kBlock), 0, st, recs, grad_sn, scratch, max_slices);
-  hipLaunchKernelGGL(sn_bwd_apply_kernel, elems, dim3(kBlock), 0, st, recs, grad_sn, saved, sigma, scratch, grad_w,
-                     max_slices);
-  return launch_status();
+  return sn_backward(table, kSnWords0, dims, 2, n, grad_sn, saved, sigma, grad_w, scratch, stream);
+}
+
+extern "C" int gfla_spectral_norm_mixed_layout(const int64_t *dims, int64_t n, int64_t *offsets, int64_t *totals) {
+  return sn_layout(dims, 3, n, offsets, totals);
+}
+
+extern "C" int64_t gfla_spectral_norm_mixed_bwd_scratch_floats(const int64_t *dims, int64_t n) {
+  return sn_bwd_scratch(dims, 3, n);
+}
+
+extern "C" int gfla_spectral_norm_mixed_fwd_f32(const void *table, const int64_t *dims, int64_t n, float *w_sn, float *sigma,
+                                                float *saved, float *scratch, int power_iterations, double eps,
+                                                gfla_stream_t stream) {
+  return sn_forward(table, kSnWords, dims, 3, n, w_sn, sigma, saved, scratch, power_iterations, eps, stream);
+}
+
+extern "C" int gfla_spectral_norm_mixed_bwd_f32(const void *table, const int64_t *dims, int64_t n, const float *grad_sn,
+                                                const float *saved, const float *sigma, float *grad_w, float *scratch,
+                                                gfla_stream_t stream) {
+  return sn_backward(table, kSnWords, dims, 3, n, grad_sn, saved, sigma, grad_w, scratch, stream);
 }

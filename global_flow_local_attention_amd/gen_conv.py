@@ -346,6 +346,8 @@ class InferenceConv(nn.Module):
     impl="torch".  geometry P1K1 (Conv2d(k 1, s 1, p 0), what fuse_inference_convs makes with pointwise=True) is conv1x1
     with pool=1, which has the same dispatch and its torch composition for everything else."""
 
+    fuses_add = True                           # _rewrite.epilogue_slot: forward(x, add) adds in the kernel's epilogue
+
     def __init__(self, conv, geometry, padding="zeros", pre_slope=None, impl="auto", grad="torch"):
         super(InferenceConv, self).__init__()
         _lib.check_impl(impl)
@@ -391,7 +393,7 @@ def fuse_inference_convs(net, impl="auto", grad="torch", pointwise=False):
     the convolution is folded in (its slot becomes nn.Identity(); a shared activation object is left as it is: only slots
     change).  Indices and state-dict keys do not change; a convolution also registered under another name (the
     reference's Jump keeps its own as `conv1` and `model.N`) is replaced there by the same InferenceConv.
-    Left alone, uncounted: modules with any hook (spectral norm), CoordConv, groups / dilation other than 1, other padding
+    Left alone, uncounted: modules with any hook (spectral norm: spectral_norm.fuse_spectral_norm rewrites those), CoordConv, groups / dilation other than 1, other padding
     modes, 1x1 convolutions unless pointwise=True, anything inside an ExtractorAttn (`fully_connect_layer`), 3x3
     convolutions of at most 8 output channels (head_conv.py's: HeadConv3x3 slots and the flow / mask heads).  grad: the
     `grad` of every InferenceConv made ("kernels": training runs on GenConvFunction).  Returns the number of convolutions
@@ -426,11 +428,23 @@ def fuse_inference_convs(net, impl="auto", grad="torch", pointwise=False):
     return len(replaced)
 
 
-def _last_inference_conv(seq):
-    if not isinstance(seq, nn.Sequential) or len(seq) == 0:
-        return None
-    last = seq[len(seq) - 1]
-    return last if type(last) is InferenceConv else None
+def install_residual_forwards(base_function):
+    """Replace ResBlock.forward and ResBlockDecoder.forward of the reference's base_function (base_function.py:386-391,
+    529-531) by versions that hand the residual (x, or shortcut(x)) as `add` to the last slot of `self.model` when
+    _rewrite.epilogue_slot finds one there -- an InferenceConv, a SpectralConv on a kernel geometry or a
+    SpectralConvTranspose on the transposed 3x3 kernels --; otherwise they call the original forward.  One flag
+    (`_gfla_residual_in_epilogue`) whoever installs them: idempotent.  Returns the names of the classes found."""
+    def make_forward(orig, decoder):
+        def forward(self, x):
+            if _rewrite.epilogue_slot(self.model) is None:
+                return orig(self, x)
+            if decoder or self.learnable_shortcut:
+                return _rewrite.run_with_add(self.model, x, self.shortcut(x))
+            return _rewrite.run_with_add(self.model, x, x)
+        return forward
+    return [name for name in ("ResBlock", "ResBlockDecoder")
+            if _rewrite.wrap_method(getattr(base_function, name, None), "forward", "_gfla_residual_in_epilogue",
+                                    lambda orig, decoder=name == "ResBlockDecoder": make_forward(orig, decoder))]
 
 
 _REFERENCE_CONV_BLOCKS = ("EncoderBlock", "ResBlock", "ResBlockDecoder", "Jump")
@@ -439,21 +453,12 @@ _REFERENCE_CONV_BLOCKS = ("EncoderBlock", "ResBlock", "ResBlockDecoder", "Jump")
 def patch_reference_convs(base_function, impl="auto", grad="torch", pointwise=False):
     """Wrap the constructors of the reference's EncoderBlock, ResBlock, ResBlockDecoder and Jump so that every block built
     from now on comes out rewritten (fuse_inference_convs on the finished block), and replace ResBlock.forward and
-    ResBlockDecoder.forward by versions that hand the residual (x, or shortcut(x)) as `add` to the last InferenceConv of
-    `self.model`; whenever that slot is no InferenceConv they call the original forward.  With grad="kernels" the blocks
+    ResBlockDecoder.forward by versions that hand the residual (x, or shortcut(x)) as `add` to the last slot of `self.model`
+    when it adds in its epilogue (install_residual_forwards); otherwise they call the original forward.  With grad="kernels" the blocks
     train on GenConvFunction and the residual's gradient flows through its `add`.  pointwise=True: the learnable 1x1
     shortcut of a ResBlock is rewritten as well (fuse_inference_convs).  Idempotent.  Returns the names of the classes
     wrapped."""
     check_grad(grad)
-
-    def make_forward(orig, decoder):
-        def forward(self, x):
-            if _last_inference_conv(self.model) is None:
-                return orig(self, x)
-            if decoder or self.learnable_shortcut:
-                return _rewrite.run_with_add(self.model, x, self.shortcut(x))
-            return _rewrite.run_with_add(self.model, x, x)
-        return forward
     wrapped = []
     for name in _REFERENCE_CONV_BLOCKS:
         cls = getattr(base_function, name, None)
@@ -461,7 +466,5 @@ def patch_reference_convs(base_function, impl="auto", grad="torch", pointwise=Fa
                                   lambda self: fuse_inference_convs(self, impl, grad, pointwise)):
             continue
         wrapped.append(name)
-        if name in ("ResBlock", "ResBlockDecoder"):
-            _rewrite.wrap_method(cls, "forward", "_gfla_residual_in_epilogue",
-                                 lambda orig, decoder=name == "ResBlockDecoder": make_forward(orig, decoder))
+    install_residual_forwards(base_function)
     return wrapped

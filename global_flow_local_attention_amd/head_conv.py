@@ -260,7 +260,8 @@ def fuse_output_heads(module, impl="auto"):
     and state-dict keys do not change (a convolution that is also registered under another name -- the reference's
     `Output` keeps its own as `conv1` and as `model.2` -- stays there untouched: the Parameters are shared), and an
     activation instance shared with other places of the network is left as it is: only slots are replaced.  Convolutions
-    that carry any forward or backward hook (spectral norm recomputes the weight in one) are left alone.  An activation
+    that carry any forward or backward hook (spectral norm recomputes the weight in one) are left alone here:
+    spectral_norm.fuse_spectral_norm(generator=True) makes a SpectralHead of a spectrally normalised head.  An activation
     built with inplace=True no longer overwrites the caller's input once it is fused: the op reads x and leaves it as it
     is.  Returns the number of heads fused."""
     _lib.check_impl(impl)

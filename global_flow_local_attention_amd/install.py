@@ -45,7 +45,7 @@ def _bind_vgg(cls, vgg):
 def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, allow_vendor_fallback=None,
             dual_stream_face=False, strict_mfma=None, vgg=None, bilinear_sampling_block=False, fuse_instance_norm=False,
             fuse_heads=False, inference_convs=False, train_convs=False, discriminator_convs=False, pointwise_convs=False,
-            temporal_convs=False):
+            generator_spectral=False, temporal_convs=False):
     """Alias the three op modules; optionally patch the reference's ExtractorAttn with the fused
     forward.  `reference_root` (a checkout of the reference) is only needed if `model` is not
     already importable.  Returns the reference's `model.networks.base_function` module when it
@@ -85,7 +85,7 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     (LeakyReLU -> ReflectionPad2d(1) -> Conv2d(ngf, 3, 3) -> Tanh; state-dict keys `conv1.*` and `model.2.*` and the
     Parameter objects unchanged), and `attn_output` of PoseFlowNet / FaceFlowNet / ShapeNetFlowNet computes the flow field
     and its sigmoid mask in one launch (head_conv.flow_mask_heads).  Imports the reference's generator module.  Heads built
-    with spectral norm or coordinate convolutions keep the reference's modules.  False (the default) changes nothing.
+    with spectral norm (unless generator_spectral is set: see there) or coordinate convolutions keep the reference's modules.  False (the default) changes nothing.
 
     inference_convs: True (or "auto" / "torch", the `impl` of gen_conv.py) wraps the constructors of the reference's
     EncoderBlock, ResBlock, ResBlockDecoder and Jump so that a generator built AFTER install() has its 3x3, 4x4 stride-2 and
@@ -122,12 +122,24 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
     window of three frames (csrc/conv3d.hip), the AvgPool3d((3,2,2), (1,2,2)) on csrc/avg_pool_frames.hip, the 1x1x1 bypass
     on csrc/conv1x1.hip, and their spectral norms join the one batched call.  With train_convs and pointwise_convs a
     TemporalDiscriminator then trains with no vendor convolution or pool.  State-dict keys, Parameter and buffer objects are
-    unchanged.  False (the default) changes nothing; without discriminator_convs it raises ValueError."""
+    unchanged.  False (the default) changes nothing; without discriminator_convs it raises ValueError.
+
+    generator_spectral: True (or "auto" / "torch", the `impl` of spectral_norm.py) wraps the constructors of the reference's
+    PoseGenerator, PoseFlowNetGenerator, DanceGenerator, FaceGenerator, ShapeNetGenerator and ShapeNetFlowNetGenerator
+    (generator.py) so that one built AFTER install() with spectral norm (the pose model's default, --use_spect_g) has every
+    hooked convolution on the library: Conv2d as SpectralConv, ConvTranspose2d (normalised along dim 1) as
+    SpectralConvTranspose, every Jump as a reflect-padded SpectralConv, the Output head as a SpectralHead
+    (fuse_spectral_norm(generator=True)) -- one batched normalisation per forward of the whole generator -- and ResBlock /
+    ResBlockDecoder add their residual in the last convolution's epilogue.  With train_convs the convolutions train on the
+    library's gradient kernels, with pointwise_convs the 1x1 shortcuts run gen_conv.conv1x1; either accepts
+    generator_spectral as the flag it needs.  CoordConv and ExtractorAttn keep the reference's modules.  Indices,
+    state-dict keys, Parameter and buffer objects are unchanged.  Composes with fuse_instance_norm.  Imports the reference's
+    generator module.  False (the default) changes nothing."""
     if temporal_convs and not discriminator_convs:
         raise ValueError("install: temporal_convs=True needs discriminator_convs")
-    if pointwise_convs and not (inference_convs or discriminator_convs):
-        raise ValueError("install: pointwise_convs=True needs inference_convs or discriminator_convs")
-    if train_convs and not (inference_convs or discriminator_convs):
+    if pointwise_convs and not (inference_convs or discriminator_convs or generator_spectral):
+        raise ValueError("install: pointwise_convs=True needs inference_convs, discriminator_convs or generator_spectral")
+    if train_convs and not (inference_convs or discriminator_convs or generator_spectral):
         raise ValueError("install: train_convs=True needs inference_convs%s"
                          % ("" if not discriminator_convs else " or discriminator_convs"))
     from . import extractor_attn as _ea
@@ -195,6 +207,11 @@ def install(reference_root=None, fuse_extractor_attn=True, stub_missing=True, al
                                        "kernels" if train_convs else "torch",
                                        "kernels" if pointwise_convs else "torch",
                                        "kernels" if temporal_convs else "torch")
+    if base_function is not None and generator_spectral:
+        from .spectral_norm import patch_reference_generators
+        patch_reference_generators(importlib.import_module("model.networks.generator"), base_function,
+                                   generator_spectral if isinstance(generator_spectral, str) else "auto",
+                                   "kernels" if train_convs else "torch", "kernels" if pointwise_convs else "torch")
     if vgg is not None:
         from . import losses
         external_function = importlib.import_module("model.networks.external_function")

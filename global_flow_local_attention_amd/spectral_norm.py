@@ -11,8 +11,14 @@ shortcut folded into the convolution (gen_conv.conv1x1).
     SpectralNormFunction    the autograd Function on the kernels
     SpectralConv            module with the hooked convolution's Parameters, buffers and names
     SpectralConv3d          the same for the Conv3d of a ResBlock3DEncoder, on frames-major maps (conv3d.py)
+    SpectralConvTranspose   the same for an nn.ConvTranspose2d, which torch normalises along dim 1
+    SpectralHead            a hooked narrow 3x3 convolution behind a reflection pad, on head_conv.head_conv3x3
     fuse_spectral_norm      rewrite the hooked convolutions of a network in place
     patch_reference_discriminators   the reference's discriminators, rewritten as they are built
+    patch_reference_generators       the reference's generators, rewritten as they are built
+
+A weight normalised along dim 1 -- (Cin, Cout, kh, kw), the matrix being weight.permute(1,0,2,3).reshape(Cout, -1) -- is
+read by the kernels where it lies: W_sn and the gradients keep the weight's storage layout and no permuted copy is made.
 
 Float32 parameters on the GPU run on the kernels (under torch.autocast as well: parameters stay float32).  CPU tensors,
 float64, 16-bit parameters and impl="torch" take the torch composition: the operations of the hook's compute_weight in
@@ -31,7 +37,8 @@ from . import _lib
 from . import _rewrite
 from . import conv3d as _c3
 from . import gen_conv as _gc
-from ._conv_common import P1K1, S1K3, S2K4, check_grad, conv_geometry
+from . import head_conv as _hc
+from ._conv_common import P1K1, PADDINGS, S1K3, S2K4, T2K3, check_grad, conv_geometry
 
 POINTWISE = ("torch", "kernels")
 TEMPORAL = ("torch", "kernels")
@@ -42,24 +49,30 @@ _TABLE_CACHE_MAX = 64
 class _Table(object):
     """The device table of a batch (include/gfla_spectral_norm.h) with the host numbers that go with it."""
 
-    def __init__(self, weights, us, vs):
+    def __init__(self, weights, us, vs, dims=None):
         n = len(weights)
         self.n = n
         self.shapes = [tuple(w.shape) for w in weights]
-        self.dims = (ctypes.c_int64 * (2 * n))()
+        # a batch of dim-0 matrices only: the entry points and the 8-word records it always had; otherwise the mixed ones,
+        # (R, K, inner) and 9 words per matrix
+        self.mixed = dims is not None and any(dims)
+        per = 3 if self.mixed else 2
+        self.entry = "gfla_spectral_norm_mixed_" if self.mixed else "gfla_spectral_norm_"
+        self.dims = (ctypes.c_int64 * (per * n))()
         for i, w in enumerate(weights):
-            self.dims[2 * i], self.dims[2 * i + 1] = w.size(0), w.numel() // max(w.size(0), 1)
+            self.dims[per * i: per * i + per] = _matrix_dims(w, dims[i] if self.mixed else 0)[:per]
         offsets, totals = (ctypes.c_int64 * (3 * n))(), (ctypes.c_int64 * 2)()
-        status = _lib.lib().gfla_spectral_norm_layout(ctypes.addressof(self.dims), n, ctypes.addressof(offsets),
-                                                      ctypes.addressof(totals))
+        status = getattr(_lib.lib(), self.entry + "layout")(ctypes.addressof(self.dims), n, ctypes.addressof(offsets),
+                                                            ctypes.addressof(totals))
         if status != 0:
             err = _lib.Unsupported if status == _lib._ERR_UNSUPPORTED else ValueError
             raise err("spectral_normalize: %s" % _lib.lib().gfla_status_string(status).decode())
         self.elems, self.vecs = int(totals[0]), int(totals[1])
         self.elem_off = [int(offsets[3 * i]) for i in range(n)]
-        self.bwd_scratch = int(_lib.lib().gfla_spectral_norm_bwd_scratch_floats(ctypes.addressof(self.dims), n))
-        rows = [[w.data_ptr(), u.data_ptr(), v.data_ptr(), self.dims[2 * i], self.dims[2 * i + 1], offsets[3 * i],
-                 offsets[3 * i + 1], offsets[3 * i + 2]] for i, (w, u, v) in enumerate(zip(weights, us, vs))]
+        self.bwd_scratch = int(getattr(_lib.lib(), self.entry + "bwd_scratch_floats")(ctypes.addressof(self.dims), n))
+        rows = [[w.data_ptr(), u.data_ptr(), v.data_ptr(), self.dims[per * i], self.dims[per * i + 1], offsets[3 * i],
+                 offsets[3 * i + 1], offsets[3 * i + 2]] + ([self.dims[per * i + 2]] if self.mixed else [])
+                for i, (w, u, v) in enumerate(zip(weights, us, vs))]
         self.device = weights[0].device
         self.table = torch.tensor(rows, dtype=torch.int64).to(self.device)
 
@@ -67,22 +80,30 @@ class _Table(object):
         return ctypes.c_void_p(ctypes.addressof(self.dims))
 
 
-def _table(weights, us, vs):
-    """the table of this batch: built once, rebuilt only when a pointer or a shape changes"""
+def _matrix_dims(w, dim):
+    """(R, K, inner) of the weight `w` normalised along `dim` (include/gfla_spectral_norm.h): inner 0 is dim 0, the matrix
+    as stored; dim 1 is (Cin, R, ...) with inner = the elements behind the first two axes"""
+    rows = w.size(dim)
+    return rows, w.numel() // max(rows, 1), 0 if dim == 0 else w.numel() // max(w.size(0) * rows, 1)
+
+
+def _table(weights, us, vs, dims=None):
+    """the table of this batch: built once, rebuilt only when a pointer, a shape or a dim changes"""
+    dims = None if dims is None or not any(dims) else tuple(dims)
     key = tuple((w.data_ptr(), u.data_ptr(), v.data_ptr(), tuple(w.shape)) for w, u, v in zip(weights, us, vs))
-    key = (weights[0].device, key)
+    key = (weights[0].device, key, dims)
     hit = _TABLE_CACHE.get(key)
     if hit is None:
         if len(_TABLE_CACHE) >= _TABLE_CACHE_MAX:
             _TABLE_CACHE.clear()
-        hit = _TABLE_CACHE[key] = _Table(weights, us, vs)
+        hit = _TABLE_CACHE[key] = _Table(weights, us, vs, dims)
     return hit
 
 
 class SpectralNormFunction(Function):
     """(table, power_iterations, eps, *weight_origs) -> (*W_sn) on the library's kernels: the whole batch in
-    2 power_iterations + 1 launches (2 in eval mode), the backward in 2.  u and v, the buffers the table points at, are
-    updated in place.  Saved per call: the u, v and sigma the outputs were computed with (written by the forward's own
+    2 power_iterations + 1 launches (2 in eval mode), the backward in 2, whether the table holds dim-0 matrices, dim-1
+    matrices or both.  u and v, the buffers the table points at, are updated in place.  Saved per call: the u, v and sigma the outputs were computed with (written by the forward's own
     launches), so that a backward after a later forward -- D(real), D(fake), one backward -- uses its own call's values."""
 
     @staticmethod
@@ -92,8 +113,9 @@ class SpectralNormFunction(Function):
         flat = torch.empty(table.elems, dtype=torch.float32, device=dev)
         sigma = torch.empty(table.n, dtype=torch.float32, device=dev)
         saved = torch.empty(table.vecs, dtype=torch.float32, device=dev) if needs else None
-        scratch = torch.empty(table.vecs, dtype=torch.float32, device=dev)
-        _lib.call("gfla_spectral_norm_fwd_f32", flat, _lib.ptr(table.table), table.dims_ptr(), table.n, _lib.ptr(flat),
+        # the mixed entry points keep the dim-1 matrices' t and s in float64 behind the float32 vector arrays
+        scratch = torch.empty(3 * table.vecs + 2 if table.mixed else table.vecs, dtype=torch.float32, device=dev)
+        _lib.call(table.entry + "fwd_f32", flat, _lib.ptr(table.table), table.dims_ptr(), table.n, _lib.ptr(flat),
                   _lib.ptr(sigma), _lib.ptr(saved), _lib.ptr(scratch), int(power_iterations), float(eps))
         ctx.table = table
         ctx.sigma = sigma
@@ -111,16 +133,20 @@ class SpectralNormFunction(Function):
         grad_sn = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
         grad_w = torch.empty(table.elems, dtype=torch.float32, device=table.device)
         scratch = torch.empty(max(table.bwd_scratch, 1), dtype=torch.float32, device=table.device)
-        _lib.call("gfla_spectral_norm_bwd_f32", grad_w, _lib.ptr(table.table), table.dims_ptr(), table.n, _lib.ptr(grad_sn),
+        _lib.call(table.entry + "bwd_f32", grad_w, _lib.ptr(table.table), table.dims_ptr(), table.n, _lib.ptr(grad_sn),
                   _lib.ptr(saved), _lib.ptr(sigma), _lib.ptr(grad_w), _lib.ptr(scratch))
         out = [grad_w[o:o + torch.Size(s).numel()].view(s) if need else None
                for o, s, need in zip(table.elem_off, table.shapes, ctx.needs_input_grad[3:])]
         return (None, None, None) + tuple(out)
 
 
-def torch_spectral_normalize(weight, u, v, power_iterations=1, eps=1e-12):
-    """One weight by the operations of torch's SpectralNorm.compute_weight (dim 0), in its order; u and v in place."""
-    weight_mat = weight.reshape(weight.size(0), -1)
+def torch_spectral_normalize(weight, u, v, power_iterations=1, eps=1e-12, dim=0):
+    """One weight by the operations of torch's SpectralNorm.compute_weight, in its order; u and v in place.  dim: the
+    hook's -- 0, or 1 for a transposed convolution, whose matrix is the hook's reshape_weight_to_matrix (a permute)."""
+    weight_mat = weight
+    if dim != 0:
+        weight_mat = weight_mat.permute(dim, *[d for d in range(weight_mat.dim()) if d != dim])
+    weight_mat = weight_mat.reshape(weight_mat.size(0), -1)
     if power_iterations > 0:
         with torch.no_grad():
             for _ in range(power_iterations):
@@ -141,29 +167,36 @@ def _kernel_batch(weights, us, vs):
     return True
 
 
-def spectral_normalize(weights, us, vs, power_iterations=1, eps=1e-12, impl="auto"):
+def spectral_normalize(weights, us, vs, power_iterations=1, eps=1e-12, impl="auto", dims=None):
     """[W / sigma for every weight (Cout, ...) of `weights`], with `power_iterations` rounds of the power iteration on the
     vectors us[i] (Cout) and vs[i] (the rest), updated in place; 0 (eval mode) leaves them untouched.  Arithmetic and
-    gradient (u, v, sigma constants) as torch.nn.utils.spectral_norm with dim 0.
+    gradient (u, v, sigma constants) as torch.nn.utils.spectral_norm.
+    dims: one 0 or 1 per weight, the hook's `dim`; None: all 0.  A weight with dim 1 is (Cin, Cout, ...), the layout of
+    an nn.ConvTranspose2d: u is (Cout,), v (numel / Cout,) in the order of weight.permute(1, 0, ...).reshape(Cout, -1), and
+    the result has the weight's own layout.  Both kinds go in one call.
     impl "auto": contiguous float32 GPU tensors run as ONE batched call on the kernels (SpectralNormFunction); anything
     else -- CPU, float64, 16-bit, sizes the library refuses -- and impl "torch" take torch_spectral_normalize per weight."""
     _lib.check_impl(impl)
     weights, us, vs = list(weights), list(us), list(vs)
+    dims = [0] * len(weights) if dims is None else [int(d) for d in dims]
+    if len(dims) != len(weights) or any(d not in (0, 1) for d in dims):
+        raise ValueError("spectral_normalize: dims is None or one 0 / 1 per weight (got %r)" % (dims,))
     if not (len(weights) == len(us) == len(vs)) or not weights:
         raise ValueError("spectral_normalize: as many us and vs as weights, at least one (got %d, %d, %d)"
                          % (len(weights), len(us), len(vs)))
     if int(power_iterations) < 0 or not float(eps) > 0:
         raise ValueError("spectral_normalize: power_iterations >= 0 and eps > 0 (got %r, %r)" % (power_iterations, eps))
-    for w, u, v in zip(weights, us, vs):
-        if w.dim() < 1 or w.numel() == 0 or tuple(u.shape) != (w.size(0),) or tuple(v.shape) != (w.numel() // w.size(0),):
-            raise ValueError("spectral_normalize: weight (R, ...), u (R,), v (K,) (got %s, %s, %s)"
+    for w, u, v, d in zip(weights, us, vs, dims):
+        if w.dim() <= d or w.numel() == 0 or tuple(u.shape) != (w.size(d),) or tuple(v.shape) != (w.numel() // w.size(d),):
+            raise ValueError("spectral_normalize: weight (R, ...) or with dim 1 (Cin, R, ...), u (R,), v (K,) (got %s, %s, %s)"
                              % (tuple(w.shape), tuple(u.shape), tuple(v.shape)))
     if impl == "auto" and _kernel_batch(weights, us, vs):
         try:
-            return list(SpectralNormFunction.apply(_table(weights, us, vs), int(power_iterations), float(eps), *weights))
+            return list(SpectralNormFunction.apply(_table(weights, us, vs, dims), int(power_iterations), float(eps), *weights))
         except _lib.Unsupported:
             pass
-    return [torch_spectral_normalize(w, u, v, int(power_iterations), float(eps)) for w, u, v in zip(weights, us, vs)]
+    return [torch_spectral_normalize(w, u, v, int(power_iterations), float(eps), d)
+            for w, u, v, d in zip(weights, us, vs, dims)]
 
 
 def _check_pointwise(pointwise):
@@ -184,7 +217,7 @@ class _Normalized(nn.Module):
     its order, the hook's numbers, and the weight that the network's batched call hands over."""
 
     def _adopt(self, conv, hook):
-        self.n_power_iterations, self.eps = int(hook.n_power_iterations), float(hook.eps)
+        self.n_power_iterations, self.eps, self.dim = int(hook.n_power_iterations), float(hook.eps), int(hook.dim)
         for name, p in conv._parameters.items():
             self.register_parameter(name, p)
         for name, b in conv._buffers.items():
@@ -204,7 +237,7 @@ class _Normalized(nn.Module):
         weight, self.__dict__["_handed"] = self.__dict__["_handed"], None
         if weight is None:
             weight = spectral_normalize([self.weight_orig], [self.weight_u], [self.weight_v], self.power_iterations(),
-                                        self.eps, self.impl)[0]
+                                        self.eps, self.impl, [self.dim])[0]
         return weight
 
 
@@ -218,10 +251,12 @@ class SpectralConv(_Normalized):
     s 1, p 0) runs through gen_conv.conv1x1 with pointwise="kernels" -- `pool` 2: behind the AvgPool2d(2) that
     fuse_spectral_norm folded in, which needs that route --, and with the default pointwise="torch" through F.conv2d on the
     normalised weight, as every other geometry does (groups, dilation, k 4 with s 1).
+    padding "reflect": `conv` is a Conv2d(k 3, s 1, p 0) that stood directly behind an nn.ReflectionPad2d(1) -- every Jump
+    of the reference's generators --, and the module stands for both: gen_conv.conv3x3(padding="reflect").
     Inside a forward of a network rewritten by fuse_spectral_norm the weight was normalised with all the others in one
     call; called on its own, the module normalises itself, a batch of one."""
 
-    def __init__(self, conv, pre_slope=None, impl="auto", grad="torch", pointwise="torch", pool=1):
+    def __init__(self, conv, pre_slope=None, impl="auto", grad="torch", pointwise="torch", pool=1, padding="zeros"):
         super(SpectralConv, self).__init__()
         _lib.check_impl(impl)
         check_grad(grad)
@@ -232,7 +267,10 @@ class SpectralConv(_Normalized):
                              "other hook")
         self.impl, self.grad = impl, grad
         self.pre_slope = None if pre_slope is None else float(pre_slope)
-        geometry = (conv_geometry(conv) or (None,))[0]
+        if padding not in PADDINGS or (padding == "reflect" and conv_geometry(conv, True) != (S1K3, "reflect")):
+            raise ValueError("SpectralConv: padding 'zeros', or 'reflect' for a Conv2d(k 3, s 1, p 0) (got %r)" % (padding,))
+        self.padding = padding
+        geometry = (conv_geometry(conv, padding == "reflect") or (None,))[0]
         self.geometry = geometry if geometry in (S1K3, S2K4) else None
         self.pointwise = pointwise == "kernels" and geometry == P1K1
         if pool not in _gc.POOLS or (pool == 2 and (not self.pointwise or pre_slope is not None)):
@@ -249,14 +287,94 @@ class SpectralConv(_Normalized):
             a = x if self.pre_slope is None else F.leaky_relu(x, self.pre_slope)
             return self.original._conv_forward(a, weight, self.bias)
         # a geometry of the kernels runs as its functional form does; only the others need the convolution's own
-        return _gc.run(geometry, x, weight, self.bias, "zeros", self.pre_slope, add, self.pool, self.impl, self.grad,
+        return _gc.run(geometry, x, weight, self.bias, self.padding, self.pre_slope, add, self.pool, self.impl, self.grad,
                        own if geometry is None else None)
+
+    @property
+    def fuses_add(self):                 # _rewrite.epilogue_slot: `add` goes into the epilogue of the 3x3 / 4x4 kernels
+        return self.geometry is not None
 
     def extra_repr(self):
         c = self.original
-        return "%d -> %d, kernel_size=%s, stride=%s, n_power_iterations=%d, pre_slope=%s, impl=%r, grad=%r%s" % (
+        return "%d -> %d, kernel_size=%s, stride=%s, n_power_iterations=%d, pre_slope=%s, impl=%r, grad=%r%s%s" % (
             c.in_channels, c.out_channels, tuple(c.kernel_size), tuple(c.stride), self.n_power_iterations, self.pre_slope,
-            self.impl, self.grad, ", pointwise='kernels', pool=%d" % self.pool if self.pointwise else "")
+            self.impl, self.grad, ", pointwise='kernels', pool=%d" % self.pool if self.pointwise else "",
+            ", padding='reflect'" if self.padding == "reflect" else "")
+
+
+class SpectralConvTranspose(_Normalized):
+    """[LeakyReLU(pre_slope)] -> the nn.ConvTranspose2d `conv` under torch's spectral_norm hook (+ add), with the
+    normalisation on the batched op.  torch normalises a transposed convolution along dim 1: the matrix is
+    weight.permute(1,0,2,3).reshape(Cout, -1), `weight_u` is (Cout,), `weight_v` (Cin kh kw,).  The kernels read that matrix
+    in the weight's storage (Cin, Cout, kh, kw), so the normalised weight is what the convolution takes, as it is.
+    SpectralConv's contract otherwise: conv's own `weight_orig`, `bias`, `weight_u`, `weight_v` under conv's names and in
+    conv's order, the hook's n_power_iterations and eps, one batched call for the whole network inside a forward of a
+    network rewritten by fuse_spectral_norm(generator=True).
+    ConvTranspose2d(k 3, s 2, p 1, output_padding 1) runs through gen_conv.run(T2K3, ...), i.e. conv_transpose3x3_up with
+    its dispatch (grad="kernels": the library's gradient kernels); every other geometry runs F.conv_transpose2d with conv's
+    own arguments on the normalised weight."""
+
+    def __init__(self, conv, pre_slope=None, impl="auto", grad="torch"):
+        super(SpectralConvTranspose, self).__init__()
+        _lib.check_impl(impl)
+        check_grad(grad)
+        hook = _rewrite.spectral_norm_hook(conv, dims=(1,))
+        if type(conv) is not nn.ConvTranspose2d or hook is None:
+            raise ValueError("SpectralConvTranspose: an nn.ConvTranspose2d under torch.nn.utils.spectral_norm (name 'weight', "
+                             "dim 1) and no other hook")
+        self.impl, self.grad = impl, grad
+        self.pre_slope = None if pre_slope is None else float(pre_slope)
+        self.geometry = T2K3 if conv_geometry(conv) == (T2K3, "zeros") else None
+        self._adopt(conv, hook)
+
+    def forward(self, x, add=None):
+        weight = self.normalized_weight()
+
+        def own(x):                      # the convolution's own arithmetic on the normalised weight
+            c = self.original
+            a = x if self.pre_slope is None else F.leaky_relu(x, self.pre_slope)
+            return F.conv_transpose2d(a, weight, self.bias, c.stride, c.padding, c.output_padding, c.groups, c.dilation)
+        return _gc.run(self.geometry, x, weight, self.bias, "zeros", self.pre_slope, add, 1, self.impl, self.grad,
+                       own if self.geometry is None else None)
+
+    @property
+    def fuses_add(self):                 # _rewrite.epilogue_slot
+        return self.geometry == T2K3
+
+    def extra_repr(self):
+        c = self.original
+        return "%d -> %d, kernel_size=%s, stride=%s, n_power_iterations=%d, pre_slope=%s, impl=%r, grad=%r" % (
+            c.in_channels, c.out_channels, tuple(c.kernel_size), tuple(c.stride), self.n_power_iterations, self.pre_slope,
+            self.impl, self.grad)
+
+
+class SpectralHead(_Normalized):
+    """[LeakyReLU(pre_slope)] -> ReflectionPad2d(1) -> the Conv2d(C, at most 8, 3) `conv` under torch's spectral_norm hook
+    -> [Tanh | Sigmoid] as one op: the reference's `Output` under spectral norm.  The normalised weight goes to
+    head_conv.head_conv3x3(x, W_sn, bias, "reflect", pre_slope, post), whose gradient reaches `weight_orig` through
+    SpectralNormFunction.  SpectralConv's contract otherwise (conv's own Parameters and buffers, names and order)."""
+
+    def __init__(self, conv, pre_slope=None, post=None, impl="auto"):
+        super(SpectralHead, self).__init__()
+        _lib.check_impl(impl)
+        hook = _rewrite.spectral_norm_hook(conv)
+        if type(conv) is not nn.Conv2d or hook is None or conv_geometry(conv, True) != (S1K3, "reflect") or \
+                conv.out_channels > _hc.MAX_COUT:
+            raise ValueError("SpectralHead: an nn.Conv2d(k 3, s 1, p 0) of at most %d output channels under "
+                             "torch.nn.utils.spectral_norm (name 'weight', dim 0) and no other hook" % _hc.MAX_COUT)
+        if post not in _hc.POSTS:
+            raise ValueError("SpectralHead: post is one of %s (got %r)" % (_hc.POSTS, post))
+        self.impl, self.post = impl, post
+        self.pre_slope = None if pre_slope is None else float(pre_slope)
+        self._adopt(conv, hook)
+
+    def forward(self, x):
+        return _hc.head_conv3x3(x, self.normalized_weight(), self.bias, "reflect", self.pre_slope, self.post, None, self.impl)
+
+    def extra_repr(self):
+        c = self.original
+        return "%d -> %d, n_power_iterations=%d, pre_slope=%s, post=%s, impl=%r" % (
+            c.in_channels, c.out_channels, self.n_power_iterations, self.pre_slope, self.post, self.impl)
 
 
 def conv3d_geometry(module):
@@ -412,20 +530,20 @@ def _normalize_all(convs, impl):
         groups.setdefault((c.power_iterations(), c.eps), []).append(c)
     for (iters, eps), members in groups.items():
         normed = spectral_normalize([c.weight_orig for c in members], [c.weight_u for c in members],
-                                    [c.weight_v for c in members], iters, eps, impl)
+                                    [c.weight_v for c in members], iters, eps, impl, [c.dim for c in members])
         for c, w in zip(members, normed):
             c.hand(w)
 
 
-def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch", temporal="torch"):
+def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch", temporal="torch", generator=False):
     """Rewrite, in place and recursively, every nn.Conv2d of `net` that carries torch.nn.utils.spectral_norm's hook (name
     "weight", dim 0) and no other: its slot becomes a SpectralConv with the same Parameter and buffer objects.  Indices
     and state-dict keys do not change.  Inside an nn.Sequential an nn.LeakyReLU directly in front is folded into the
     convolution (its slot becomes nn.Identity(); a shared activation object is left as it is: only slots change).
     One forward pre-hook on `net` normalises all rewritten convolutions in one batched call per forward and hands each
     its weight; a forward hook drops what a forward did not use.
-    Left alone, uncounted: ConvTranspose2d under spectral norm (dim 1), the convolution inside a CoordConv, modules with
-    any other hook.  grad: the `grad` of every SpectralConv ("kernels": the convolutions train on GenConvFunction).
+    Left alone, uncounted: ConvTranspose2d under spectral norm (dim 1) unless generator=True, the convolution inside a
+    CoordConv, modules with any other hook.  grad: the `grad` of every SpectralConv ("kernels": the convolutions train on GenConvFunction).
     pointwise "kernels": every rewritten Conv2d(k 1, s 1, p 0) runs gen_conv.conv1x1, and inside an nn.Sequential an
     nn.AvgPool2d(kernel 2, stride 2, padding 0, ceil_mode False, divisor_override None) directly in front of one is folded
     into it (the pool's slot becomes nn.Identity(), the convolution gets pool=2); a pool of any other geometry stays.  The
@@ -437,6 +555,17 @@ def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch", tempor
     block's forward (frames_major_block_forward) converts on the way in and out when it is called on its own.  The three
     weights join the one batched normalisation.  A block with norm layers, another pool, a CoordConv or a foreign hook is
     left alone, uncounted.  The default "torch" looks at no Conv3d, as before.
+    generator True: what a generator under spectral norm has besides.  Every nn.ConvTranspose2d under the hook (name
+    "weight", dim 1, no other hook) becomes a SpectralConvTranspose, an nn.LeakyReLU directly in front folded in.  Inside an
+    nn.Sequential a hooked Conv2d(k 3, s 1, p 0) directly behind an nn.ReflectionPad2d(1) becomes ONE module for both: with
+    more than 8 output channels a SpectralConv(padding="reflect") (the reference's Jump), with at most 8 a SpectralHead
+    (the reference's Output), which also absorbs an nn.Tanh / nn.Sigmoid directly behind; an nn.LeakyReLU in front of the
+    pad is folded in.  The slots of the pad, the activation in front and the absorbed post-activation become
+    nn.Identity().  nn.Sequential containers are visited first, so that a convolution also registered outside one (Jump
+    and Output keep theirs as `conv1` and `model.2`) is rewritten where its neighbours can be seen; the other name gets
+    the same module.  All weights, both dims, join the one batched call.  Left alone as before: CoordConv, foreign hooks;
+    and anything inside a module with a `fully_connect_layer` (ExtractorAttn).  The default False does exactly what the
+    function did before.
     Returns the number of convolutions rewritten."""
     _lib.check_impl(impl)
     check_grad(grad)
@@ -449,15 +578,50 @@ def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch", tempor
             found = _temporal_block(block)
             if found is not None and not any(id(c) in replaced for c in (found[0], found[1], found[3])):
                 _rewrite_temporal_block(block, found, impl, grad, replaced)
-    for parent in list(net.modules()):
-        if hasattr(parent, "addcoords"):                     # CoordConv: its convolution sees two more channels
+    parents, skip = list(net.modules()), set()
+    if generator:
+        parents.sort(key=lambda m: not isinstance(m, nn.Sequential))         # stable: containers first
+        for m in net.modules():
+            if hasattr(m, "fully_connect_layer"):
+                skip.update(id(sub) for sub in m.modules())
+    for parent in parents:
+        if hasattr(parent, "addcoords") or id(parent) in skip:   # CoordConv: its convolution sees two more channels
             continue
         names = list(parent._modules.keys())
+        in_seq = isinstance(parent, nn.Sequential)
         for i, name in enumerate(names):
             conv = parent._modules[name]
-            if type(conv) is not nn.Conv2d or id(conv) in replaced or _rewrite.spectral_norm_hook(conv) is None:
+            if conv is None or id(conv) in replaced:
                 continue
-            before = parent._modules[names[i - 1]] if isinstance(parent, nn.Sequential) and i >= 1 else None
+            if generator and type(conv) is nn.ConvTranspose2d and _rewrite.spectral_norm_hook(conv, dims=(1,)) is not None:
+                slope = _rewrite.slope_of(parent._modules[names[i - 1]], relu=False) if in_seq and i >= 1 else None
+                if slope is not None:
+                    parent._modules[names[i - 1]] = nn.Identity()
+                replaced[id(conv)] = (conv, SpectralConvTranspose(conv, slope, impl, grad))
+                parent._modules[name] = replaced[id(conv)][1]
+                continue
+            if type(conv) is not nn.Conv2d or _rewrite.spectral_norm_hook(conv) is None:
+                continue
+            pad = parent._modules[names[i - 1]] if generator and in_seq and i >= 1 else None
+            if pad is not None and _rewrite.is_reflect_pad(pad) and _rewrite.no_hooks(pad) and \
+                    conv_geometry(conv, True) == (S1K3, "reflect"):
+                slope = _rewrite.slope_of(parent._modules[names[i - 2]], relu=False) if i >= 2 else None
+                if conv.out_channels <= _hc.MAX_COUT:
+                    after = parent._modules[names[i + 1]] if i + 1 < len(names) else None
+                    post = None if after is None or not _rewrite.no_hooks(after) else \
+                        "tanh" if type(after) is nn.Tanh else "sigmoid" if type(after) is nn.Sigmoid else None
+                    fused = SpectralHead(conv, slope, post, impl)
+                    if post is not None:
+                        parent._modules[names[i + 1]] = nn.Identity()
+                else:
+                    fused = SpectralConv(conv, slope, impl, grad, pointwise, 1, "reflect")
+                parent._modules[names[i - 1]] = nn.Identity()
+                if slope is not None:
+                    parent._modules[names[i - 2]] = nn.Identity()
+                replaced[id(conv)] = (conv, fused)
+                parent._modules[name] = fused
+                continue
+            before = parent._modules[names[i - 1]] if in_seq and i >= 1 else None
             slope = _rewrite.slope_of(before, relu=False)
             pool = 2 if slope is None and pointwise == "kernels" and conv_geometry(conv) == (P1K1, "zeros") and \
                 _is_pool2(before) else 1
@@ -479,6 +643,30 @@ def fuse_spectral_norm(net, impl="auto", grad="torch", pointwise="torch", tempor
         handles = (net.register_forward_pre_hook(before), net.register_forward_hook(after, always_call=True))
         net.__dict__["_gfla_spectral_norm_hooks"] = handles
     return len(replaced)
+
+
+_REFERENCE_GENERATORS = ("PoseGenerator", "PoseFlowNetGenerator", "DanceGenerator", "FaceGenerator", "ShapeNetGenerator",
+                         "ShapeNetFlowNetGenerator")
+
+
+def patch_reference_generators(generator_module, base_function=None, impl="auto", grad="torch", pointwise="torch"):
+    """Wrap the constructors of the reference's PoseGenerator, PoseFlowNetGenerator, DanceGenerator, FaceGenerator,
+    ShapeNetGenerator and ShapeNetFlowNetGenerator (generator.py) so that every one built from now on comes out rewritten:
+    fuse_spectral_norm(generator=True) once on the finished network -- per network, so that all its convolutions, of the
+    flow net and of the target net, share ONE batched normalisation per forward, not one per block.  Given base_function,
+    ResBlock.forward and ResBlockDecoder.forward hand the residual to the last convolution's epilogue
+    (gen_conv.install_residual_forwards: the same forwards and the same flag patch_reference_convs installs).  A generator
+    built without spectral norm has nothing to rewrite and stays as it is.  Idempotent.  Returns the names of the classes
+    wrapped."""
+    _lib.check_impl(impl)
+    check_grad(grad)
+    _check_pointwise(pointwise)
+    wrapped = [name for name in _REFERENCE_GENERATORS
+               if _rewrite.wrap_init(getattr(generator_module, name, None), "_gfla_fuses_spectral_norm",
+                                     lambda self: fuse_spectral_norm(self, impl, grad, pointwise, generator=True))]
+    if base_function is not None:
+        wrapped += _gc.install_residual_forwards(base_function)
+    return wrapped
 
 
 _REFERENCE_DISCRIMINATORS = ("ResDiscriminator", "PatchDiscriminator", "TemporalDiscriminator")

@@ -35,7 +35,33 @@
  * matrix gives the same bits alone as in a batch.
  * NULL table, dims or outputs (offsets / totals; w_sn / sigma / scratch; grad_sn / saved / grad_w) -> -1; n <= 0, a
  * non-positive R or K, power_iterations < 0, eps <= 0 -> -2; n > 65535, R or K > 2^24, R K > 2^31 - 1 ->
- * GFLA_ERR_UNSUPPORTED, nothing is launched.  Additive: GFLA_ABI_VERSION stays 8. */
+ * GFLA_ERR_UNSUPPORTED, nothing is launched.  Additive: GFLA_ABI_VERSION stays 8.
+ *
+ * ---- matrices that are not their storage: the gfla_spectral_norm_mixed_* entry points ------------------------------------
+ * torch normalises an nn.ConvTranspose2d along dim 1: the matrix of a weight stored (Cin, Cout, kh, kw) is
+ * weight.permute(1,0,2,3).reshape(Cout, Cin kh kw).  With inner = kh kw it has R = Cout rows and K = Cin inner columns, and
+ * element (r, c) is at ((c / inner) R + r) inner + c % inner of the storage.  The mixed entry points take such matrices
+ * ("dim 1") and matrices read as stored ("dim 0") in one batch, with the arithmetic above on every one of them:
+ *   `dims`:  n x 3 int64 in HOST memory, (R_i, K_i, inner_i); inner_i = 0: dim 0, as stored; inner_i >= 1: dim 1.
+ *   `table`: n records of 9 int64: [0] .. [7] as above, [8] = inner_i.  u_i keeps R_i entries and v_i K_i entries, in the
+ *            matrix's own order (v: column c = ci inner + tap), so they are the buffers of torch's hook.
+ *   w_sn, grad_sn and grad_w hold matrix i at its element offset IN THE WEIGHT'S STORAGE LAYOUT: W_sn,i is the tensor a
+ *   transposed convolution takes as it is, and its weight gradient enters as it is.  No permuted copy exists anywhere.
+ * Layout, `saved`, the backward's scratch, status codes and limits as above; in addition a negative inner or a K that is
+ * no multiple of inner -> -2, inner > 25 -> GFLA_ERR_UNSUPPORTED.  scratch of gfla_spectral_norm_mixed_fwd_f32:
+ * 3 totals[1] + 2 floats, uninitialised (the float32 vector arrays, and behind them, at the next multiple of 8 bytes, the
+ * same vectors in float64 for the dim-1 matrices).
+ * Launches: the same as above whatever the batch holds -- 2 power_iterations + 1 forward (2 with power_iterations = 0),
+ * 2 backward; a workgroup takes the branch of its matrix.  Every pass of a dim-1 matrix reads the weight in storage
+ * order, consecutive lanes at consecutive addresses: the column sums take one slab W[ci] (R inner contiguous floats) per
+ * workgroup, each thread adding into its own LDS bin per tap, a wave then adding a tap's 256 bins in a fixed order; the
+ * row dots take max(1, 64 / inner) rows per workgroup, whose floats are one contiguous run in every slab, one lane per
+ * float, the four waves a quarter of the slabs each; the scale pass and <G, W> are element-wise; grad_w maps a storage
+ * offset back to (r, c).  The sums of a dim-1 matrix's forward are float64 on the float32 weight -- bins and per-row sums
+ * are serial where the dim-0 passes have a butterfly, and sigma = u . (W v) cancels on fresh buffers --: t, s and both
+ * norms stay float64 between the launches, u, v and sigma are each rounded to float32 once.  The order of every sum is fixed by (R, K, inner) alone: bit-identical from call to call and for
+ * a matrix alone or in any batch, and a dim-0 matrix gives the bits the dim-0 entry points give (which run the same
+ * kernels on 8-word records).  u and v are written by one workgroup per matrix in launches in which nobody reads them. */
 #ifndef GFLA_SPECTRAL_NORM_H_
 #define GFLA_SPECTRAL_NORM_H_
 
@@ -45,5 +71,12 @@ int gfla_spectral_norm_fwd_f32(const void *table, const int64_t *dims, int64_t n
                                float *scratch, int power_iterations, double eps, gfla_stream_t stream);
 int gfla_spectral_norm_bwd_f32(const void *table, const int64_t *dims, int64_t n, const float *grad_sn, const float *saved,
                                const float *sigma, float *grad_w, float *scratch, gfla_stream_t stream);
+int gfla_spectral_norm_mixed_layout(const int64_t *dims, int64_t n, int64_t *offsets, int64_t *totals);
+int64_t gfla_spectral_norm_mixed_bwd_scratch_floats(const int64_t *dims, int64_t n);
+int gfla_spectral_norm_mixed_fwd_f32(const void *table, const int64_t *dims, int64_t n, float *w_sn, float *sigma,
+                                     float *saved, float *scratch, int power_iterations, double eps, gfla_stream_t stream);
+int gfla_spectral_norm_mixed_bwd_f32(const void *table, const int64_t *dims, int64_t n, const float *grad_sn,
+                                     const float *saved, const float *sigma, float *grad_w, float *scratch,
+                                     gfla_stream_t stream);
 
 #endif /* GFLA_SPECTRAL_NORM_H_ */
