@@ -33,6 +33,8 @@ from .pose_inputs import (PoseInputs, normalize_images, pose_cords, pose_maps, t
                           torch_pose_cords, torch_pose_maps)
 from .image_inputs import (affine_images, augmentation_matrices, resize_images, torch_affine_images,  # noqa: F401
                            torch_resize_images)
+from .recon_metrics import (ReconstructionMetrics, images_to_uint8, reconstruction_metrics,  # noqa: F401
+                            torch_images_to_uint8, torch_reconstruction_metrics)
 from .install import install  # noqa: F401
 from .trainer import TrainerShell, load_reference_checkpoint  # noqa: F401
 from .face_step import (DualStreamAttn, MaskBlendFunction, face_target_forward, generate_frames,  # noqa: F401

@@ -4,7 +4,8 @@ include/gfla_hip.h is the single description of the C ABI: the argument and retu
 dispatch-trace ids (enum gfla_path -> PATH_*), the tuning keys (enum gfla_tuning_key -> TUNE_*), the status codes and
 ABI_VERSION are read from it, never restated here.
 Headers it includes (include/gfla_gen_conv.h, include/gfla_lds_plane.h, include/gfla_spectral_norm.h,
-include/gfla_conv3d.h, include/gfla_adam.h, include/gfla_pose.h, include/gfla_image.h) are read in the same way.
+include/gfla_conv3d.h, include/gfla_adam.h, include/gfla_pose.h, include/gfla_image.h, include/gfla_metrics.h) are read in
+the same way.
 
 The library is the only implementation of the ops: there is no Python/torch fallback.  If it
 is missing or fails to load, importing an op raises; if a call returns a non-zero status, a
@@ -25,7 +26,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfla_hip.h")   # c
 # headers gfla_hip.h includes, in the same dialect: their entry points are bound as well (extension_symbols)
 EXTENSION_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), name) for name in ("gfla_gen_conv.h", "gfla_lds_plane.h",
                                                                                             "gfla_spectral_norm.h", "gfla_conv3d.h", "gfla_adam.h", "gfla_pose.h",
-                                                                                            "gfla_image.h"))
+                                                                                            "gfla_image.h", "gfla_metrics.h"))
 _lib = None
 
 # the types the ABI is written in; a pointer of any pointee crosses as c_void_p

@@ -995,6 +995,10 @@ int gfla_head_conv3x3_bwd_bf16(const uint16_t *x, const float *w, const uint16_t
  * (csrc/image_inputs.hip): gfla_affine_images_*, gfla_resize_pass_u8, declared and documented in gfla_image.h ---- */
 #include "gfla_image.h"
 
+/* ---- reconstruction metrics: generator output -> bytes, SSIM (uniform and Gaussian window), PSNR, L1, MAE of byte images
+ * (csrc/recon_metrics.hip): gfla_images_to_uint8_*, gfla_recon_metrics*, declared and documented in gfla_metrics.h ---- */
+#include "gfla_metrics.h"
+
 #ifdef __cplusplus
 }
 #endif
